@@ -21,18 +21,27 @@ step     : one pass of the hot path over one batch of `--tiles` tiles per GPU, H
            volumes are gathered on rank 0 over RCCL / xGMI and leave through rank 0's link (one writer, as the north
            star's "gather of per-chunk logits").
 value    = tiles * 128^3 * N * K / (max over ranks of the wall time of K steps), in Mvox/s.  Weak scaling.
-           `config.device_resident_value` is the same K steps with inputs and outputs left in HBM (kernel throughput).
 
-Extra objects on the JSON line: `roofline` for the dominant kernel (the 3x3x3 MFMA convolution; live HIP-event
-timings recorded on the launch stream inside the timed region), `network` (whole-net HBM-roofline fraction) and
-`cpu_baseline` (the torch-CPU fp32 oracle on a bounded sample on this box's host cores, rank 0, N = 1 only, plus the
-margin-safe / margin-unsafe split of every label disagreement between the HIP path and that oracle).
+A plain run sets up, warms up, times the K steps and prints the JSON line; nothing else runs on the GPU.
+
+--full   also measures, in the same process (the timed region then carries the per-launch HIP events and clock stamps):
+         `config.device_resident_value` (the same K steps with inputs and outputs left in HBM: kernel throughput),
+         `config.single_tile_ms` and the reference-precision plan's rate, `roofline` for the dominant kernel (the 3x3x3 MFMA
+         convolution; live HIP-event timings recorded on the launch stream inside the timed region, plus a pure MFMA loop on
+         the same GPU), `network` (whole-net HBM-roofline fraction) and `cpu_baseline` (the torch-CPU fp32 oracle on a bounded
+         sample on the host's cores, rank 0, N = 1 only, plus the margin-safe / margin-unsafe split of every label
+         disagreement between the HIP path and that oracle; --no-cpu-baseline leaves out this and the single-tile and
+         reference-precision rates).
+--dump-outputs DIR   after the timed steps, writes what the last timed step handed its caller (rank 0's host label volumes,
+         or the result volume of a volume workload) to DIR/<name>.npy in float32 (dump_outputs: a fixed, seeded sample of at
+         most 2^23 values per array).  Inputs and weights are seeded: the same arguments give the same inputs on every run.
 """
 import argparse
 import json
 import os
 import sys
 import time
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
@@ -43,18 +52,41 @@ sys.path.insert(0, ROOT)
 PEAK_HBM_GBS = 8000.0        # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8 TB/s
 PEAK_MFMA_TFLOPS = 2500.0    # dense bf16/f16 MFMA
 BENCH_FINAL_SCALE = 8.0      # scale of the random final 1x1x1 weights (spreads the class logits)
+DUMP_MAX_VALUES = 1 << 23    # values per array written by --dump-outputs (32 MiB of float32)
 
 
 def synthetic_em_tiles(n, size, seed):
-    """Structured synthetic EM: Gaussian-filtered (sigma 2) uniform noise rescaled to 0..255."""
+    """Structured synthetic EM: Gaussian-filtered (sigma 2) uniform noise rescaled to 0..255.  The noise is drawn
+    tile by tile from one generator; the filtering of a group of tiles runs on threads (scipy releases the GIL), which leaves
+    every value as a serial loop computes it."""
     from scipy.ndimage import gaussian_filter
     rng = np.random.default_rng(seed)
     out = np.empty((n, size, size, size), np.uint8)
-    for i in range(n):
-        v = gaussian_filter(rng.random((size, size, size), dtype=np.float32), 2.0)
+
+    def finish(i, noise):
+        v = gaussian_filter(noise, 2.0)
         v = (v - v.min()) / (v.max() - v.min())
         out[i] = (v * 255).astype(np.uint8)
+
+    workers = max(1, min(16, len(os.sched_getaffinity(0)) if hasattr(os, 'sched_getaffinity') else (os.cpu_count() or 1), n))
+    with ThreadPoolExecutor(workers) as ex:
+        for i0 in range(0, n, workers):
+            group = [(i, rng.random((size, size, size), dtype=np.float32)) for i in range(i0, min(n, i0 + workers))]
+            for f in [ex.submit(finish, i, noise) for i, noise in group]:
+                f.result()
     return out
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array of `arrays` (name -> what the timed path handed its caller) as <out_dir>/<name>.npy in float32 --
+    whole when it holds at most DUMP_MAX_VALUES values, else the values at DUMP_MAX_VALUES flat positions drawn from a fixed seed
+    (sorted; the same positions for the same shape on every run), so that two builds can be compared output for output."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.size > DUMP_MAX_VALUES:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).integers(0, a.size, DUMP_MAX_VALUES))]
+        np.save(os.path.join(out_dir, name + '.npy'), a.astype(np.float32))
 
 
 def layer_accounting(ops, L, D, H, W, act_bytes=2, out_bytes_per_class=1):
@@ -218,8 +250,13 @@ def timed(fn_step, fn_drain, steps, par, dev):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=20)
+    ap.add_argument('--steps', type=int, default=None, help='timed steps (default: 20; volume workloads: 2)')
     ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--full', action='store_true',
+                    help='also the device-resident rate, single-tile and reference-precision rates, roofline / network figures and '
+                         'the CPU baseline (module docstring); a plain run times the K steps only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed to DIR/<name>.npy (float32, seeded sample of large arrays)')
     ap.add_argument('--tiles', type=int, default=96, help='128^3 tiles per GPU per step (96 tiles in launch sets of 8: 20 steps are a\n'
                     '                    timed region of >= 1.3 s -- long enough for the clock to settle and for an SMI sampler to see the load)')
     ap.add_argument('--tile', type=int, default=128)
@@ -245,6 +282,7 @@ def main():
     if args.workload != 'config2':
         return volume_main(args)
     args.act = args.act or 'bf16'
+    args.steps = 20 if args.steps is None else args.steps
 
     from syconn_amd import _lib as L
     from syconn_amd import parallel as par
@@ -282,12 +320,59 @@ def main():
     for _ in range(args.warmup):
         pipe.step()
     pipe.drain()
-    dm.profile(nbatch * args.steps)              # event ring: every launch set of the timed region keeps its own slot
+    if args.full:
+        dm.profile(nbatch * args.steps)          # event ring: every launch set of the timed region keeps its own slot
     elapsed = timed(pipe.step, pipe.drain, args.steps, par, dev)
     rank_seconds = list(timed.rank_seconds)
     vox_total = float(T) * S ** 3 * world * args.steps
     value = vox_total / elapsed / 1e6
+    pipe.drain()
+    last = pipe.out_host[(pipe.k - 1) & 1]        # the label volumes of the LAST step as they arrived in rank 0's host memory, rank by rank
 
+    labels_sha = None
+    if rank == 0 and args.labels_sha:
+        # (tests compare an N-rank run with the same tiles predicted by one rank)
+        import hashlib
+        labels_sha = hashlib.sha256(last.numpy().tobytes()).hexdigest()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {'labels': last.numpy()})
+
+    roof = net = cpu = None
+    more = dict.fromkeys(('single_tile_ms', 'single_tile_mvox_per_s', 'reference_precision_f16x2_mvox_per_s',
+                          'reference_precision_f16x2_ms_per_tile', 'device_resident_value', 'device_resident_ms_per_step'))
+    if args.full:
+        roof, net, cpu, more = full_report(args, L, sd, dm, tiles_host, ids, thr, B, nbatch, vox_total, pipe, dev, par, rank, world)
+    if rank == 0:
+        line = {'metric': 'segmented Mvoxels/s (whole node), 128^3 EM tiles', 'value': value, 'unit': 'Mvox/s',
+                'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
+                'ms_per_step': elapsed / args.steps * 1e3, 'higher_is_better': True, 'scaling': 'weak',
+                'vs_baseline': None, 'dtype': args.act, 'data': 'synthetic',
+                'config': {'workload': f'BASELINE configs[1]: {args.arch} 3D U-Net on {S}^3 uint8 tiles, {T} tiles per GPU '
+                                       f'per step in launch sets of {B} (sd_forward_labels_batch), random-init weights, '
+                                       f'HOST TO HOST: pinned host uint8 tiles -> H2D -> kernels -> '
+                                       + ('pinned host uint8 labels (stored by the last kernel, no copy)' if pipe.zero_copy
+                                          else 'D2H -> pinned host uint8 labels')
+                                       + (f' x{pipe.d2h_repeat}' if pipe.d2h_repeat > 1 else '') + ', 3 HIP streams, 2 buffer sets',
+                           'tiles_per_launch_set': B,
+                           'tiles_per_gpu_per_step': T, 'tile': [S, S, S], 'parallelism': f'tile-sharded x{world}',
+                           'hip_streams_per_gpu': 3,
+                           'collective': 'RCCL gather of uint8 labels to rank 0, D2H there' if par.collectives_active() else 'none',
+                           **more,
+                           'pcie_bytes_per_step_each_way': T * S ** 3, 'labels_sha256': labels_sha},
+                'roofline': roof, 'network': net, 'cpu_baseline': cpu,
+                'distributed': dict(dist_info(par), rank_ms_per_step=[round(v / args.steps * 1e3, 3) for v in rank_seconds])}
+        print(json.dumps(line))
+    if par.collectives_active():
+        par.barrier()
+        torch.distributed.destroy_process_group()
+
+
+def full_report(args, L, sd, dm, tiles_host, ids, thr, B, nbatch, vox_total, pipe, dev, par, rank, world):
+    """--full, after the timed region (every rank): per-kernel HIP-event times and clock stamps of the timed launch sets, the same K
+    steps device-resident, single-tile and reference-precision rates, roofline / network figures and the CPU baseline.
+    -> (roofline, network, cpu_baseline, the rates that go into `config`)."""
+    T, S = tiles_host.shape[0], tiles_host.shape[1]
+    from syconn_amd.engine import DenseModel
     # ---- per-kernel timings from the HIP events recorded inside the timed region (rank 0) ----------------------
     per_op = np.zeros(dm.n_ops)
     n_fw = nbatch * args.steps
@@ -422,41 +507,12 @@ def main():
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args, sd, dm, tiles_host[:B], ids, L)
 
-    labels_sha = None
-    if rank == 0 and args.labels_sha:
-        # checksum of the label volumes of the LAST step as they arrived in rank 0's host memory, rank by rank (tests compare
-        # an N-rank run with the same tiles predicted by one rank)
-        import hashlib
-        pipe.drain()
-        labels_sha = hashlib.sha256(pipe.out_host[(pipe.k - 1) & 1].numpy().tobytes()).hexdigest()
-    if rank == 0:
-        line = {'metric': 'segmented Mvoxels/s (whole node), 128^3 EM tiles', 'value': value, 'unit': 'Mvox/s',
-                'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
-                'ms_per_step': elapsed / args.steps * 1e3, 'higher_is_better': True, 'scaling': 'weak',
-                'vs_baseline': None, 'dtype': args.act, 'data': 'synthetic',
-                'config': {'workload': f'BASELINE configs[1]: {args.arch} 3D U-Net on {S}^3 uint8 tiles, {T} tiles per GPU '
-                                       f'per step in launch sets of {B} (sd_forward_labels_batch), random-init weights, '
-                                       f'HOST TO HOST: pinned host uint8 tiles -> H2D -> kernels -> '
-                                       + ('pinned host uint8 labels (stored by the last kernel, no copy)' if pipe.zero_copy
-                                          else 'D2H -> pinned host uint8 labels')
-                                       + (f' x{pipe.d2h_repeat}' if pipe.d2h_repeat > 1 else '') + ', 3 HIP streams, 2 buffer sets',
-                           'tiles_per_launch_set': B,
-                           'tiles_per_gpu_per_step': T, 'tile': [S, S, S], 'parallelism': f'tile-sharded x{world}',
-                           'hip_streams_per_gpu': 3,
-                           'collective': 'RCCL gather of uint8 labels to rank 0, D2H there' if par.collectives_active() else 'none',
-                           'single_tile_ms': single_tile_ms,
-                           'single_tile_mvox_per_s': None if single_tile_ms is None else S ** 3 / single_tile_ms / 1e3,
-                           'reference_precision_f16x2_mvox_per_s': None if ref_prec is None else S ** 3 / ref_prec / 1e3,
-                           'reference_precision_f16x2_ms_per_tile': ref_prec,
-                           'device_resident_value': value_res,
-                           'device_resident_ms_per_step': elapsed_res / args.steps * 1e3,
-                           'pcie_bytes_per_step_each_way': T * S ** 3, 'labels_sha256': labels_sha},
-                'roofline': roof, 'network': net, 'cpu_baseline': cpu,
-                'distributed': dict(dist_info(par), rank_ms_per_step=[round(v / args.steps * 1e3, 3) for v in rank_seconds])}
-        print(json.dumps(line))
-    if par.collectives_active():
-        par.barrier()
-        torch.distributed.destroy_process_group()
+    return roof, net, cpu, {'single_tile_ms': single_tile_ms,
+                            'single_tile_mvox_per_s': None if single_tile_ms is None else S ** 3 / single_tile_ms / 1e3,
+                            'reference_precision_f16x2_mvox_per_s': None if ref_prec is None else S ** 3 / ref_prec / 1e3,
+                            'reference_precision_f16x2_ms_per_tile': ref_prec,
+                            'device_resident_value': value_res,
+                            'device_resident_ms_per_step': elapsed_res / args.steps * 1e3}
 
 
 # ---- BASELINE configs[2..4]: whole volumes, chunk-parallel ------------------------------------------------------------
@@ -534,7 +590,7 @@ def volume_main(args):
     # (the result arrives in ONE page-locked host tensor, reused by every step: rank 0's part of a step is two contiguous PCIe streams,
     # volume in and result out -- chunk + halo boxes are cut and results placed on its GPU, parallel.predict_volume_distributed)
     res_host = torch.empty((1, *vol_shape), dtype=torch.uint8).pin_memory() if rank == 0 else None
-    steps, warm = (args.steps if args.steps != 20 else 2), min(args.warmup, 1)
+    steps, warm = (2 if args.steps is None else args.steps), min(args.warmup, 1)
     # rounds dealt from a cost-sorted chunk list (cost = voxels of all windows the chunk's predicted tiles run on, from geometry):
     # the chunks of a lock-step round then cost the same (parallel.predict_volume_distributed; --zmajor-rounds: the old order)
     cm = pred.chunk_cost_model(halo, in_halo, skip_outside)
@@ -550,6 +606,8 @@ def volume_main(args):
     rank_seconds = list(timed.rank_seconds)
     if pred.overflowed():
         raise SystemExit('fp16 activation overflow during the volume workload: rerun with bf16')
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {'labels' if ncls > 2 else 'proba_u8_channel1': out[0].numpy()})
     nvox = float(np.prod(vol_shape))
     if rank == 0:
         nchunks = int(np.prod([-(-v // c) for v, c in zip(vol_shape, chunk)]))

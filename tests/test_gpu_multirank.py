@@ -50,7 +50,7 @@ def test_bench_two_ranks_default_workload(gpu):
     """`bench.py --gpus 2` as the driver launches it (HostToHostPipeline with the gather branch): rc 0, one JSON line with
     n_gpus 2, and the label volumes that arrived in rank 0's host memory equal what ONE rank computes for the same tiles."""
     line = _json_line(_torchrun(2, ['bench.py', '--gpus', '2', '--steps', '2', '--warmup', '1', '--tiles', '2', '--no-cpu-baseline',
-                                    '--labels-sha'], {'SD_BENCH_ONE_GPU_DEBUG': '1'}))
+                                    '--labels-sha', '--full'], {'SD_BENCH_ONE_GPU_DEBUG': '1'}))
     assert line['n_gpus'] == 2 and line['steps'] == 2 and line['value'] > 0 and line['scaling'] == 'weak'
     assert line['roofline']['frac'] > 0 and line['config']['labels_sha256']
     from bench import BENCH_FINAL_SCALE, synthetic_em_tiles
@@ -189,3 +189,29 @@ def test_bench_default_and_volume_workload_through_rccl_group_of_one(gpu):
         assert plain['config']['collective'] == 'none' and rccl['config']['collective'].startswith('RCCL')
         assert plain['distributed']['backend'] is None and rccl['distributed']['backend'] == 'nccl' and rccl['distributed']['rccl_version']
         assert plain['config']['labels_sha256'] and plain['config']['labels_sha256'] == rccl['config']['labels_sha256']
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_one(gpu, tmp_path):
+    """A plain `bench.py` run (no --full) times exactly --steps steps and leaves the --full figures out; --dump-outputs writes the
+    label volume of the last timed step (the one --labels-sha hashes), the same file on a second run (seeded inputs).  A volume
+    workload honours --steps too and dumps its result volume."""
+    args = [sys.executable, 'bench.py', '--gpus', '1', '--steps', '3', '--warmup', '1', '--tiles', '2', '--batch', '2', '--labels-sha']
+    runs = []
+    for k in range(2):
+        d = tmp_path / f'run{k}'
+        line = _json_line(_run(args + ['--dump-outputs', str(d)]))
+        assert line['steps'] == 3 and line['ms_per_step'] > 0 and line['value'] > 0
+        assert line['roofline'] is None and line['cpu_baseline'] is None and line['config']['device_resident_value'] is None
+        lab = np.load(d / 'labels.npy')
+        assert lab.dtype == np.float32 and lab.shape == (1, 2, 128, 128, 128)
+        assert hashlib.sha256(lab.astype(np.uint8).tobytes()).hexdigest() == line['config']['labels_sha256']
+        runs.append(lab)
+    assert np.array_equal(runs[0], runs[1])
+    d = tmp_path / 'volume'
+    line = _json_line(_run([sys.executable, 'bench.py', '--gpus', '1', '--workload', 'config3', '--volume', '160', '224', '224',
+                            '--steps', '3', '--warmup', '0', '--dump-outputs', str(d)]))
+    assert line['steps'] == 3
+    files = sorted(os.listdir(d))
+    assert len(files) == 1 and files[0].endswith('.npy')
+    vol = np.load(d / files[0])
+    assert vol.dtype == np.float32 and vol.shape == (1, 160, 224, 224) and vol.min() >= 0 and vol.max() <= 255
