@@ -363,6 +363,33 @@ size_t sd_gauss_workspace_bytes(int X, int Y, int Z);
 int sd_gaussian_threshold(const uint8_t* prob_dev, int X, int Y, int Z, const double* sigma_xyz, double threshold,
                           uint8_t* mask_dev, float* smoothed_dev, void* workspace_dev, size_t ws_bytes, void* stream);
 
+/* ---- contact sites (/root/reference/syconn/extraction/cs_extraction_steps.py:317-495) ----------
+ * detect_seg_boundaries (/root/reference/syconn/extraction/find_object_properties.py:424-455): mask_dev (X,Y,Z) uint8 = 1 where a
+ * non-zero voxel of seg_dev (uint32, z fastest) has an in-array 6-neighbour of another value (0 included), else 0. */
+int sd_seg_boundaries(const uint32_t* seg_dev, int X, int Y, int Z, uint8_t* mask_dev, void* stream);
+/* process_block_nonzero + kernel (/root/reference/syconn/extraction/block_processing_C.pyx:21-75): valid convolution of the
+ * (sx,sy,sz) stencil (odd extents) over seg_dev; out_dev uint64 (X-sx+1, Y-sy+1, Z-sz+1).  For a centre with edges_dev != 0 the
+ * most frequent id of its window other than 0 and the centre id c wins (ties: the smallest id), out = (min(c,k) << 32) | max(c,k);
+ * 0 when the window holds no other id or the centre is not flagged.  Exact for any number of distinct ids per window (windows
+ * with more than 8 go through an exact second kernel).  Stencils up to (sx+7)(sy+7)(sz+15) <= 16384 and sx*sy*sz <= 4096.
+ * Workspace: sd_contact_partners_workspace_bytes(). */
+size_t sd_contact_partners_workspace_bytes(void);
+int sd_contact_partners(const uint8_t* edges_dev, const uint32_t* seg_dev, int X, int Y, int Z, int sx, int sy, int sz,
+                        uint64_t* out_dev, void* workspace_dev, size_t ws_bytes, void* stream);
+/* The closing loop of _contact_site_extraction_thread (cs_extraction_steps.py:437-461) on a contact volume c0_dev (uint64, X,Y,Z):
+ * per site id, res = binary_dilation^n_dilate(binary_closing^n_close(c0 == id)) (6-connected cross, border_value 0) computed inside
+ * the site's box only, and background voxels of c0 inside res take the id.  Where several sites claim a voxel the SMALLEST id wins
+ * (the reference's order is that of an unordered_map: DESIGN.md section 7).  One call handles a batch of sites:
+ *   table_dev  int64[n_obj][8]: id, box origin x, y, z, box extent x, y, z (the reference's [max(lo - n_close, 0), hi + n_close)
+ *              clipped at the array end), offset of the box in the workspace planes (ascending; boxes packed without gaps);
+ *   tot_vox    summed box volume of the batch; workspace >= 2 * tot_vox bytes;
+ *   flags      SD_CS_FIRST: out = c0 before the batch (first batch); SD_CS_LAST: unclaimed voxels become 0 (last batch).
+ * Voxels that are non-zero in c0 keep their value.  The id 2^64 - 1 is reserved (it marks unclaimed voxels): no site may carry
+ * it (packed cell pairs never do). */
+enum sd_cs_flags { SD_CS_FIRST = 1, SD_CS_LAST = 2 };
+int sd_cs_close_dilate(const uint64_t* c0_dev, int X, int Y, int Z, const int64_t* table_dev, int64_t n_obj, int64_t tot_vox,
+                       int n_close, int n_dilate, int flags, uint64_t* out_dev, void* workspace_dev, size_t ws_bytes, void* stream);
+
 /* ---- host-side helpers of the chunk pipeline (no GPU) -----------------------------------------------------------------
  * Multi-threaded strided copy of an (nz, ny, nx)-byte box between two uint8 host arrays whose x-rows are contiguous
  * (strides in bytes), and a multi-threaded memset: what numpy slicing does on one core when the reference cuts a chunk

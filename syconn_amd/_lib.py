@@ -11,6 +11,7 @@ SD_U8, SD_F32, SD_BF16, SD_F16, SD_U64, SD_U32, SD_F16X2 = 0, 1, 2, 3, 4, 5, 6
 SD_OUT_LOGITS_F32, SD_OUT_PROBS_F32, SD_OUT_PROBS_U8 = 0, 1, 2
 SD_OP_CONV, SD_OP_POOL, SD_OP_UPCONV, SD_OP_GROUPNORM, SD_OP_FINAL = 1, 2, 3, 4, 5
 SD_MOP_OPENING, SD_MOP_CLOSING, SD_MOP_DILATION, SD_MOP_EROSION = 1, 2, 3, 4
+SD_CS_FIRST, SD_CS_LAST = 1, 2
 
 LIB_NAME = 'libsyconn_dense_hip.so'
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), os.environ.get('SD_LIB_NAME', LIB_NAME))
@@ -24,7 +25,8 @@ EXPORTS = ['sd_init', 'sd_device_count', 'sd_model_create', 'sd_model_destroy', 
            'sd_segstats_compact_pairs', 'sd_objseg_workspace_bytes', 'sd_object_segmentation', 'sd_objseg_watershed_workspace_bytes',
            'sd_object_segmentation_watershed', 'sd_marker_flood', 'sd_host_box_copy', 'sd_host_zero', 'sd_plan_clip_window',
            'sd_gauss_workspace_bytes', 'sd_gaussian_threshold', 'sd_model_set_roi', 'sd_labels_make_unique', 'sd_labels_box_lut',
-           'sd_chunkprops_append', 'sd_chunkpairs_append', 'sd_propmerge_temp_bytes', 'sd_propmerge_objects', 'sd_propmerge_pairs', 'sd_profile_read_clocks', 'sd_probe_mfma_rate', 'sd_memcpy2d_async']
+           'sd_chunkprops_append', 'sd_chunkpairs_append', 'sd_propmerge_temp_bytes', 'sd_propmerge_objects', 'sd_propmerge_pairs', 'sd_profile_read_clocks', 'sd_probe_mfma_rate', 'sd_memcpy2d_async',
+           'sd_seg_boundaries', 'sd_contact_partners_workspace_bytes', 'sd_contact_partners', 'sd_cs_close_dilate']
 
 
 class OpDesc(C.Structure):
@@ -124,6 +126,11 @@ def load():
     lib.sd_host_zero.argtypes = [vp, i64, i32]; lib.sd_host_zero.restype = i32
     lib.sd_plan_clip_window.argtypes = [C.POINTER(OpDesc), i32, i32, i32, i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]
     lib.sd_plan_clip_window.restype = i32
+    lib.sd_seg_boundaries.argtypes = [vp, i32, i32, i32, vp, vp]; lib.sd_seg_boundaries.restype = i32
+    lib.sd_contact_partners_workspace_bytes.argtypes = []; lib.sd_contact_partners_workspace_bytes.restype = sz
+    lib.sd_contact_partners.argtypes = [vp, vp] + [i32] * 6 + [vp, vp, sz, vp]; lib.sd_contact_partners.restype = i32
+    lib.sd_cs_close_dilate.argtypes = [vp, i32, i32, i32, vp, i64, i64, i32, i32, i32, vp, vp, sz, vp]
+    lib.sd_cs_close_dilate.restype = i32
     _lib = lib
     return lib
 

@@ -229,3 +229,85 @@ def map_subcell_C(ch, subcell_chs):
     subs = [subcell_chs[i] for i in range(len(subcell_chs))]
     r = segstats(ch, subs, want_props=False)
     return [_pair_dict(*p) for p in r.pairs]
+
+
+# ---- contact sites (block_processing_C.pyx:21-75, find_object_properties.py:424-472 of the reference) -------------------------
+def _cs_device(device=None) -> torch.device:
+    lib = L.load()
+    if not torch.cuda.is_available():
+        raise RuntimeError('syconn_amd: no MI355X visible to PyTorch-ROCm; this package has no CPU fallback')
+    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    L.check(lib.sd_init(dev.index or 0), 'sd_init')
+    return dev
+
+
+def _u32_volume(arr, device) -> torch.Tensor:
+    """uint32 (X, Y, Z) volume -> contiguous int32 device tensor (the same bits)."""
+    if isinstance(arr, np.ndarray):
+        if arr.dtype != np.uint32:
+            raise TypeError(f'the cell segmentation must be uint32, got {arr.dtype}')
+        t = torch.from_numpy(np.ascontiguousarray(arr).view(np.int32)).to(device)
+    else:
+        if arr.dtype not in (torch.uint32, torch.int32):
+            raise TypeError(f'the cell segmentation must be a 32-bit integer tensor, got {arr.dtype}')
+        t = arr.view(torch.int32).to(device).contiguous()
+    if t.dim() != 3:
+        raise ValueError('the segmentation must be 3D (x, y, z)')
+    return t
+
+
+def _mask_volume(arr, device) -> torch.Tensor:
+    """any (X, Y, Z) array / tensor -> contiguous uint8 device tensor, 1 where non-zero."""
+    t = torch.from_numpy(np.ascontiguousarray(arr)) if isinstance(arr, np.ndarray) else arr
+    if t.dtype == torch.uint64:
+        t = t.view(torch.int64)
+    elif t.dtype == torch.uint32:
+        t = t.view(torch.int32)
+    return (t.to(device) != 0).to(torch.uint8).contiguous()
+
+
+def detect_seg_boundaries(arr, return_device: bool = False, device=None):
+    """find_object_properties.py:424-455: boolean mask of the non-zero voxels of `arr` (uint32, x, y, z) that have an in-array
+    6-neighbour with another value (0 counts as another value).  ``return_device``: a uint8 device tensor instead."""
+    dev = _cs_device(device)
+    seg = _u32_volume(arr, dev)
+    X, Y, Z = (int(s) for s in seg.shape)
+    mask = torch.empty((X, Y, Z), dtype=torch.uint8, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    L.check(L.load().sd_seg_boundaries(seg.data_ptr(), X, Y, Z, mask.data_ptr(), stream), 'sd_seg_boundaries')
+    return mask if return_device else mask.cpu().numpy().view(np.bool_)
+
+
+def process_block_nonzero(edges, arr, stencil1=(7, 7, 3), return_device: bool = False, device=None):
+    """block_processing_C.pyx:50-75: for every centre voxel with ``edges != 0`` the most frequent id of its `stencil1` window other
+    than 0 and the centre id (ties: the smallest id), packed as ``(min << 32) | max`` with the centre id; valid convolution, uint64
+    of shape ``arr.shape - stencil1 + 1``.  ``return_device``: an int64 device tensor holding the uint64 bits."""
+    stencil = tuple(int(s) for s in stencil1)
+    assert sum(s % 2 for s in stencil) == 3
+    dev = _cs_device(device)
+    seg = _u32_volume(arr, dev)
+    e = _mask_volume(edges, dev)
+    X, Y, Z = (int(s) for s in seg.shape)
+    if tuple(e.shape) != (X, Y, Z):
+        raise ValueError('edges and arr must have the same shape')
+    out_shape = tuple(max(n - s + 1, 0) for n, s in zip((X, Y, Z), stencil))
+    out = torch.zeros(out_shape, dtype=torch.int64, device=dev)
+    lib = L.load()
+    ws = torch.empty(lib.sd_contact_partners_workspace_bytes(), dtype=torch.uint8, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    if out.numel():
+        L.check(lib.sd_contact_partners(e.data_ptr(), seg.data_ptr(), X, Y, Z, *stencil, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                        stream), 'sd_contact_partners')
+    return out if return_device else out.cpu().numpy().view(np.uint64)
+
+
+def detect_cs(arr, stencil=None, return_device: bool = False, device=None):
+    """find_object_properties.py:458-472: contact-site ids of a uint32 cell segmentation (uint64, valid convolution of the
+    stencil; default ``config['cell_objects']['cs_filtersize']``)."""
+    if stencil is None:
+        from .. import global_params
+        stencil = global_params.config['cell_objects']['cs_filtersize']
+    dev = _cs_device(device)
+    seg = _u32_volume(arr, dev)
+    edges = detect_seg_boundaries(seg, return_device=True, device=dev)
+    return process_block_nonzero(edges, seg, stencil, return_device=return_device, device=dev)

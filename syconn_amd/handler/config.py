@@ -57,6 +57,10 @@ DEFAULTS = {
             'er': ['binary_dilation'] * 3 + ['binary_erosion'] * 3,
             'golgi': ['binary_dilation'] * 3 + ['binary_erosion'] * 3,
         },
+        # contact sites (config.yml:146-150): the stencil of the partner search (odd extents; max // 2 closings follow) and the
+        # dilations after the closing
+        'cs_filtersize': [13, 13, 7],
+        'cs_dilation': 2,
     },
 }
 
