@@ -317,6 +317,13 @@ int sd_object_segmentation(const uint8_t* prob_dev, int X, int Y, int Z, double 
                            int32_t* labels_dev, int32_t* max_label_dev, uint8_t* mask_out_dev, void* workspace_dev,
                            size_t ws_bytes, void* stream);
 
+/* Mask-only form of the same morphology (cs_extraction_steps.py:405-408: apply_morphological_operations on the sj mask): mask =
+ * in > threshold (0: any value != 0), then the operation list (erosion allowed here; runs merged by the caller), mask_out_dev
+ * (X,Y,Z) uint8 = the 0/1 result.  An empty mask stays empty.  Workspace: sd_objseg_workspace_bytes as above. */
+int sd_binary_morphology(const uint8_t* in_dev, int X, int Y, int Z, double threshold, const int32_t* ops, const int32_t* iterations,
+                         int n_ops, const uint8_t* struct_host, int sx, int sy, int sz, uint8_t* mask_out_dev, void* workspace_dev,
+                         size_t ws_bytes, void* stream);
+
 /* The WATERSHED branch of the same function (object_extraction_steps.py:319-352) -- what SyConn's default config selects for
  * mi / sj / vc (config.yml:130-136: opening, closing, erosion(s)); taken when the operation list contains 'binary_erosion':
  *   ops / iterations          the operations BEFORE the first erosion -> tmp_data (:320-322);
@@ -389,6 +396,41 @@ int sd_contact_partners(const uint8_t* edges_dev, const uint32_t* seg_dev, int X
 enum sd_cs_flags { SD_CS_FIRST = 1, SD_CS_LAST = 2 };
 int sd_cs_close_dilate(const uint64_t* c0_dev, int X, int Y, int Z, const int64_t* table_dev, int64_t n_obj, int64_t tot_vox,
                        int n_close, int n_dilate, int flags, uint64_t* out_dev, void* workspace_dev, size_t ws_bytes, void* stream);
+
+/* Synapse statistics of the contact sites of a chunk (/root/reference/syconn/extraction/block_processing_C.pyx:78-158
+ * extract_cs_syntype, called by _contact_site_extraction_thread, cs_extraction_steps.py:464-470).  All volumes are (X,Y,Z) with z
+ * fastest; the calls read the window [ox, ox+nx) x [oy, oy+ny) x [oz, oz+nz) of them (the worker's core inside its halo volume).
+ *   sd_cs_syntype_scan     one pass over cs_dev (uint32 / uint64 site ids, 0 = background) and the uint8 masks syn_dev (any value
+ *                          != 0 is syn), asym_dev, sym_dev (== 1 counts) into the hash table of `cap` slots (power of two,
+ *                          sd_cs_syntype_table_bytes(cap) bytes; the call initialises it).  Per site: the cs record (first voxel in
+ *                          the x, y, z scan, box, size), the syn record (the same over its syn voxels) and the voxel counts of
+ *                          syn && asym == 1 and syn && sym == 1.  cs_out_dev / syn_out_dev (optional, (nx,ny,nz) of the id type): the
+ *                          window's ids, and its ids where syn != 0 else 0 (the worker's syn segmentation, :476-480).
+ *                          *status_dev = 1 when the table overflowed: repeat with a larger capacity.
+ *   sd_cs_syntype_compact  the occupied slots: ids_dev / slots_dev (unordered), *count_dev = their number.
+ *   sd_cs_syntype_records  rec_dev int64[n][SD_CST_COLS] for the slots in the order given (the caller sorts them by id):
+ *                          0 id | 1-3 first voxel (window coordinates) | 4 size | 5-7 box min | 8-10 box max + 1 |
+ *                          11-20 the same for the syn voxels (zeros when the site has none) | 21 asym count | 22 sym count |
+ *                          23 offset of the site's syn voxels (exclusive sum of column 14); *n_syn_dev = the total.
+ *   sd_cs_syntype_voxels   vox_dev int64[n_syn][3]: every site's syn voxels in scan order from row column 23 on, as window
+ *                          coordinates + offset_host[3] (HOST array; voxels_syn of the reference).  *status_dev = 1 if a count
+ *                          disagreed with the records (not expected).
+ * sd_syntype_masks: the syn-type masks of the worker (cs_extraction_steps.py:411-433) on n voxels: dtype SD_U8 (raw data):
+ * out_a = vol >= 123; SD_U64 (labels): out_a = vol == label_a and, when out_b_dev is given, out_b = vol == label_b. */
+enum { SD_CST_COLS = 24 };
+size_t sd_cs_syntype_table_bytes(size_t capacity);
+int sd_cs_syntype_scan(const void* cs_dev, int dtype, const uint8_t* syn_dev, const uint8_t* asym_dev, const uint8_t* sym_dev, int X,
+                       int Y, int Z, int ox, int oy, int oz, int nx, int ny, int nz, void* table_dev, size_t cap, void* cs_out_dev,
+                       void* syn_out_dev, int32_t* status_dev, void* stream);
+int sd_cs_syntype_compact(const void* table_dev, size_t cap, uint64_t* ids_dev, int32_t* slots_dev, size_t max_out,
+                          uint64_t* count_dev, void* stream);
+int sd_cs_syntype_records(const void* table_dev, size_t cap, const int32_t* slots_dev, int64_t n, int nx, int ny, int nz,
+                          int64_t* rec_dev, int64_t* n_syn_dev, void* stream);
+int sd_cs_syntype_voxels(const void* cs_dev, int dtype, const uint8_t* syn_dev, int X, int Y, int Z, int ox, int oy, int oz,
+                         const int64_t* rec_dev, int64_t n, int64_t n_syn, const int64_t* offset_host, int64_t* vox_dev,
+                         int32_t* status_dev, void* stream);
+int sd_syntype_masks(const void* vol_dev, int dtype, size_t n, uint64_t label_a, uint64_t label_b, uint8_t* out_a_dev,
+                     uint8_t* out_b_dev, void* stream);
 
 /* ---- host-side helpers of the chunk pipeline (no GPU) -----------------------------------------------------------------
  * Multi-threaded strided copy of an (nz, ny, nx)-byte box between two uint8 host arrays whose x-rows are contiguous

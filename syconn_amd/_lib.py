@@ -12,6 +12,7 @@ SD_OUT_LOGITS_F32, SD_OUT_PROBS_F32, SD_OUT_PROBS_U8 = 0, 1, 2
 SD_OP_CONV, SD_OP_POOL, SD_OP_UPCONV, SD_OP_GROUPNORM, SD_OP_FINAL = 1, 2, 3, 4, 5
 SD_MOP_OPENING, SD_MOP_CLOSING, SD_MOP_DILATION, SD_MOP_EROSION = 1, 2, 3, 4
 SD_CS_FIRST, SD_CS_LAST = 1, 2
+SD_CST_COLS = 24
 
 LIB_NAME = 'libsyconn_dense_hip.so'
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), os.environ.get('SD_LIB_NAME', LIB_NAME))
@@ -26,7 +27,9 @@ EXPORTS = ['sd_init', 'sd_device_count', 'sd_model_create', 'sd_model_destroy', 
            'sd_object_segmentation_watershed', 'sd_marker_flood', 'sd_host_box_copy', 'sd_host_zero', 'sd_plan_clip_window',
            'sd_gauss_workspace_bytes', 'sd_gaussian_threshold', 'sd_model_set_roi', 'sd_labels_make_unique', 'sd_labels_box_lut',
            'sd_chunkprops_append', 'sd_chunkpairs_append', 'sd_propmerge_temp_bytes', 'sd_propmerge_objects', 'sd_propmerge_pairs', 'sd_profile_read_clocks', 'sd_probe_mfma_rate', 'sd_memcpy2d_async',
-           'sd_seg_boundaries', 'sd_contact_partners_workspace_bytes', 'sd_contact_partners', 'sd_cs_close_dilate']
+           'sd_seg_boundaries', 'sd_contact_partners_workspace_bytes', 'sd_contact_partners', 'sd_cs_close_dilate',
+           'sd_binary_morphology', 'sd_cs_syntype_table_bytes', 'sd_cs_syntype_scan', 'sd_cs_syntype_compact', 'sd_cs_syntype_records',
+           'sd_cs_syntype_voxels', 'sd_syntype_masks']
 
 
 class OpDesc(C.Structure):
@@ -131,6 +134,18 @@ def load():
     lib.sd_contact_partners.argtypes = [vp, vp] + [i32] * 6 + [vp, vp, sz, vp]; lib.sd_contact_partners.restype = i32
     lib.sd_cs_close_dilate.argtypes = [vp, i32, i32, i32, vp, i64, i64, i32, i32, i32, vp, vp, sz, vp]
     lib.sd_cs_close_dilate.restype = i32
+    # block_processing_C.pyx:78-158 (extract_cs_syntype) and cs_extraction_steps.py:402-433 (sj morphology, syn-type masks)
+    lib.sd_binary_morphology.argtypes = [vp, i32, i32, i32, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32), i32, vp, i32, i32,
+                                         i32, vp, vp, sz, vp]
+    lib.sd_binary_morphology.restype = i32
+    lib.sd_cs_syntype_table_bytes.argtypes = [sz]; lib.sd_cs_syntype_table_bytes.restype = sz
+    lib.sd_cs_syntype_scan.argtypes = [vp, i32, vp, vp, vp] + [i32] * 9 + [vp, sz, vp, vp, vp, vp]
+    lib.sd_cs_syntype_scan.restype = i32
+    lib.sd_cs_syntype_compact.argtypes = [vp, sz, vp, vp, sz, vp, vp]; lib.sd_cs_syntype_compact.restype = i32
+    lib.sd_cs_syntype_records.argtypes = [vp, sz, vp, i64, i32, i32, i32, vp, vp, vp]; lib.sd_cs_syntype_records.restype = i32
+    lib.sd_cs_syntype_voxels.argtypes = [vp, i32, vp] + [i32] * 6 + [vp, i64, i64, C.POINTER(i64), vp, vp, vp]
+    lib.sd_cs_syntype_voxels.restype = i32
+    lib.sd_syntype_masks.argtypes = [vp, i32, sz, C.c_uint64, C.c_uint64, vp, vp, vp]; lib.sd_syntype_masks.restype = i32
     _lib = lib
     return lib
 

@@ -1494,6 +1494,34 @@ int sd_object_segmentation(const uint8_t* prob_dev, int X, int Y, int Z, double 
     return hipGetLastError() == hipSuccess ? SD_OK : sd_fail_msg(SD_ERR_HIP, "sd_object_segmentation: launch failed");
 }
 
+// apply_morphological_operations on a 0/1 mask (cs_extraction_steps.py:405-408 with image.py:358-438, 485-519): the same threshold
+// and morphology kernels as above, erosion included, without the labelling; the mask after the operations -> mask_out_dev
+int sd_binary_morphology(const uint8_t* in_dev, int X, int Y, int Z, double threshold, const int32_t* ops, const int32_t* iterations,
+                         int n_ops, const uint8_t* struct_host, int sx, int sy, int sz, uint8_t* mask_out_dev, void* ws, size_t ws_bytes,
+                         void* stream) {
+    if (!in_dev || !mask_out_dev || !ws || X <= 0 || Y <= 0 || Z <= 0 || n_ops < 0 || (n_ops && (!ops || !iterations)))
+        return sd_fail_msg(SD_ERR_INVALID, "sd_binary_morphology: bad argument");
+    if ((size_t)X * Y * Z >= (1ull << 31)) return sd_fail_msg(SD_ERR_INVALID, "sd_binary_morphology: volume must have < 2^31 voxels");
+    if (threshold != threshold) return sd_fail_msg(SD_ERR_INVALID, "sd_binary_morphology: NaN threshold");
+    int P = 0;
+    int rc = check_ops(ops, iterations, n_ops, true, P);
+    if (rc != SD_OK) return rc;
+    Offs o{};
+    if (n_ops && (rc = make_offsets(struct_host, sx, sy, sz, o)) != SD_OK) return rc;
+    const WsLayout w = ws_layout(X, Y, Z, P);
+    if (ws_bytes < w.total) return sd_fail_msg(SD_ERR_NOMEM, "sd_binary_morphology: workspace too small");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    char* const wb = reinterpret_cast<char*>(ws);
+    uint32_t* A = reinterpret_cast<uint32_t*>(wb + w.a);
+    uint32_t* B = reinterpret_cast<uint32_t*>(wb + w.b);
+    const Dom d = make_dom(X, Y, Z, P);
+    const size_t pwords = (size_t)d.PX * d.PY * d.PZW;
+    hipLaunchKernelGGL(k_threshold_bits, dim3(grid_for(pwords)), dim3(256), 0, s, in_dev, cut_of(threshold), d, A);
+    run_morph(s, A, B, d, reinterpret_cast<int*>(wb + w.bbox), ops, iterations, n_ops, o);
+    hipLaunchKernelGGL(k_mask_bytes, dim3(grid_for((size_t)X * Y * Z)), dim3(256), 0, s, A, d, mask_out_dev);
+    return hipGetLastError() == hipSuccess ? SD_OK : sd_fail_msg(SD_ERR_HIP, "sd_binary_morphology: launch failed");
+}
+
 size_t sd_objseg_watershed_workspace_bytes(int X, int Y, int Z, int max_iterations) {
     if (X <= 0 || Y <= 0 || Z <= 0 || max_iterations < 0) return 0;
     return ws_layout2(X, Y, Z, max_iterations).total;

@@ -13,13 +13,11 @@
 #include <algorithm>
 #include <cstdlib>
 #include <string>
+#include "sd_hash.h"
 
 extern int sd_fail_msg(int code, const char* msg);      // sd_api.hip: sets sd_last_error()
 
 namespace {
-
-typedef unsigned long long u64;
-constexpr u64 EMPTY = 0ull;                               // label 0 is background and never inserted
 
 // Object table of `cap` slots (power of two), structure of arrays in one buffer:
 //   keys u64[cap] | first u64[cap] (smallest raster index) | size u64[cap] | bbmin i32[3][cap] | bbmax i32[3][cap]
@@ -40,26 +38,6 @@ __host__ __device__ inline ObjTable obj_table(void* base, u64 cap) {
 constexpr size_t OBJ_SLOT_BYTES = 3 * 8 + 6 * 4;
 // Pair table: keys u64[cap] ((subcell slot << 32 | cell slot) + 1) | count u64[cap]
 constexpr size_t PAIR_SLOT_BYTES = 16;
-
-__device__ __forceinline__ u64 mix64(u64 k) {             // murmur3 finaliser
-    k ^= k >> 33; k *= 0xff51afd7ed558ccdull; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull; k ^= k >> 33;
-    return k;
-}
-
-// slot of `k` in an open-addressing table (linear probing), inserting it if absent; -1 when the table is full
-__device__ __forceinline__ long find_or_insert(u64* keys, u64 cap, u64 k) {
-    const u64 mask = cap - 1;
-    u64 h = mix64(k) & mask;
-    for (u64 probe = 0; probe < cap; ++probe, h = (h + 1) & mask) {
-        u64 cur = __hip_atomic_load(&keys[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (cur == k) return (long)h;
-        if (cur == EMPTY) {
-            const u64 old = atomicCAS(&keys[h], EMPTY, k);
-            if (old == EMPTY || old == k) return (long)h;
-        }
-    }
-    return -1;
-}
 
 __global__ __launch_bounds__(256) void k_obj_init(ObjTable t) {
     for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < t.cap; i += (u64)gridDim.x * 256) {
@@ -88,15 +66,6 @@ struct ScanParams {
 
 template <typename L>
 __device__ __forceinline__ u64 load_label(const void* vol, u64 i) { return (u64)reinterpret_cast<const L*>(vol)[i]; }
-
-// run structure of a wave: `head` lanes start a run of equal values inside one z-row; returns the run length for head lanes
-__device__ __forceinline__ int run_length(bool head, int lane, int nvalid) {
-    const u64 m = __ballot(head);
-    const u64 later = (lane == 63) ? 0ull : (m >> (lane + 1));
-    int next = later ? (lane + 1 + __builtin_ctzll(later)) : 64;
-    if (next > nvalid) next = nvalid;
-    return next - lane;
-}
 
 __device__ __forceinline__ void obj_update(const ObjTable& t, u64 key, u64 lin, int x, int y, int z, int len, int* status) {
     const long s = find_or_insert(t.keys, t.cap, key);
@@ -466,7 +435,6 @@ __global__ __launch_bounds__(256) void k_pair_compact(const u64* pkeys, const u6
     }
 }
 
-inline bool pow2(u64 v) { return v && !(v & (v - 1)); }
 // ---- globally unique object ids across chunks (object_extraction_steps.py:369-443 make_unique_labels, :658-736 apply_merge_list)
 // per-chunk int32 component labels -> uint64 ids shifted by the chunk's offset (background stays 0)
 __global__ __launch_bounds__(256) void k_labels_offset(const int32_t* __restrict__ lab, u64 n, u64 offset, u64* __restrict__ out) {
@@ -492,8 +460,6 @@ __global__ __launch_bounds__(256) void k_labels_box_lut(const u64* __restrict__ 
         dst[i] = v;
     }
 }
-
-inline int grid_for(u64 n, int cap = 4096) { u64 g = (n + 255) / 256; return (int)(g < 1 ? 1 : (g > (u64)cap ? (u64)cap : g)); }
 
 }  // namespace
 

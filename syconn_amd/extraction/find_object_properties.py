@@ -311,3 +311,166 @@ def detect_cs(arr, stencil=None, return_device: bool = False, device=None):
     seg = _u32_volume(arr, dev)
     edges = detect_seg_boundaries(seg, return_device=True, device=dev)
     return process_block_nonzero(edges, seg, stencil, return_device=return_device, device=dev)
+
+
+# ---- synapse statistics of contact sites (block_processing_C.pyx:78-158 extract_cs_syntype; find_object_properties.py:302-344) ----
+def _u8_volume(arr, device) -> torch.Tensor:
+    """uint8 / bool (X, Y, Z) array or tensor -> contiguous uint8 device tensor with the same values."""
+    t = torch.from_numpy(np.ascontiguousarray(arr)) if isinstance(arr, np.ndarray) else arr
+    if t.dtype == torch.bool:
+        t = t.to(torch.uint8)
+    if t.dtype != torch.uint8:
+        raise TypeError(f'syn / type masks must be uint8, got {t.dtype}')
+    return t.to(device).contiguous()
+
+
+class CsSyntype:
+    """Result of ``cs_syntype`` as device tensors, sites in ascending id order.  ``rec`` int64 (n, SD_CST_COLS), the columns of
+    ``sd_cs_syntype_records``; ``voxels`` int64 (n_syn, 3), the syn voxels of site i at rows ``rec[i, 23] : rec[i, 23] + rec[i, 14]``,
+    in scan order, offset included."""
+
+    def __init__(self, rec: torch.Tensor, voxels: torch.Tensor, cs_core=None, syn_core=None):
+        self.rec, self.voxels, self.cs_core, self.syn_core = rec, voxels, cs_core, syn_core
+
+    @property
+    def ids(self) -> torch.Tensor:
+        return self.rec[:, 0]
+
+    def host(self):
+        """(rec, voxels) as numpy arrays (column 0 of rec holds the uint64 ids' bits)."""
+        return self.rec.cpu().numpy(), self.voxels.cpu().numpy()
+
+
+def cs_syntype_dicts(rec: np.ndarray, voxels: np.ndarray):
+    """Host records -> the return value of ``extract_cs_syntype`` (dicts in ascending id order)."""
+    ids = rec[:, 0].view(np.uint64).tolist() if len(rec) else []
+    def props(c0):
+        return (dict(zip(ids, rec[:, c0:c0 + 3].tolist())), dict(zip(ids, rec[:, c0 + 4:c0 + 10].reshape(-1, 2, 3).tolist())),
+                dict(zip(ids, rec[:, c0 + 3].tolist())))
+    cs_rc, cs_bb, cs_sz = props(1)
+    syn = rec[:, 14] > 0
+    s_rc, s_bb, s_sz = props(11)
+    keep = lambda d, m: {k: v for (k, v), f in zip(d.items(), m) if f}
+    syn_m = syn.tolist()
+    asym = {k: v for k, v in zip(ids, rec[:, 21].tolist()) if v}
+    sym = {k: v for k, v in zip(ids, rec[:, 22].tolist()) if v}
+    vox = {}
+    if len(rec):
+        for k, o, n in zip(ids, rec[:, 23].tolist(), rec[:, 14].tolist()):
+            if n:
+                vox[k] = voxels[o:o + n].tolist()
+    return [cs_rc, cs_bb, cs_sz], [keep(s_rc, syn_m), keep(s_bb, syn_m), keep(s_sz, syn_m)], asym, sym, vox
+
+
+class CsSyntypeScan:
+    """The hash table of ``sd_cs_syntype_scan`` kept on the device from call to call; its capacity grows (and stays grown) when a
+    pass reports overflow, as ``DeviceScan`` does."""
+
+    def __init__(self, device=None, cap: Optional[int] = None):
+        self.lib = L.load()
+        self.device = _cs_device(device)
+        self.cap = _pow2_at_least(cap) if cap else 0
+        self.table = None
+        self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.passes = 0                          # scan passes of the last call (> 1: the table overflowed)
+
+    def run(self, cs, syn, asym, sym, offset=(0, 0, 0), origin=(0, 0, 0), extent=None, want_cores: bool = False) -> CsSyntype:
+        """extract_cs_syntype on the window [origin, origin + extent) of the four (X, Y, Z) volumes (default: all of it);
+        `offset` is added to the voxel lists only.  ``want_cores``: also the window's ids and its syn segmentation (the ids where
+        syn != 0, else 0) as (nx, ny, nz) device tensors of the id type."""
+        lib, dev = self.lib, self.device
+        c, dtype = _to_device(cs, dev)
+        if c.dim() != 3:
+            raise ValueError('cs_seg must be 3D (x, y, z)')
+        shape = tuple(int(s) for s in c.shape)
+        m = [_u8_volume(v, dev) for v in (syn, asym, sym)]
+        for v in m:
+            if tuple(v.shape) != shape:
+                raise ValueError('cs_seg, syn_mask, sym_mask and asym_mask must all have the same shape')
+        org = tuple(int(v) for v in origin)
+        ext = tuple(int(s) - o for s, o in zip(shape, org)) if extent is None else tuple(int(v) for v in extent)
+        off = np.asarray(offset, dtype=np.int64).reshape(3)
+        nvox = ext[0] * ext[1] * ext[2]
+        if not self.cap:
+            self.cap = _pow2_at_least(min(2 * max(nvox, 1), max(1 << 12, nvox // 256)))
+        cores = [torch.empty(ext, dtype=c.dtype, device=dev) for _ in range(2)] if want_cores else [None, None]
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        self.passes = 0
+        while True:
+            nb = lib.sd_cs_syntype_table_bytes(self.cap)
+            if self.table is None or self.table.numel() != nb:
+                self.table = torch.empty(nb, dtype=torch.uint8, device=dev)
+            L.check(lib.sd_cs_syntype_scan(c.data_ptr(), dtype, m[0].data_ptr(), m[1].data_ptr(), m[2].data_ptr(), *shape, *org, *ext,
+                                           self.table.data_ptr(), self.cap, cores[0].data_ptr() if want_cores else None,
+                                           cores[1].data_ptr() if want_cores else None, self.status.data_ptr(), stream),
+                    'sd_cs_syntype_scan')
+            self.passes += 1
+            if not int(self.status.item()):
+                break
+            if self.cap >= 2 * max(nvox, 1):
+                raise RuntimeError('sd_cs_syntype_scan: table overflow at maximum capacity')
+            self.cap *= 4
+        cap = self.cap
+        cnt = torch.zeros(1, dtype=torch.int64, device=dev)
+        ids = torch.empty(cap, dtype=torch.int64, device=dev)
+        slots = torch.empty(cap, dtype=torch.int32, device=dev)
+        L.check(lib.sd_cs_syntype_compact(self.table.data_ptr(), cap, ids.data_ptr(), slots.data_ptr(), cap, cnt.data_ptr(), stream),
+                'sd_cs_syntype_compact')
+        n = int(cnt.item())
+        # ascending ids: the order is taken on the host from the n ids, as segstats does
+        order = np.argsort(ids[:n].cpu().numpy().view(np.uint64), kind='stable')
+        slots_sorted = slots[:n][torch.from_numpy(order).to(dev)].contiguous()
+        rec = torch.empty((max(n, 1), L.SD_CST_COLS), dtype=torch.int64, device=dev)
+        n_syn = torch.zeros(1, dtype=torch.int64, device=dev)
+        L.check(lib.sd_cs_syntype_records(self.table.data_ptr(), cap, slots_sorted.data_ptr() if n else None, n, *ext, rec.data_ptr(),
+                                          n_syn.data_ptr(), stream), 'sd_cs_syntype_records')
+        ns = int(n_syn.item())
+        vox = torch.empty((max(ns, 1), 3), dtype=torch.int64, device=dev)
+        offs = (C.c_int64 * 3)(*off.tolist())
+        L.check(lib.sd_cs_syntype_voxels(c.data_ptr(), dtype, m[0].data_ptr(), *shape, *org, rec.data_ptr(), n, ns, offs,
+                                         vox.data_ptr(), self.status.data_ptr(), stream), 'sd_cs_syntype_voxels')
+        if ns and int(self.status.item()):
+            raise RuntimeError('sd_cs_syntype_voxels: voxel counts disagree with the site records')
+        return CsSyntype(rec[:n], vox[:ns], *cores)
+
+
+def cs_syntype(cs_seg, syn_mask, asym_mask, sym_mask, offset=(0, 0, 0), device=None, cap: Optional[int] = None, **kw) -> CsSyntype:
+    """Array form of ``extract_cs_syntype``: everything stays on the device (see ``CsSyntype``)."""
+    return CsSyntypeScan(device, cap).run(cs_seg, syn_mask, asym_mask, sym_mask, offset, **kw)
+
+
+def extract_cs_syntype(cs_seg, syn_mask, asym_mask, sym_mask, offset=(0, 0, 0), device=None):
+    """block_processing_C.pyx:78-158: ``[rep_coords, bounding_box, sizes], [rep_coords_syn, bounding_box_syn, sizes_syn], cs_asym,
+    cs_sym, voxels_syn`` of a uint32 / uint64 contact volume (x, y, z; 0 = background) and three uint8 masks of its shape.  Syn
+    voxels are those with ``syn_mask != 0``; ``cs_asym`` / ``cs_sym`` count syn voxels whose type mask is exactly 1; a site appears in
+    the syn, asym, sym and voxel dicts only when it has an entry there.  ``voxels_syn[id]`` lists the syn voxels in x, y, z scan
+    order as ``[x + offset[0], y + offset[1], z + offset[2]]``; coordinates and boxes are local.  Dict keys are in ascending id
+    order (the reference's follow its unordered_maps: DESIGN.md section 7)."""
+    return cs_syntype_dicts(*cs_syntype(cs_seg, syn_mask, asym_mask, sym_mask, offset, device=device).host())
+
+
+def merge_type_dicts(type_dicts: List[dict]):
+    """find_object_properties.py:302-321: add the counts of every further dict into the first, in place."""
+    tot_map = type_dicts[0]
+    for el in type_dicts[1:]:
+        for cs_id, cnt in el.items():
+            if cs_id in tot_map:
+                tot_map[cs_id] += cnt
+            else:
+                tot_map[cs_id] = cnt
+
+
+def merge_voxel_dicts(voxel_dicts: List[dict], key_to_str: bool = False):
+    """find_object_properties.py:324-344: append the voxel lists of every further dict to the first, in place (numpy arrays
+    become lists on first insertion); ``key_to_str``: keys become ``str(id)`` (for ``np.savez``)."""
+    tot_map = voxel_dicts[0]
+    for el in voxel_dicts[1:]:
+        for cs_id, vxs in el.items():
+            if key_to_str:
+                cs_id = str(cs_id)
+            if cs_id in tot_map:
+                tot_map[cs_id].extend(vxs)
+            else:
+                if isinstance(vxs, np.ndarray):
+                    vxs = vxs.tolist()
+                tot_map[cs_id] = vxs

@@ -29,3 +29,19 @@ def kd_factory(kd_path: str, channel: str = 'jpg') -> KnossosDataset:
     else:
         raise ValueError(f'Could not find KnossosDataset config at {kd_path}.')
     return kd
+
+
+def write_obj2pkl(path: str, objects):
+    """basics.py:485-508: pickle `objects` to `path` (written to ``path + '.tmp'`` and moved into place)."""
+    import pickle
+    import shutil
+    with open(path + '.tmp', 'wb') as output:
+        pickle.dump(objects, output, protocol=pickle.HIGHEST_PROTOCOL)
+    shutil.move(path + '.tmp', path)
+
+
+def load_pkl2obj(path: str):
+    """basics.py:511-530: the object pickled at `path`."""
+    import pickle
+    with open(path, 'rb') as inp:
+        return pickle.load(inp)

@@ -23,7 +23,9 @@ DEFAULTS = {
     'log_level': 20,
     'default_log_dir': None,
     'disable_file_logging': True,
-    'paths': {'kd_seg': None},
+    'paths': {'kd_seg': None, 'kd_sj': None, 'kd_sym': None, 'kd_asym': None},
+    # synapse-type datasets (config.py:700-707): False = no sym / asym masks (cs_extraction_steps.py:431-433)
+    'syntype_avail': False,
     'process_cell_organelles': ['mi', 'vc'],      # config.yml:15
     'dense_prediction': {
         'overlap_shape_tiles': [30, 31, 20],   # xyz, prediction.py:672
@@ -61,6 +63,10 @@ DEFAULTS = {
         # dilations after the closing
         'cs_filtersize': [13, 13, 7],
         'cs_dilation': 2,
+        # labels of the synapse types in the kd_sym / kd_asym segmentations (config.py:803-809); None: those datasets hold raw
+        # data, thresholded at 123 (cs_extraction_steps.py:414-424)
+        'sym_label': None,
+        'asym_label': None,
     },
 }
 
@@ -170,6 +176,19 @@ class DynConfig:
     @property
     def mpath_mivcsj(self) -> str:
         return self.model_dir + '/mivcsj/model.pt'
+
+    @property
+    def syntype_available(self) -> bool:
+        """config.py:700-708: synaptic types are available as KnossosDataset(s)."""
+        return bool(self['syntype_avail'])
+
+    @property
+    def asym_label(self) -> Optional[int]:
+        return self['cell_objects']['asym_label']
+
+    @property
+    def sym_label(self) -> Optional[int]:
+        return self['cell_objects']['sym_label']
 
     @property
     def ngpu_total(self) -> int:

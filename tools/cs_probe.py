@@ -73,6 +73,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=3)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--part2-out', default=None, help='also time the part-2 stages (sj mask, type masks, statistics, voxel lists, '
+                                                      'host copies, one worker chunk) and write them here')
     args = ap.parse_args()
     dev = torch.device('cuda', 0)
     lib = L.load()
@@ -109,6 +111,110 @@ def main():
         os.makedirs(os.path.dirname(args.out) or '.', exist_ok=True)
         with open(args.out, 'w') as f:
             f.write(line + '\n')
+    if args.part2_out:
+        del edges, ws, wsc
+        part2(out, n_close, dev, args)
+
+
+def part2(contacts, overlap, dev, args):
+    """The stages after the closing on the closed contact volume (a 512^3 core inside `overlap`) and a synthetic sj map with ~1 %
+    foreground.  Kernel-only rows time the sd_* launches; rows marked _host include host syncs and allocations."""
+    from syconn_amd.extraction.cs_extraction_steps import binary_morphology, syntype_masks
+    from syconn_amd.extraction.find_object_properties import CsSyntypeScan, cs_syntype_dicts
+    from syconn_amd.extraction.object_extraction_steps import get_aniso_struct
+    lib = L.load()
+    shape = tuple(int(s) for s in contacts.shape)
+    g = torch.Generator(device=dev).manual_seed(1)
+    pool = torch.nn.functional.avg_pool3d(torch.rand((1, 1) + shape, generator=g, device=dev), 5, 1, 2)[0, 0]
+    sj_raw = torch.where(pool > 0.56, 200, 10).to(torch.uint8)
+    del pool
+    ops = ['binary_opening', 'binary_closing', 'binary_erosion']
+    struct = get_aniso_struct(np.array([10, 10, 20]))
+    sj, t_sj = timed(lambda: binary_morphology(sj_raw, ops, struct, threshold=255 * 0.19047619, return_device=True, device=dev),
+                     args.reps)
+    labels = torch.randint(0, 4, shape, generator=g, device=dev, dtype=torch.int64)
+    (asym, sym), t_types = timed(lambda: syntype_masks(labels, 3, 1, device=dev), args.reps)
+    del labels
+    core = tuple(s - 2 * overlap for s in shape)
+    sc = CsSyntypeScan(dev)
+    res, t_all = timed(lambda: sc.run(contacts, sj, asym, sym, offset=(0, 0, 0), origin=(overlap,) * 3, extent=core, want_cores=True),
+                       args.reps)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    cs_core, syn_core = res.cs_core, res.syn_core
+    _, t_scan = timed(lambda: L.check(lib.sd_cs_syntype_scan(contacts.data_ptr(), L.SD_U64, sj.data_ptr(), asym.data_ptr(), sym.data_ptr(),
+                                                             *shape, *(overlap,) * 3, *core, sc.table.data_ptr(), sc.cap,
+                                                             cs_core.data_ptr(), syn_core.data_ptr(), sc.status.data_ptr(), stream)),
+                      args.reps)
+    _, t_scan_nocore = timed(lambda: L.check(lib.sd_cs_syntype_scan(contacts.data_ptr(), L.SD_U64, sj.data_ptr(), asym.data_ptr(),
+                                                                    sym.data_ptr(), *shape, *(overlap,) * 3, *core, sc.table.data_ptr(),
+                                                                    sc.cap, None, None, sc.status.data_ptr(), stream)), args.reps)
+    import ctypes as C
+    n, ns = int(res.rec.shape[0]), int(res.voxels.shape[0])
+    vox = torch.empty((max(ns, 1), 3), dtype=torch.int64, device=dev)
+    offs = (C.c_int64 * 3)(0, 0, 0)
+    _, t_vox = timed(lambda: L.check(lib.sd_cs_syntype_voxels(contacts.data_ptr(), L.SD_U64, sj.data_ptr(), *shape, *(overlap,) * 3,
+                                                              res.rec.data_ptr(), n, ns, offs, vox.data_ptr(), sc.status.data_ptr(),
+                                                              stream)), args.reps)
+
+    def to_host():
+        a = cs_core.permute(2, 1, 0).contiguous().cpu()
+        b = syn_core.permute(2, 1, 0).contiguous().cpu()
+        return a, b, res.host()
+    _, t_copy = timed(to_host, args.reps)
+    t0 = __import__('time').perf_counter()
+    cs_syntype_dicts(*res.host())
+    t_dicts = (__import__('time').perf_counter() - t0) * 1e3
+    # one worker chunk with KnossosDataset I/O (a smaller chunk: 256 x 256 x 128, written to a temporary dataset first)
+    t_worker = worker_chunk(dev)
+    out = dict(core=list(core), sites=n, syn_sites=int((res.rec[:, 14] > 0).sum()), syn_voxels=ns,
+               sj_foreground=float(sj.float().mean()), scan_table_slots=sc.cap,
+               ms_sj_threshold_morphology_host=round(t_sj, 3), ms_type_masks_host=round(t_types, 3),
+               ms_stats_pass_kernel=round(t_scan, 3), ms_stats_pass_kernel_without_cores=round(t_scan_nocore, 3),
+               ms_voxel_lists_kernel=round(t_vox, 3), ms_stats_voxels_records_host=round(t_all, 3),
+               ms_copies_to_host=round(t_copy, 3), ms_dicts_host=round(t_dicts, 3), worker_chunk=[256, 256, 128],
+               ms_worker_chunk_with_kd_io=round(t_worker, 1), device=torch.cuda.get_device_name(0))
+    line = json.dumps(out)
+    print(line)
+    os.makedirs(os.path.dirname(args.part2_out) or '.', exist_ok=True)
+    with open(args.part2_out, 'w') as f:
+        f.write(line + '\n')
+
+
+def worker_chunk(dev):
+    import tempfile
+    import time
+    import yaml
+    from syconn_amd import global_params
+    from syconn_amd.extraction.cs_extraction_steps import _contact_site_extraction_thread
+    from syconn_amd.knossos import Chunk, KnossosDataset
+    chunk, halo = (256, 256, 128), (12, 12, 9)
+    box = tuple(c + 2 * h for c, h in zip(chunk, halo))
+    with tempfile.TemporaryDirectory() as tmp:
+        def kd(path, seg=None, raw=None):
+            k = KnossosDataset().initialize_without_conf(path, box, (10, 10, 20), 'probe', mags=[1])
+            if seg is not None:
+                k.save_seg(offset=(0, 0, 0), mags=[1], data=np.ascontiguousarray(seg.swapaxes(0, 2)), data_mag=1)
+            if raw is not None:
+                k.save_raw(offset=(0, 0, 0), mags=[1], data=np.ascontiguousarray(raw.swapaxes(0, 2)), data_mag=1)
+        cells = voronoi_cells(box, (4, 4, 2), dev, seed=2).cpu().numpy().view(np.uint32).astype(np.uint64)
+        sj = (torch.nn.functional.avg_pool3d(torch.rand((1, 1) + box, device=dev), 5, 1, 2)[0, 0] > 0.56).to(torch.uint8) * 200
+        kd(f'{tmp}/cells', seg=cells)
+        kd(f'{tmp}/sj', raw=sj.cpu().numpy())
+        kd(f'{tmp}/wd/knossosdatasets/cs_seg/')
+        kd(f'{tmp}/wd/knossosdatasets/syn_seg/')
+        with open(f'{tmp}/wd/config.yml', 'w') as f:
+            yaml.safe_dump({'scaling': [10, 10, 20], 'paths': {'kd_sj': f'{tmp}/sj'}}, f)
+        saved = global_params.wd
+        global_params.wd = f'{tmp}/wd'
+        try:
+            ch = [Chunk(0, halo, chunk, (0, 0, 0))]
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            _contact_site_extraction_thread((ch, f'{tmp}/cells', 0, f'{tmp}/props', None))
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3
+        finally:
+            global_params.wd = saved
 
 
 if __name__ == '__main__':
