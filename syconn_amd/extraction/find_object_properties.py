@@ -44,13 +44,15 @@ def _pow2_at_least(n: int) -> int:
 
 class SegStats:
     """Result of one pass, still as dense arrays (ids ascending): ``cell`` / ``sub[i]`` = (ids, first, size, bbox) with
-    bbox (n, 2, 3); ``pairs[i]`` = (subcell ids, cell ids, counts)."""
+    bbox (n, 2, 3); ``pairs[i]`` = (subcell ids, cell ids, counts).  ``cap_obj`` / ``cap_pair``: the table capacities the pass
+    ended with (larger than the ones it started with when a table overflowed and the pass was repeated)."""
 
     def __init__(self):
         self.shape = None
         self.cell = None
         self.sub: List[tuple] = []
         self.pairs: List[tuple] = []
+        self.cap_obj = self.cap_pair = 0
 
 
 class DeviceScan:
@@ -182,6 +184,7 @@ def segstats(cell, subs: Sequence = (), want_props: bool = True, device=None, ca
 
     res = SegStats()
     res.shape = shape
+    res.cap_obj, res.cap_pair = cap_obj, cap_pair
     if want_props:
         if cell_t is not None:
             res.cell = objects(tabs[0])

@@ -109,16 +109,24 @@ def test_map_subcell_extract_props_over_knossos_datasets(gpu, name, tmp_path):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize('n,n_ids,seed', [(1, 1, 0), (1000, 37, 1), (200000, 5000, 2), (70000, 70000, 3)])
+@pytest.mark.parametrize('n,n_ids,seed', [(1, 1, 0), (1000, 37, 1), (200000, 5000, 2), (70000, 70000, 3), (3000000, 150000, 4)])
 def test_propmerge_kernels_against_numpy(gpu, n, n_ids, seed):
-    """sd_propmerge_objects / sd_propmerge_pairs on random records: stable order inside an id, sums, last representative."""
+    """sd_propmerge_objects / sd_propmerge_pairs on random records: stable order inside an id, sums, last representative.  Ids come
+    from the whole uint64 range (2^63, 2^63 + 1 and 2^64 - 1 among them); 3,000,000 records are almost three grid strides of every
+    kernel of the merge, with segments of 20 records on average."""
     import torch
     from syconn_amd import _lib as L
     lib = L.load()
     rng = np.random.default_rng(seed)
-    pool = np.unique(rng.integers(1, 2 ** 62, n_ids * 2, dtype=np.int64).astype(np.uint64))[:n_ids]
+    pool = np.unique(rng.integers(1, 2 ** 64 - 1, n_ids * 2, dtype=np.uint64))
+    pool = pool[(pool != 2 ** 63) & (pool != 2 ** 63 + 1)]
     rng.shuffle(pool)
+    pool = pool[:n_ids]
+    if n_ids >= 3:
+        pool[:3] = np.array([2 ** 64 - 1, 2 ** 63, 2 ** 63 + 1], dtype=np.uint64)
+        rng.shuffle(pool)
     n_ids = len(pool)
+    assert len(np.unique(pool)) == n_ids and (n_ids < 3 or int(np.count_nonzero(pool >= 2 ** 63)) >= 3)
     ids = pool[rng.integers(0, n_ids, n)]
     sizes = rng.integers(1, 10 ** 9, n, dtype=np.int64)
     rc = rng.integers(0, 2 ** 20, (n, 3), dtype=np.int32)
@@ -200,6 +208,42 @@ def test_chunk_driver_on_device_volumes_equals_whole_volume_statistics(gpu):
         assert np.array_equal(lo, whole.sub[i][3][:, 0]) and np.array_equal(hi, whole.sub[i][3][:, 1])
         s, c, n = whole.pairs[i]
         assert np.array_equal(map_t[o].sub_ids, s) and np.array_equal(map_t[o].cell_ids, c) and np.array_equal(map_t[o].counts, n)
+    # ... and the numpy oracle of the whole volume, the cell table included: ids, sizes, union of the per-chunk boxes, overlap counts
+    from oracle.objprops_ref import map_subcell_extract_props_np
+    w_cell, w_sub, w_map = map_subcell_extract_props_np(vols['sv'], np.stack([vols['mi'], vols['vc']]))
+    cs = np.array([32, 32, 16])
+
+    def last_chunk_first_voxel(vol):
+        """per id (ascending): the first voxel, in raster order, inside the last chunk (x outermost, z innermost) that holds the id"""
+        idx = np.flatnonzero(vol.reshape(-1))
+        xyz = np.stack(np.unravel_index(idx, vol.shape), axis=1)
+        g, c = -(-np.array(vol.shape) // cs), xyz // cs
+        ch = (c[:, 0] * g[1] + c[:, 1]) * g[2] + c[:, 2]
+        ids = vol.reshape(-1)[idx]
+        order = np.lexsort((idx, ch, ids))
+        i_s, c_s = ids[order], ch[order]
+        head = np.flatnonzero(np.concatenate(([True], (i_s[1:] != i_s[:-1]) | (c_s[1:] != c_s[:-1]))))
+        hid = i_s[head]
+        last = np.flatnonzero(np.concatenate((hid[1:] != hid[:-1], [True])))
+        return hid[last], xyz[order][head[last]]
+
+    def check(tab, vol, w_bb, w_sz):
+        keys = sorted(w_sz)
+        assert tab.ids.tolist() == keys and tab.sizes.tolist() == [w_sz[k] for k in keys]
+        lo = np.minimum.reduceat(tab.boxes[:, 0], tab.box_begin[:-1], axis=0)
+        hi = np.maximum.reduceat(tab.boxes[:, 1], tab.box_begin[:-1], axis=0)
+        assert np.array_equal(np.stack((lo, hi), axis=1), np.array([w_bb[k] for k in keys]))
+        rc = np.asarray(tab.rep_coords)
+        assert np.array_equal(vol[rc[:, 0], rc[:, 1], rc[:, 2]], tab.ids)                 # the representative lies inside the object
+        ids, want_rc = last_chunk_first_voxel(vol)
+        assert np.array_equal(ids, tab.ids) and np.array_equal(rc, want_rc)
+    check(cell_t, vols['sv'], w_cell[1], w_cell[2])
+    for i, o in enumerate(['mi', 'vc']):
+        check(sub_t[o], vols[o], w_sub[1][i], w_sub[2][i])
+        got = {}
+        for a, b, n in zip(map_t[o].sub_ids.tolist(), map_t[o].cell_ids.tolist(), map_t[o].counts.tolist()):
+            got.setdefault(a, {})[b] = n
+        assert got == w_map[i]
 
 
 @pytest.mark.gpu

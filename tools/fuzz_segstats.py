@@ -1,5 +1,6 @@
 """GPU box: randomized sweep of the label-statistics pass -- every kernel form (one voxel per lane / four voxels per lane, sequential or with
-1-4 volumes prefetched, with or without a cell volume, properties on / off, uint32 / uint64) against the numpy oracle and against each other.
+1-4 volumes prefetched, with or without a cell volume, up to 8 subcell volumes, properties on / off, uint32 / uint64, device volumes whose pointer
+is not 16-byte aligned) against the numpy oracle and against each other.  A manual tool; the fixed cases live in tests/test_gpu_segstats_edges.py.
 usage: fuzz_segstats.py [seconds] [seed]"""
 import os, sys, time
 import numpy as np, torch
@@ -23,6 +24,13 @@ def volume(shape, nid, dtype, coherent):
     return np.ascontiguousarray(v).astype(dtype)
 
 
+def misaligned(v):
+    flat = torch.from_numpy(v.view(np.int64 if v.dtype == np.uint64 else np.int32).reshape(-1))
+    buf = torch.empty(flat.numel() + 1, dtype=flat.dtype, device=dev)
+    buf[1:] = flat.to(dev)
+    return buf[1:].view(*v.shape)
+
+
 def pairs_np(cell, sub):
     both = np.flatnonzero((sub.reshape(-1) != 0) & (cell.reshape(-1) != 0))
     if both.size == 0:
@@ -44,18 +52,21 @@ while time.time() - t0 < budget:
     nid = int(rng.choice([2, 5, 40, 3000]))
     coh = bool(rng.random() < 0.6)
     has_cell = bool(rng.random() < 0.7)
-    n_sub = int(rng.integers(0 if has_cell else 1, 6))
+    n_sub = int(rng.integers(0 if has_cell else 1, 9))
     want = bool(rng.random() < 0.8) or not has_cell or n_sub == 0
     cell = volume(shape, nid, dtype, coh) if has_cell else None
     subs = [volume(shape, max(2, nid // 2), dtype, coh and k % 2 == 0) for k in range(n_sub)]
     if dtype == np.uint64 and has_cell:
         cell[cell == 1] = np.uint64(2 ** 63 + 5)
     os.environ.pop('SD_SEGSTATS_V1', None)
-    r4 = segstats(cell, subs, want_props=want, device=dev)
+    d_cell, d_subs = cell, subs
+    if rng.random() < 0.25:          # device volumes cut from a flat buffer at an offset of one element: the library must leave the 16-byte loads
+        d_cell, d_subs = (misaligned(cell) if has_cell else None), [misaligned(s) if rng.random() < 0.7 else s for s in subs]
+    r4 = segstats(d_cell, d_subs, want_props=want, device=dev)
     os.environ['SD_SEGSTATS_V1'] = '1'
     r1 = segstats(cell, subs, want_props=want, device=dev)
     os.environ.pop('SD_SEGSTATS_V1', None)
-    key = (z % 4 == 0, has_cell, min(n_sub, 5), want, dtype.__name__)
+    key = (z % 4 == 0, has_cell, n_sub, want, dtype.__name__)
     forms[key] = forms.get(key, 0) + 1
     if want:
         if has_cell:
