@@ -432,6 +432,45 @@ int sd_cs_syntype_voxels(const void* cs_dev, int dtype, const uint8_t* syn_dev, 
 int sd_syntype_masks(const void* vol_dev, int dtype, size_t n, uint64_t label_a, uint64_t label_b, uint8_t* out_a_dev,
                      uint8_t* out_b_dev, void* stream);
 
+/* Dataset-wide merge of contact sites and synapses (/root/reference/syconn/extraction/cs_extraction_steps.py: the running merges
+ * of _contact_site_extraction_thread :484-492, _write_props_collect_helper :631-673 and the merge / join / filter of
+ * _write_props_to_syn_thread :544-623), on record arrays that stay on the device; the counterpart of sd_chunkprops_append /
+ * sd_propmerge_objects for the records of sd_cs_syntype_records.  Coordinates are int32, ids uint64, counts uint64.
+ *   sd_cs_merge_append    one chunk core: rec_dev int64[n][SD_CST_COLS] and vox_dev int64[n_vox][3] (n_vox = the sum of column 14,
+ *                         rows as sd_cs_syntype_voxels lays them out, origin already added there).  Appends at cursors_dev (uint64[3]:
+ *                         cs records, syn records, voxel rows; zeroed by the caller before the first chunk) one cs record per site
+ *                         (id, first voxel + (ox,oy,oz), box + (ox,oy,oz), size), one syn record per site with column 14 > 0 (the
+ *                         same from columns 11-20, the asym and sym counts, and the row at which its voxel run starts in vox_all_dev;
+ *                         the run's length is its size) and the voxel rows as uint32[.][3].  Cursors count past max_cs / max_syn /
+ *                         max_vox (the caller detects the overrun); nothing is written beyond them.  Asynchronous, no host sync.
+ *   sd_cs_merge_objects   n records -> one row per id with merged size >= min_obj_vx, ids ascending: uniq_ids, tot_sizes, last_rc
+ *                         [.][3] (the record appended last), union_bbox [.][6] (min of mins | max of maxes), seg_begin = first slot of
+ *                         the id in bbox_sorted [.][6] (the kept records' boxes, id-major, append order inside an id).
+ *                         counts_dev uint64[4] = kept ids, kept boxes, 0, ids before the filter.  Outputs hold n rows; temp: sd_cs_merge_temp_bytes(n).
+ *   sd_cs_merge_synapses  the same for the syn records, and: an id is kept only if it is among cs_ids_dev[n_cs] (ascending: the
+ *                         uniq_ids sd_cs_merge_objects kept) -- cs_size = cs_sizes_dev there; asym_tot / sym_tot = summed counts;
+ *                         vox_out_dev uint32[.][3] = the voxel runs of every kept id gathered into one run (append order inside an id,
+ *                         row order inside a run), starting at row vox_begin; counts_dev[2] = kept rows, [3] = ids before the filter.
+ *                         vox_out holds n_vox rows.
+ * Limits: n < 2^32 records and n_vox < 2^32 voxel rows per merge call (SD_ERR_INVALID otherwise). */
+int sd_cs_merge_append(const int64_t* rec_dev, size_t n, const int64_t* vox_dev, size_t n_vox, int ox, int oy, int oz,
+                       uint64_t* cs_ids_dev, int32_t* cs_rc_dev, int32_t* cs_bbox_dev, uint64_t* cs_sizes_dev, size_t max_cs,
+                       uint64_t* syn_ids_dev, int32_t* syn_rc_dev, int32_t* syn_bbox_dev, uint64_t* syn_sizes_dev, uint64_t* syn_asym_dev,
+                       uint64_t* syn_sym_dev, uint64_t* syn_vpos_dev, size_t max_syn, uint32_t* vox_all_dev, size_t max_vox,
+                       uint64_t* cursors_dev, void* stream);
+size_t sd_cs_merge_temp_bytes(size_t n_records);
+int sd_cs_merge_objects(const uint64_t* ids_dev, const uint64_t* sizes_dev, const int32_t* rc_dev, const int32_t* bbox_dev, size_t n,
+                        uint64_t min_obj_vx, uint64_t* uniq_ids_dev, uint64_t* tot_sizes_dev, int32_t* last_rc_dev,
+                        int32_t* union_bbox_dev, uint32_t* seg_begin_dev, int32_t* bbox_sorted_dev, uint64_t* counts_dev, void* temp_dev,
+                        size_t temp_bytes, void* stream);
+int sd_cs_merge_synapses(const uint64_t* ids_dev, const uint64_t* sizes_dev, const int32_t* rc_dev, const int32_t* bbox_dev,
+                         const uint64_t* asym_dev, const uint64_t* sym_dev, const uint64_t* vpos_dev, size_t n,
+                         const uint32_t* vox_all_dev, size_t n_vox, const uint64_t* cs_ids_dev, const uint64_t* cs_sizes_dev, size_t n_cs,
+                         uint64_t min_obj_vx, uint64_t* uniq_ids_dev, uint64_t* tot_sizes_dev, int32_t* last_rc_dev,
+                         int32_t* union_bbox_dev, uint32_t* seg_begin_dev, int32_t* bbox_sorted_dev, uint64_t* asym_tot_dev,
+                         uint64_t* sym_tot_dev, uint64_t* cs_size_dev, uint32_t* vox_begin_dev, uint32_t* vox_out_dev,
+                         uint64_t* counts_dev, void* temp_dev, size_t temp_bytes, void* stream);
+
 /* ---- host-side helpers of the chunk pipeline (no GPU) -----------------------------------------------------------------
  * Multi-threaded strided copy of an (nz, ny, nx)-byte box between two uint8 host arrays whose x-rows are contiguous
  * (strides in bytes), and a multi-threaded memset: what numpy slicing does on one core when the reference cuts a chunk

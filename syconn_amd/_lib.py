@@ -29,7 +29,8 @@ EXPORTS = ['sd_init', 'sd_device_count', 'sd_model_create', 'sd_model_destroy', 
            'sd_chunkprops_append', 'sd_chunkpairs_append', 'sd_propmerge_temp_bytes', 'sd_propmerge_objects', 'sd_propmerge_pairs', 'sd_profile_read_clocks', 'sd_probe_mfma_rate', 'sd_memcpy2d_async',
            'sd_seg_boundaries', 'sd_contact_partners_workspace_bytes', 'sd_contact_partners', 'sd_cs_close_dilate',
            'sd_binary_morphology', 'sd_cs_syntype_table_bytes', 'sd_cs_syntype_scan', 'sd_cs_syntype_compact', 'sd_cs_syntype_records',
-           'sd_cs_syntype_voxels', 'sd_syntype_masks']
+           'sd_cs_syntype_voxels', 'sd_syntype_masks', 'sd_cs_merge_append', 'sd_cs_merge_temp_bytes', 'sd_cs_merge_objects',
+           'sd_cs_merge_synapses']
 
 
 class OpDesc(C.Structure):
@@ -146,6 +147,13 @@ def load():
     lib.sd_cs_syntype_voxels.argtypes = [vp, i32, vp] + [i32] * 6 + [vp, i64, i64, C.POINTER(i64), vp, vp, vp]
     lib.sd_cs_syntype_voxels.restype = i32
     lib.sd_syntype_masks.argtypes = [vp, i32, sz, C.c_uint64, C.c_uint64, vp, vp, vp]; lib.sd_syntype_masks.restype = i32
+    # cs_extraction_steps.py:484-492, :544-623, :631-673 (the dataset merge of contact sites and synapses)
+    lib.sd_cs_merge_append.argtypes = [vp, sz, vp, sz, i32, i32, i32, vp, vp, vp, vp, sz] + [vp] * 7 + [sz, vp, sz, vp, vp]
+    lib.sd_cs_merge_append.restype = i32
+    lib.sd_cs_merge_temp_bytes.argtypes = [sz]; lib.sd_cs_merge_temp_bytes.restype = sz
+    lib.sd_cs_merge_objects.argtypes = [vp, vp, vp, vp, sz, C.c_uint64] + [vp] * 8 + [sz, vp]; lib.sd_cs_merge_objects.restype = i32
+    lib.sd_cs_merge_synapses.argtypes = [vp] * 7 + [sz, vp, sz, vp, vp, sz, C.c_uint64] + [vp] * 13 + [sz, vp]
+    lib.sd_cs_merge_synapses.restype = i32
     _lib = lib
     return lib
 

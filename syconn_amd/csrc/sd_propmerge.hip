@@ -13,18 +13,11 @@
 // Records of one chunk are appended in table order (arbitrary) but chunks are appended in stream order and an id occurs at most once
 // per chunk, so a STABLE sort by id alone yields chunk order inside every segment.
 #include "../../include/syconn_dense.h"
-#include <hip/hip_runtime.h>
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-#include <stdint.h>
-#include <algorithm>
+#include "sd_sortseg.h"
 
 extern int sd_fail_msg(int code, const char* msg);      // sd_api.hip: sets sd_last_error()
 
 namespace {
-
-typedef unsigned long long u64;
-typedef unsigned int u32;
 
 // view of an object table as sd_segstats.hip lays it out: keys | first | size | bbmin[3][cap] | bbmax[3][cap]
 struct TabView {
@@ -81,16 +74,8 @@ __global__ __launch_bounds__(256) void k_chunkpairs_append(const u64* pkeys, con
     }
 }
 
-__global__ __launch_bounds__(256) void k_iota(u32* p, u64 n) {
-    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256) p[i] = (u32)i;
-}
 __global__ __launch_bounds__(256) void k_gather64(const u64* src, const u32* idx, u64* dst, u64 n) {
     for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256) dst[i] = src[idx[i]];
-}
-// head[i] = 1 where a new key starts in the sorted order
-__global__ __launch_bounds__(256) void k_heads(const u64* ka, const u64* kb /* may be nullptr */, u32* head, u64 n) {
-    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256)
-        head[i] = (i == 0 || ka[i] != ka[i - 1] || (kb && kb[i] != kb[i - 1])) ? 1u : 0u;
 }
 
 // one thread per segment of equal ids: total voxel count, representative coordinate of the last chunk; every thread also moves its own
@@ -124,19 +109,6 @@ __global__ __launch_bounds__(256) void k_reduce_pairs(const u64* ssub, const u64
         const u32 s = seg[i] - 1u;
         out_sub[s] = a; out_cell[s] = b; out_cnt[s] = sum;
     }
-}
-
-inline int grid_for(u64 n, int cap = 4096) { u64 g = (n + 255) / 256; return (int)(g < 1 ? 1 : (g > (u64)cap ? (u64)cap : g)); }
-inline bool pow2(u64 v) { return v && !(v & (v - 1)); }
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// rocPRIM scratch for n records (radix sort of u64 keys with u32 values, inclusive scan of u32)
-size_t prim_bytes(size_t n) {
-    size_t a = 0, b = 0;
-    u64* k = nullptr; u32* v = nullptr;
-    (void)rocprim::radix_sort_pairs(nullptr, a, k, k, v, v, n, 0, 64, (hipStream_t)0);
-    (void)rocprim::inclusive_scan(nullptr, b, v, v, n, rocprim::plus<u32>(), (hipStream_t)0);
-    return up256(std::max(a, b));
 }
 
 // carve the caller's scratch: [u64 n | u64 n | u64 n | u32 n x 4 | rocPRIM]

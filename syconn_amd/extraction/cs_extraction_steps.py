@@ -3,6 +3,9 @@
 
 Here: the partner search (``find_object_properties.detect_cs``) and the closing + dilation of every contact site inside its own
 box (:437-461, ``close_and_dilate_cs``).  Where several sites claim one background voxel the smallest id wins.
+Further down: the sj / syn-type masks, the per-chunk worker (:317-495) and the dataset driver ``extract_contact_sites`` (:44-314)
+with the merging half of its second step (``_write_props_to_syn_thread`` / ``_write_props_collect_helper``, :498-673): the records
+of all chunks stay on the device and are merged once (``ContactSiteMerger``, ``csrc/sd_cs_merge.hip``).
 There is no CPU fallback.
 """
 import ctypes as C
@@ -194,54 +197,42 @@ def _check_worker_config(cfg):
     return cs_filtersize, overlap
 
 
-def _contact_site_extraction_thread(args):
-    """cs_extraction_steps.py:317-495: contact sites and synapses of the chunks `args[0]`.  `args` = (chunks, knossos_path of the
-    cell segmentation, worker_nr, dir_props, transf_func_sj_seg).  Writes ``cs_props_{w}.pkl``, ``syn_props_{w}.pkl``,
-    ``syn_voxels_{w}.npz``, ``tot_asym_cnt_{w}.pkl`` and ``tot_sym_cnt_{w}.pkl`` into ``{dir_props}/{w}/`` and the chunk cores
-    into ``{wd}/knossosdatasets/cs_seg/`` and ``syn_seg/`` (initialised by the caller).  Per chunk everything between the loads
-    and the two core volumes runs on the device; the host does the KnossosDataset I/O and the dict merges.  Returns
-    ``(worker_nr, dict(cs=[ids], syn=[ids]))``; dict keys are in ascending id order per chunk."""
-    import os
-    from collections import defaultdict
-    from .. import global_params
-    from ..handler import basics
-    from ..proc.sd_proc import merge_prop_dicts
-    from .find_object_properties import CsSyntypeScan, cs_syntype_dicts, detect_cs, merge_type_dicts, merge_voxel_dicts
-    from .object_extraction_steps import get_aniso_struct
+class _ChunkExtractor:
+    """Steps 1-5 of the worker body (:374-480) for one chunk at a time: loads, partner stencil, closing + dilation, sj and syn-type
+    masks, and the statistics pass over the chunk core.  Everything between the loads and the result stays on the device.  Shared
+    by ``_contact_site_extraction_thread`` and ``extract_contact_sites``."""
 
-    chunks, knossos_path, worker_nr, dir_props, transf_func_sj_seg = args[:5]
-    worker_dir_props = f"{dir_props}/{worker_nr}/"
-    os.makedirs(worker_dir_props, exist_ok=True)
-    cfg = global_params.config
-    morph_ops = cfg['cell_objects']['extract_morph_op']
-    scaling = np.array(cfg['scaling'])
-    struct = get_aniso_struct(scaling)
-    cs_filtersize, overlap = _check_worker_config(cfg)
-    syntype = cfg.syntype_available
-    sym_label, asym_label = cfg.sym_label, cfg.asym_label
-    same_kd = syntype and cfg.kd_asym_path == cfg.kd_sym_path
-    if same_kd:
-        assert asym_label is not None, 'Label of asymmetric synapses is not set.'
-        assert sym_label is not None, 'Label of symmetric synapses is not set.'
+    def __init__(self, knossos_path, transf_func_sj_seg=None, device=None):
+        from .. import global_params
+        from ..handler import basics
+        from .find_object_properties import CsSyntypeScan
+        from .object_extraction_steps import get_aniso_struct
+        cfg = self.cfg = global_params.config
+        self.transf_func_sj_seg = transf_func_sj_seg
+        morph_ops = cfg['cell_objects']['extract_morph_op']
+        self.struct = get_aniso_struct(np.array(cfg['scaling']))
+        self.cs_filtersize, self.overlap = _check_worker_config(cfg)
+        self.syntype = cfg.syntype_available
+        self.sym_label, self.asym_label = cfg.sym_label, cfg.asym_label
+        self.same_kd = self.syntype and cfg.kd_asym_path == cfg.kd_sym_path
+        if self.same_kd:
+            assert self.asym_label is not None, 'Label of asymmetric synapses is not set.'
+            assert self.sym_label is not None, 'Label of symmetric synapses is not set.'
+        self.kd_sj = basics.kd_factory(cfg.kd_sj_path)
+        self.kd_sym = basics.kd_factory(cfg.kd_sym_path) if self.syntype else None
+        self.kd_asym = basics.kd_factory(cfg.kd_asym_path) if self.syntype else None
+        self.kd = basics.kd_factory(knossos_path)
+        self.cs_dilation = int(cfg['cell_objects']['cs_dilation'])
+        self.stencil_offset = self.cs_filtersize // 2
+        self.sj_ops = list(morph_ops['sj']) if 'sj' in morph_ops else []
+        self.dev = _cs_device(device)
+        self.scan = CsSyntypeScan(self.dev)
 
-    kd_cs = basics.kd_factory(f"{cfg.working_dir}/knossosdatasets/cs_seg/")
-    kd_syn = basics.kd_factory(f"{cfg.working_dir}/knossosdatasets/syn_seg/")
-    kd_sj = basics.kd_factory(cfg.kd_sj_path)
-    kd_sym = basics.kd_factory(cfg.kd_sym_path) if syntype else None
-    kd_asym = basics.kd_factory(cfg.kd_asym_path) if syntype else None
-    kd = basics.kd_factory(knossos_path)
-
-    cs_props = [{}, defaultdict(list), {}]
-    syn_props = [{}, defaultdict(list), {}]
-    syn_voxels = {}
-    tot_sym_cnt = {}
-    tot_asym_cnt = {}
-    cs_dilation = int(cfg['cell_objects']['cs_dilation'])
-    stencil_offset = cs_filtersize // 2
-    sj_ops = list(morph_ops['sj']) if 'sj' in morph_ops else []
-    dev = _cs_device()
-    scan = CsSyntypeScan(dev)
-    for chunk in chunks:
+    def run(self, chunk):
+        """-> (``CsSyntype`` of the chunk core with both core volumes, the core's (x, y, z) origin in the dataset)."""
+        from .find_object_properties import detect_cs
+        cfg, dev, overlap, stencil_offset = self.cfg, self.dev, self.overlap, self.stencil_offset
+        kd, kd_sj, kd_sym, kd_asym = self.kd, self.kd_sj, self.kd_sym, self.kd_asym
         offset = np.array(chunk.coordinates - overlap)
         size = 2 * overlap + np.array(chunk.size)
         # 1. cell segmentation with the stencil's halo, truncated to uint32 (:374-376)
@@ -249,51 +240,83 @@ def _contact_site_extraction_thread(args):
         seg = (seg64 & 0xFFFFFFFF).to(torch.int32)
         del seg64
         # 2. partner stencil (valid convolution: `contacts` has the shape `size`), 3. closing + dilation of every site (:437-461)
-        c0 = detect_cs(seg, stencil=cs_filtersize, return_device=True, device=dev)
+        c0 = detect_cs(seg, stencil=self.cs_filtersize, return_device=True, device=dev)
         del seg
         plan = plan_sites(c0, overlap, dev)
         contacts = torch.empty_like(c0)
         ws = torch.empty(max(plan.ws_bytes, 1), dtype=torch.uint8, device=dev)
-        run_sites(c0, plan, overlap, cs_dilation, contacts, ws)
+        run_sites(c0, plan, overlap, self.cs_dilation, contacts, ws)
         del c0, ws
         # 4. sj mask (:392-408) and syn-type masks (:411-433)
-        if transf_func_sj_seg is None:
+        if self.transf_func_sj_seg is None:
             sj_in = _upload_xyz(kd_sj.load_raw(size=size, offset=offset, mag=1), dev)
             thr = 255 * cfg['cell_objects']['probathresholds']['sj']
-            sj_d = binary_morphology(sj_in, sj_ops, struct, threshold=thr, return_device=True, device=dev)
+            sj_d = binary_morphology(sj_in, self.sj_ops, self.struct, threshold=thr, return_device=True, device=dev)
         else:
-            sj_h = np.asarray(transf_func_sj_seg(kd_sj.load_seg(size=size, offset=offset, mag=1).swapaxes(0, 2))).astype('u1', copy=False)
-            if sj_ops and np.any(sj_h > 1):
+            sj_h = np.asarray(self.transf_func_sj_seg(kd_sj.load_seg(size=size, offset=offset, mag=1).swapaxes(0, 2))).astype('u1', copy=False)
+            if self.sj_ops and np.any(sj_h > 1):
                 raise ValueError('transf_func_sj_seg returned values other than 0 and 1 while sj morphology is configured: the '
                                  'reference would apply it per label; this build takes binary sj masks only (DESIGN.md section 7)')
             sj_d = torch.from_numpy(np.ascontiguousarray(sj_h)).to(dev)
-            if sj_ops:
-                sj_d = binary_morphology(sj_d, sj_ops, struct, threshold=0, return_device=True, device=dev)
-        if syntype:
-            if not same_kd:
+            if self.sj_ops:
+                sj_d = binary_morphology(sj_d, self.sj_ops, self.struct, threshold=0, return_device=True, device=dev)
+        if self.syntype:
+            if not self.same_kd:
                 def one(kd_t, label):
                     if label is None:
                         return syntype_masks(_upload_xyz(kd_t.load_raw(size=size, offset=offset, mag=1), dev), device=dev)
                     return syntype_masks(_upload_xyz(kd_t.load_seg(size=size, offset=offset, mag=1), dev), label, device=dev)
-                sym_d, asym_d = one(kd_sym, sym_label), one(kd_asym, asym_label)
+                sym_d, asym_d = one(kd_sym, self.sym_label), one(kd_asym, self.asym_label)
             else:
-                asym_d, sym_d = syntype_masks(_upload_xyz(kd_sym.load_seg(size=size, offset=offset, mag=1), dev), asym_label,
-                                              sym_label, device=dev)
+                asym_d, sym_d = syntype_masks(_upload_xyz(kd_sym.load_seg(size=size, offset=offset, mag=1), dev), self.asym_label,
+                                              self.sym_label, device=dev)
         else:
             sym_d = torch.zeros_like(sj_d)
             asym_d = sym_d
         # 5. statistics, voxel lists and the two core volumes in one pass over the core (:464-480)
         core = tuple(int(s) - 2 * overlap for s in size)
-        res = scan.run(contacts, sj_d, asym_d, sym_d, offset=offset + overlap, origin=(overlap,) * 3, extent=core, want_cores=True)
+        res = self.scan.run(contacts, sj_d, asym_d, sym_d, offset=offset + overlap, origin=(overlap,) * 3, extent=core, want_cores=True)
+        return res, offset + overlap
+
+
+def _contact_site_extraction_thread(args):
+    """cs_extraction_steps.py:317-495: contact sites and synapses of the chunks `args[0]`.  `args` = (chunks, knossos_path of the
+    cell segmentation, worker_nr, dir_props, transf_func_sj_seg).  Writes ``cs_props_{w}.pkl``, ``syn_props_{w}.pkl``,
+    ``syn_voxels_{w}.npz``, ``tot_asym_cnt_{w}.pkl`` and ``tot_sym_cnt_{w}.pkl`` into ``{dir_props}/{w}/`` and the chunk cores
+    into ``{wd}/knossosdatasets/cs_seg/`` and ``syn_seg/`` (initialised by the caller).  Per chunk everything between the loads
+    and the two core volumes runs on the device (``_ChunkExtractor``); the host does the KnossosDataset I/O and the dict merges.
+    Returns ``(worker_nr, dict(cs=[ids], syn=[ids]))``; dict keys are in ascending id order per chunk."""
+    import os
+    from collections import defaultdict
+    from .. import global_params
+    from ..handler import basics
+    from ..proc.sd_proc import merge_prop_dicts
+    from .find_object_properties import cs_syntype_dicts, merge_type_dicts, merge_voxel_dicts
+
+    chunks, knossos_path, worker_nr, dir_props, transf_func_sj_seg = args[:5]
+    worker_dir_props = f"{dir_props}/{worker_nr}/"
+    os.makedirs(worker_dir_props, exist_ok=True)
+    cfg = global_params.config
+    body = _ChunkExtractor(knossos_path, transf_func_sj_seg)
+    kd_cs = basics.kd_factory(f"{cfg.working_dir}/knossosdatasets/cs_seg/")
+    kd_syn = basics.kd_factory(f"{cfg.working_dir}/knossosdatasets/syn_seg/")
+
+    cs_props = [{}, defaultdict(list), {}]
+    syn_props = [{}, defaultdict(list), {}]
+    syn_voxels = {}
+    tot_sym_cnt = {}
+    tot_asym_cnt = {}
+    for chunk in chunks:
+        res, core_offset = body.run(chunk)
         # 6. to the host: the two cores (z, y, x) and the compact site arrays
         cs_core = res.cs_core.permute(2, 1, 0).contiguous().cpu().numpy().view(np.uint64)
         syn_core = res.syn_core.permute(2, 1, 0).contiguous().cpu().numpy().view(np.uint64)
         curr_cs_p, curr_syn_p, asym_cnt, sym_cnt, curr_syn_vx = cs_syntype_dicts(*res.host())
-        del contacts, sj_d, sym_d, asym_d, res
-        kd_cs.save_seg(offset=offset + overlap, mags=[1, ], data=cs_core, data_mag=1)
-        kd_syn.save_seg(offset=offset + overlap, mags=[1, ], data=syn_core, data_mag=1)
-        merge_prop_dicts([cs_props, curr_cs_p], offset=offset + overlap)
-        merge_prop_dicts([syn_props, curr_syn_p], offset=offset + overlap)
+        del res
+        kd_cs.save_seg(offset=core_offset, mags=[1, ], data=cs_core, data_mag=1)
+        kd_syn.save_seg(offset=core_offset, mags=[1, ], data=syn_core, data_mag=1)
+        merge_prop_dicts([cs_props, curr_cs_p], offset=core_offset)
+        merge_prop_dicts([syn_props, curr_syn_p], offset=core_offset)
         merge_voxel_dicts([syn_voxels, curr_syn_vx], key_to_str=True)
         merge_type_dicts([tot_asym_cnt, asym_cnt])
         merge_type_dicts([tot_sym_cnt, sym_cnt])
@@ -304,3 +327,302 @@ def _contact_site_extraction_thread(args):
     basics.write_obj2pkl(f'{worker_dir_props}/tot_asym_cnt_{worker_nr}.pkl', tot_asym_cnt)
     basics.write_obj2pkl(f'{worker_dir_props}/tot_sym_cnt_{worker_nr}.pkl', tot_sym_cnt)
     return worker_nr, dict(cs=list(cs_props[0].keys()), syn=list(syn_props[0].keys()))
+
+
+# ---- the dataset driver (cs_extraction_steps.py:44-314) and the merging half of its second step (:498-673) --------------------
+def storage_keys(ids, n_folders_fs: int):
+    """The storage bucket of every id as ``rep_helper.subfold_from_ix_new(ix, n_folders_fs)`` names it (rep_helper.py:143-163).
+    The reference divides by the float ``1e3``: the bucket is ``int(ix // 1e3 % n_folders)`` in float64 arithmetic, which for
+    contact-site ids (packed uint32 pairs, mostly > 2^53) differs from the integer result and is reproduced as such."""
+    assert n_folders_fs % 10 == 0
+    order = int(np.log10(n_folders_fs))
+    ix = (np.asarray(ids, dtype=np.uint64).astype(np.float64) // 1e3 % n_folders_fs).astype(np.int64)
+    out = []
+    for v in ix.tolist():
+        id_str = '{num:0{w}d}'.format(num=v, w=order)
+        out.append('/' + ''.join('%s/' % id_str[i:i + 2] for i in range(0, order, 2)))
+    return out
+
+
+class CsTable:
+    """Merged contact sites that passed ``min_obj_vx['cs']`` (plain numpy): ``ids`` ascending (uint64), ``sizes`` (int64),
+    ``rep_coords`` (n, 3) int32 = the last chunk's, ``bounding_boxes`` (n, 2, 3) int32 = the union box, ``boxes`` (m, 2, 3) int32 =
+    every (chunk, id) box in id-major / chunk-minor order, ``box_begin`` (n + 1) offsets into ``boxes``."""
+
+    def __init__(self, ids, sizes, rep_coords, bounding_boxes, boxes, box_begin):
+        self.ids, self.sizes, self.rep_coords, self.bounding_boxes = ids, sizes, rep_coords, bounding_boxes
+        self.boxes, self.box_begin = boxes, box_begin
+
+    def __len__(self):
+        return len(self.ids)
+
+    def storage_keys(self, n_folders_fs: int):
+        return storage_keys(self.ids, n_folders_fs)
+
+    def as_dict(self) -> dict:
+        """id -> what ``_write_props_to_syn_thread`` stores for a ``cs`` object (:581-590): ``rep_coord`` (int32), ``bounding_box``,
+        ``size`` and ``boxes``, the (k, 2, 3) box list it hands to ``VoxelStorageDyn``."""
+        b = self.box_begin.tolist()
+        return {k: dict(rep_coord=self.rep_coords[i], bounding_box=self.bounding_boxes[i], size=s, boxes=self.boxes[b[i]:b[i + 1]])
+                for i, (k, s) in enumerate(zip(self.ids.tolist(), self.sizes.tolist()))}
+
+
+class SynTable(CsTable):
+    """Merged synapses whose cs object was kept and that passed ``min_obj_vx['syn']``: the columns of ``CsTable`` and ``asym`` /
+    ``sym`` (summed voxel counts), ``asym_prop`` / ``sym_prop`` (count / size, float64), ``cs_size``, ``voxels`` (v, 3) uint32 = the
+    voxel lists of all ids (id-major, chunks in chunk order, scan order inside a chunk), ``vox_begin`` (n + 1) offsets into it."""
+
+    def __init__(self, ids, sizes, rep_coords, bounding_boxes, boxes, box_begin, asym, sym, cs_size, voxels, vox_begin):
+        super().__init__(ids, sizes, rep_coords, bounding_boxes, boxes, box_begin)
+        self.asym, self.sym, self.cs_size, self.voxels, self.vox_begin = asym, sym, cs_size, voxels, vox_begin
+        # Python's int / int is the correctly rounded quotient; so is float64 division of two exactly represented integers
+        self.asym_prop = asym / sizes if len(ids) else np.zeros(0, np.float64)
+        self.sym_prop = sym / sizes if len(ids) else np.zeros(0, np.float64)
+
+    def as_dict(self) -> dict:
+        """id -> what ``_write_props_to_syn_thread`` stores for a ``syn`` object (:595-622): the entries of a cs object (boxes as
+        int64, the reference concatenates lists there), ``sym_prop``, ``asym_prop``, ``cs_id``, ``cs_size`` and ``voxels``
+        (uint32, the voxel cache)."""
+        b, v = self.box_begin.tolist(), self.vox_begin.tolist()
+        bb64, boxes64 = self.bounding_boxes.astype(np.int64), self.boxes.astype(np.int64)
+        rows = zip(self.ids.tolist(), self.sizes.tolist(), self.sym_prop.tolist(), self.asym_prop.tolist(), self.cs_size.tolist())
+        return {k: dict(rep_coord=self.rep_coords[i], bounding_box=bb64[i], size=s, boxes=boxes64[b[i]:b[i + 1]], sym_prop=sp,
+                        asym_prop=ap, cs_id=k, cs_size=cz, voxels=self.voxels[v[i]:v[i + 1]])
+                for i, (k, s, sp, ap, cz) in enumerate(rows)}
+
+
+class ContactSiteMerger:
+    """The counterpart of ``proc.sd_proc.ChunkMerger`` for contact sites: the records of every chunk (``CsSyntype``, device) are
+    appended to growable device arrays by ``sd_cs_merge_append`` and merged once per dataset by ``sd_cs_merge_objects`` /
+    ``sd_cs_merge_synapses``.  The scan that produces a chunk's result has told the host its site and voxel counts already, so the
+    arrays are sized from them and ``add_chunk`` neither waits for the device nor copies anything to the host."""
+
+    def __init__(self, min_obj_vx: dict, device, capacity: int = 1 << 14, vox_capacity: int = 1 << 18):
+        from ..proc.sd_proc import _Records
+        self.lib = L.load()
+        self.device = torch.device(device)
+        self.min_cs, self.min_syn = int(min_obj_vx['cs']), int(min_obj_vx['syn'])
+        obj = [('ids', torch.int64, 1), ('rc', torch.int32, 3), ('bb', torch.int32, 6), ('sizes', torch.int64, 1)]
+        syn = obj + [('asym', torch.int64, 1), ('sym', torch.int64, 1), ('vpos', torch.int64, 1)]
+        self.cursors = torch.zeros(3, dtype=torch.int64, device=self.device)
+        self.cs = _Records(self.device, obj, capacity, self.cursors[0:1])
+        self.syn = _Records(self.device, syn, capacity, self.cursors[1:2])
+        self.vox = _Records(self.device, [('rows', torch.int32, 3)], vox_capacity, self.cursors[2:3])
+        self.n_cs = self.n_vox = 0          # appended so far (the syn records are at most n_cs)
+        self.n_chunks = 0
+        self.n_cs_all = self.n_syn_all = 0  # ids before the size filter (set by finish: the reference's log line counts these)
+
+    def add_chunk(self, result, origin):
+        """`result`: the ``CsSyntype`` of one chunk core whose (x, y, z) origin in the dataset is `origin` (its voxel rows carry
+        the origin already, its records do not)."""
+        n, n_vox = int(result.rec.shape[0]), int(result.voxels.shape[0])
+        self.cs.room_for(self.n_cs, n)
+        self.syn.room_for(self.n_cs, n)
+        self.vox.room_for(self.n_vox, n_vox)
+        ox, oy, oz = (int(v) for v in origin)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        L.check(self.lib.sd_cs_merge_append(result.rec.data_ptr() if n else None, n, result.voxels.data_ptr() if n_vox else None, n_vox,
+                                            ox, oy, oz, *self.cs.ptrs(), self.cs.capacity, *self.syn.ptrs(), self.syn.capacity,
+                                            *self.vox.ptrs(), self.vox.capacity, self.cursors.data_ptr(), stream), 'sd_cs_merge_append')
+        self.n_cs += n
+        self.n_vox += n_vox
+        self.n_chunks += 1
+
+    def finish(self):
+        """-> (``CsTable``, ``SynTable``).  One merge of each kind on the device, then the download of the compacted tables."""
+        lib, dev = self.lib, self.device
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        n_cs, n_syn, n_vox = (int(v) for v in self.cursors.cpu().numpy())
+        if n_cs > self.cs.capacity or n_syn > self.syn.capacity or n_vox > self.vox.capacity:
+            raise RuntimeError(f'sd_cs_merge_append: record arrays overran ({n_cs}/{self.cs.capacity} cs, {n_syn}/{self.syn.capacity} '
+                               f'syn, {n_vox}/{self.vox.capacity} voxel rows)')
+        tmp = torch.empty(lib.sd_cs_merge_temp_bytes(max(n_cs, n_syn, 1)), dtype=torch.uint8, device=dev)
+        new = lambda n, w, dt: torch.empty((max(n, 1), w) if w > 1 else (max(n, 1),), dtype=dt, device=dev)
+
+        def common(n):
+            return [new(n, 1, torch.int64), new(n, 1, torch.int64), new(n, 3, torch.int32), new(n, 6, torch.int32),
+                    new(n, 1, torch.int32), new(n, 6, torch.int32)]
+        c_out, c_cnt = common(n_cs), torch.zeros(4, dtype=torch.int64, device=dev)
+        a = self.cs.arrays
+        L.check(lib.sd_cs_merge_objects(a['ids'].data_ptr(), a['sizes'].data_ptr(), a['rc'].data_ptr(), a['bb'].data_ptr(), n_cs,
+                                        self.min_cs, *[t.data_ptr() for t in c_out], c_cnt.data_ptr(), tmp.data_ptr(), tmp.numel(),
+                                        stream), 'sd_cs_merge_objects')
+        u_cs, b_cs, _, self.n_cs_all = (int(v) for v in c_cnt.cpu().numpy())
+        s_out, s_cnt = common(n_syn), torch.zeros(4, dtype=torch.int64, device=dev)
+        s_more = [new(n_syn, 1, torch.int64), new(n_syn, 1, torch.int64), new(n_syn, 1, torch.int64), new(n_syn, 1, torch.int32),
+                  new(n_vox, 3, torch.int32)]
+        a = self.syn.arrays
+        L.check(lib.sd_cs_merge_synapses(*[a[k].data_ptr() for k in ('ids', 'sizes', 'rc', 'bb', 'asym', 'sym', 'vpos')], n_syn,
+                                         self.vox.arrays['rows'].data_ptr(), n_vox, c_out[0].data_ptr(), c_out[1].data_ptr(), u_cs,
+                                         self.min_syn, *[t.data_ptr() for t in s_out + s_more], s_cnt.data_ptr(), tmp.data_ptr(),
+                                         tmp.numel(), stream), 'sd_cs_merge_synapses')
+        u_syn, b_syn, v_syn, self.n_syn_all = (int(v) for v in s_cnt.cpu().numpy())
+
+        def table(out, u, b):
+            ids, tot, rc, ubox, beg, boxes = out
+            begin = np.concatenate((beg[:u].cpu().numpy().view(np.uint32).astype(np.int64), [b]))
+            return [ids[:u].cpu().numpy().view(np.uint64), tot[:u].cpu().numpy(), rc[:u].cpu().numpy(),
+                    ubox[:u].cpu().numpy().reshape(u, 2, 3), boxes[:b].cpu().numpy().reshape(b, 2, 3), begin]
+        cs_t = CsTable(*table(c_out, u_cs, b_cs))
+        asym, sym, cs_size, vbeg, vout = s_more
+        vox_begin = np.concatenate((vbeg[:u_syn].cpu().numpy().view(np.uint32).astype(np.int64), [v_syn]))
+        syn_t = SynTable(*table(s_out, u_syn, b_syn), asym[:u_syn].cpu().numpy(), sym[:u_syn].cpu().numpy(), cs_size[:u_syn].cpu().numpy(),
+                         vout[:v_syn].cpu().numpy().view(np.uint32), vox_begin)
+        return cs_t, syn_t
+
+
+class _CoreWriter:
+    """Takes the two core volumes of a chunk off the device on a side stream into page-locked buffers (two sets, guarded by
+    events) and writes them into the cs_seg / syn_seg KnossosDatasets on a writer thread, while the device works on the next
+    chunk -- as ``parallel.py`` does for its strips."""
+
+    def __init__(self, device, kd_cs, kd_syn):
+        import queue
+        import threading
+        self.device, self.kd_cs, self.kd_syn = device, kd_cs, kd_syn
+        self.side = torch.cuda.Stream(device=device)
+        self.bufs = [None, None]
+        self.free = [threading.Event(), threading.Event()]
+        for e in self.free:
+            e.set()
+        self.jobs = queue.Queue()
+        self.error = None
+        self.k = 0
+        self.busy_s = 0.0                 # time the writer thread spent in save_seg (for the probe)
+        self.thread = threading.Thread(target=self._work, daemon=True)
+        self.thread.start()
+
+    def _work(self):
+        import time
+        while True:
+            job = self.jobs.get()
+            if job is None:
+                return
+            slot, done, offset, shape = job
+            try:
+                if self.error is None:
+                    done.synchronize()
+                    t0 = time.perf_counter()
+                    n = int(np.prod(shape))
+                    for kd, buf in zip((self.kd_cs, self.kd_syn), self.bufs[slot]):
+                        kd.save_seg(offset=offset, mags=[1, ], data=buf.numpy()[:n].view(np.uint64).reshape(shape), data_mag=1)
+                    self.busy_s += time.perf_counter() - t0
+            except BaseException as e:          # re-raised by close()
+                self.error = e
+            finally:
+                self.free[slot].set()
+
+    def submit(self, result, offset):
+        """Queue the cores of `result` ((x, y, z) device tensors) for ``save_seg(offset=offset)`` as (z, y, x) volumes."""
+        slot = self.k % 2
+        self.k += 1
+        self.free[slot].wait()
+        if self.error is not None:
+            self.close()
+        self.free[slot].clear()
+        zyx = [t.permute(2, 1, 0).contiguous() for t in (result.cs_core, result.syn_core)]
+        n = zyx[0].numel()
+        if self.bufs[slot] is None or self.bufs[slot][0].numel() < n:
+            self.bufs[slot] = [torch.empty(n, dtype=torch.int64).pin_memory() for _ in range(2)]
+        ready = torch.cuda.current_stream(self.device).record_event()
+        with torch.cuda.stream(self.side):
+            self.side.wait_event(ready)
+            for buf, t in zip(self.bufs[slot], zyx):
+                buf[:n].copy_(t.reshape(-1), non_blocking=True)
+                t.record_stream(self.side)
+            done = torch.cuda.Event()
+            done.record(self.side)
+        self.jobs.put((slot, done, np.asarray(offset), tuple(zyx[0].shape)))
+
+    def close(self):
+        self.jobs.put(None)
+        self.thread.join()
+        if self.error is not None:
+            raise self.error
+
+
+def job_major_order(chunk_list, max_n_jobs: int):
+    """The order in which the reference's two-level merge sees the chunks: dealt to jobs round-robin (``chunkify``), merged inside a
+    job in chunk order and across jobs in job order."""
+    from ..handler.basics import chunkify
+    return [c for job in chunkify(list(chunk_list), max_n_jobs) for c in job]
+
+
+def extract_contact_sites(chunk_size=None, log=None, max_n_jobs=None, cube_of_interest_bb=None, n_folders_fs: int = 1000,
+                          cube_shape=None, overwrite: bool = False, transf_func_sj_seg=None, *, as_tables: bool = False, device=None):
+    """cs_extraction_steps.py:44-314 with the merging half of its second step (:498-673): contact sites and synapses of the cell
+    segmentation ``config.kd_seg_path`` over a regular chunk grid.  Writes the ``cs_seg`` / ``syn_seg`` KnossosDatasets under
+    ``{wd}/knossosdatasets/`` and returns ``(cs, syn)``: per id what ``_write_props_to_syn_thread`` puts into its storages
+    (``CsTable.as_dict`` / ``SynTable.as_dict``), or the tables themselves with ``as_tables=True``.
+
+    The chunks run on one device in the job-major order of the reference's in-process mode (``job_major_order``), their records
+    stay on the device (``ContactSiteMerger``) and are merged once; no worker files are written.  Not built:
+    the ``AttributeDict`` / ``VoxelStorageDyn`` storages and ``storage_targets_cs.pkl`` (``storage_keys`` names every id's bucket),
+    ``dataset_analysis``, the batch-job dispatch and multi-GPU distribution.  `n_folders_fs` is accepted for the signature."""
+    import logging
+    import os
+    import shutil
+    from .. import global_params
+    from ..handler import basics
+    from ..knossos import ChunkDataset, KnossosDataset
+    from .object_extraction_wrapper import calculate_chunk_numbers_for_box
+    cfg = global_params.config
+    kd = basics.kd_factory(cfg.kd_seg_path)
+    if cube_of_interest_bb is None:
+        cube_of_interest_bb = [np.zeros(3, dtype=np.int32), kd.boundary]
+    if cube_shape is None:
+        cube_shape = (256, 256, 256)
+    if chunk_size is None:
+        chunk_size = (512, 512, 512)
+    if np.any(np.array(chunk_size) % np.array(cube_shape)):
+        raise ValueError('Chunk size must be divisible by cube shape.')
+    if max_n_jobs is None:
+        max_n_jobs = cfg.ncore_total * 8
+    size = np.asarray(cube_of_interest_bb[1]) - np.asarray(cube_of_interest_bb[0]) + 1
+    offset = np.asarray(cube_of_interest_bb[0])
+    _check_worker_config(cfg)
+    wd = cfg.working_dir
+    sd_paths = [f'{wd}/syn_0', f'{wd}/cs_0']            # SegmentationDataset(obj_type, version=0).path
+    if any(os.path.exists(p) for p in sd_paths):
+        if not overwrite:
+            raise FileExistsError('Overwrite was set to False, but SegmentationDataset "syn" or "cs" already exists.')
+        for p in sd_paths:
+            shutil.rmtree(p, ignore_errors=True)
+    cset = ChunkDataset()
+    cset.initialize(kd, kd.boundary, chunk_size, cfg.temp_path + '/chunkdatasets/cs/', box_coords=[0, 0, 0], fit_box_size=True)
+    if log is None:
+        log = logging.getLogger('syconn_amd.extraction')
+    chunk_list, _ = calculate_chunk_numbers_for_box(cset, offset, size)
+    kds = []
+    for ot in ['cs', 'syn']:
+        path_kd = f'{wd}/knossosdatasets/{ot}_seg/'
+        if os.path.isdir(path_kd):
+            log.debug('Found existing KD at {}. Removing it now.'.format(path_kd))
+            shutil.rmtree(path_kd)
+        target_kd = KnossosDataset()
+        target_kd._cube_shape = tuple(int(c) for c in cube_shape)
+        scale = np.array(cfg['scaling'])
+        target_kd.initialize_without_conf(path_kd, kd.boundary, scale, kd.experiment_name, mags=[1, ], create_pyk_conf=True,
+                                          create_knossos_conf=False)
+        kds.append(target_kd)
+    order = job_major_order(chunk_list, max_n_jobs)
+    body = _ChunkExtractor(cfg.kd_seg_path, transf_func_sj_seg, device)
+    with torch.cuda.device(body.dev):
+        merger = ContactSiteMerger(cfg['cell_objects']['min_obj_vx'], body.dev)
+        writer = _CoreWriter(body.dev, *kds)
+        try:
+            for k in order:
+                res, core_offset = body.run(cset.chunk_dict[k])
+                merger.add_chunk(res, core_offset)
+                writer.submit(res, core_offset)
+                del res
+        finally:
+            writer.close()
+        cs_t, syn_t = merger.finish()
+    log.info(f'Finished extraction of initial contact sites (#objects: {merger.n_cs_all}) and synapses'
+             f' (#objects: {merger.n_syn_all}).')
+    if merger.n_syn_all == 0:
+        log.critical('WARNING: Did not find any synapses during extraction step.')
+    if as_tables:
+        return cs_t, syn_t
+    return cs_t.as_dict(), syn_t.as_dict()

@@ -191,6 +191,11 @@ class DynConfig:
         return self['cell_objects']['sym_label']
 
     @property
+    def ncore_total(self) -> int:
+        """config.py:795-797."""
+        return self['nnodes_total'] * self['ncores_per_node']
+
+    @property
     def ngpu_total(self) -> int:
         return self['nnodes_total'] * self['ngpus_per_node']
 

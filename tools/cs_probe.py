@@ -3,6 +3,11 @@ with the worker's halo (overlap 6 + stencil offset (6, 6, 3)), ~2000 jittered-gr
 speckle.  Prints one JSON line; ``--out`` also writes it to a file.
 
     python tools/cs_probe.py [--reps 3] [--out profiles/cs_probe.json]
+    python tools/cs_probe.py --driver [--reps 3] [--out profiles/cs_driver_probe.json]
+
+``--driver``: wall time of contact-site extraction over a dataset of 2 x 2 x 2 chunks (256 x 256 x 128 each, KnossosDatasets in a
+temporary directory on tmpfs when there is one), minimum of ``--reps`` runs: (a) the per-chunk worker over all chunks plus the host
+merge of its files (tests/_cs_driver_ref.py), (b) ``extract_contact_sites``; for (b) also per stage.
 """
 import argparse
 import json
@@ -75,9 +80,12 @@ def main():
     ap.add_argument('--out', default=None)
     ap.add_argument('--part2-out', default=None, help='also time the part-2 stages (sj mask, type masks, statistics, voxel lists, '
                                                       'host copies, one worker chunk) and write them here')
+    ap.add_argument('--driver', action='store_true', help='time the dataset driver against the per-chunk worker + host merge')
     args = ap.parse_args()
     dev = torch.device('cuda', 0)
     lib = L.load()
+    if args.driver:
+        return driver_probe(dev, args)
     st = (13, 13, 7)
     shape = (512 + 12 + 12, 512 + 12 + 12, 512 + 12 + 6)
     seg = voronoi_cells(shape, (13, 13, 12), dev)
@@ -215,6 +223,174 @@ def worker_chunk(dev):
             return (time.perf_counter() - t0) * 1e3
         finally:
             global_params.wd = saved
+
+
+def driver_probe(dev, args):
+    """(a) ``_contact_site_extraction_thread`` over all chunks (one job, the parent path) + the host merge of its files against
+    (b) ``extract_contact_sites`` on the same dataset, and the stages of (b) from a timed copy of its chunk loop."""
+    import shutil
+    import tempfile
+    import time
+    import yaml
+    from syconn_amd import global_params
+    from syconn_amd.extraction import cs_extraction_steps as S
+    from syconn_amd.knossos import ChunkDataset, KnossosDataset
+    from syconn_amd.handler import basics
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tests'))
+    import _cs_driver_ref as D
+    chunk, cube, grid = (256, 256, 128), (128, 128, 128), (2, 2, 2)
+    box = tuple(c * g for c, g in zip(chunk, grid))
+    min_vx = global_params.config['cell_objects']['min_obj_vx']
+    tmp = tempfile.mkdtemp(dir='/dev/shm' if os.path.isdir('/dev/shm') else None)
+    saved = global_params.wd
+    try:
+        def kd(path, seg=None, raw=None):
+            k = KnossosDataset()
+            k._cube_shape = cube
+            k.initialize_without_conf(path, box, (10, 10, 20), 'probe', mags=[1])
+            if seg is not None:
+                k.save_seg(offset=(0, 0, 0), mags=[1], data=np.ascontiguousarray(seg.swapaxes(0, 2)), data_mag=1)
+            if raw is not None:
+                k.save_raw(offset=(0, 0, 0), mags=[1], data=np.ascontiguousarray(raw.swapaxes(0, 2)), data_mag=1)
+        cells = voronoi_cells(box, (8, 8, 4), dev, seed=2).cpu().numpy().view(np.uint32).astype(np.uint64)
+        g = torch.Generator(device=dev).manual_seed(1)
+        sj = torch.where(torch.nn.functional.avg_pool3d(torch.rand((1, 1) + box, generator=g, device=dev), 5, 1, 2)[0, 0] > 0.52, 200, 10)
+        types = torch.randint(0, 4, box, generator=g, device=dev, dtype=torch.int64).cpu().numpy().view(np.uint64)
+        kd(f'{tmp}/cells', seg=cells)
+        kd(f'{tmp}/sj', raw=sj.to(torch.uint8).cpu().numpy())
+        kd(f'{tmp}/types', seg=types)
+        del cells, sj, types
+        wd = f'{tmp}/wd'
+        os.makedirs(wd)
+        with open(f'{wd}/config.yml', 'w') as f:
+            yaml.safe_dump({'scaling': [10, 10, 20], 'syntype_avail': True,
+                            'paths': {'kd_seg': f'{tmp}/cells', 'kd_sj': f'{tmp}/sj', 'kd_sym': f'{tmp}/types', 'kd_asym': f'{tmp}/types'},
+                            'cell_objects': {'sym_label': 1, 'asym_label': 3}}, f)
+        global_params.wd = wd
+        cset = ChunkDataset().initialize(basics.kd_factory(f'{tmp}/cells'), box, chunk, '', box_coords=[0, 0, 0], fit_box_size=True)
+        chunks = [cset.chunk_dict[k] for k in sorted(cset.chunk_dict)]
+
+        def parent_path():
+            for t in ('cs', 'syn'):
+                shutil.rmtree(f'{wd}/knossosdatasets/{t}_seg/', ignore_errors=True)
+                kd(f'{wd}/knossosdatasets/{t}_seg/')
+            shutil.rmtree(f'{tmp}/props', ignore_errors=True)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            S._contact_site_extraction_thread((chunks, f'{tmp}/cells', 0, f'{tmp}/props', None))
+            t1 = time.perf_counter()
+            cs, syn = D.merge_workers([D.load_worker_files(f'{tmp}/props', 0)], min_vx['cs'], min_vx['syn'])
+            return (t1 - t0), (time.perf_counter() - t1), cs, syn
+
+        def driver():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            cs_t, syn_t = S.extract_contact_sites(chunk_size=chunk, cube_shape=cube, max_n_jobs=1, overwrite=True, as_tables=True)
+            return time.perf_counter() - t0, cs_t, syn_t
+
+        def driver_stages():
+            """The chunk loop of ``extract_contact_sites`` with a clock on every stage (same classes, same order)."""
+            kds = []
+            for t in ('cs', 'syn'):
+                shutil.rmtree(f'{wd}/knossosdatasets/{t}_seg/', ignore_errors=True)
+                k = KnossosDataset()
+                k._cube_shape = cube
+                k.initialize_without_conf(f'{wd}/knossosdatasets/{t}_seg/', box, (10, 10, 20), 'probe', mags=[1], create_pyk_conf=True,
+                                          create_knossos_conf=False)
+                kds.append(k)
+            body = S._ChunkExtractor(f'{tmp}/cells', None, dev)
+            t_load = [0.0]
+            for k in (body.kd, body.kd_sj, body.kd_sym, body.kd_asym):
+                for name in ('load_seg', 'load_raw'):
+                    def wrap(fn):
+                        def timed_load(*a, **kw):
+                            t = time.perf_counter()
+                            r = fn(*a, **kw)
+                            t_load[0] += time.perf_counter() - t
+                            return r
+                        return timed_load
+                    setattr(k, name, wrap(getattr(k, name)))
+            merger = S.ContactSiteMerger(min_vx, dev)
+            writer = S._CoreWriter(dev, *kds)
+            ev = []
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            t_body = t_submit = 0.0
+            for ch in chunks:
+                t = time.perf_counter()
+                res, off = body.run(ch)
+                t_body += time.perf_counter() - t
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                merger.add_chunk(res, off)
+                b.record()
+                ev.append((a, b))
+                t = time.perf_counter()
+                writer.submit(res, off)
+                t_submit += time.perf_counter() - t
+                del res
+            t_loop = time.perf_counter() - t0
+            writer.close()
+            t_drain = time.perf_counter() - t0 - t_loop
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            n = [int(v) for v in merger.cursors.cpu().numpy()]
+            cs_t, syn_t = merger.finish()
+            t_finish = time.perf_counter() - t
+            wall = time.perf_counter() - t0
+            return dict(ms_wall=wall * 1e3, ms_chunk_loop=t_loop * 1e3, ms_chunk_body_host_view=t_body * 1e3, ms_kd_loads_in_body=t_load[0] * 1e3,
+                        ms_append_kernels_per_chunk=[round(a.elapsed_time(b), 3) for a, b in ev], ms_submit_cores_host=t_submit * 1e3,
+                        ms_writer_save_seg_overlapped=writer.busy_s * 1e3, ms_writer_drain_after_loop=t_drain * 1e3,
+                        ms_merge_and_table_download=t_finish * 1e3, records=n, kd_load_share_of_wall=t_load[0] / wall)
+
+        def merge_only():
+            """Device time of the two merges and host time of the downloads, on the records of one more pass."""
+            body = S._ChunkExtractor(f'{tmp}/cells', None, dev)
+            merger = S.ContactSiteMerger(min_vx, dev)
+            for ch in chunks:
+                res, off = body.run(ch)
+                merger.add_chunk(res, off)
+            torch.cuda.synchronize()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0 = time.perf_counter()
+            a.record()
+            merger.finish()
+            b.record()
+            torch.cuda.synchronize()
+            return dict(ms_finish_host=(time.perf_counter() - t0) * 1e3, ms_finish_device_span=a.elapsed_time(b))
+
+        S.extract_contact_sites(chunk_size=chunk, cube_shape=cube, max_n_jobs=1, overwrite=True, as_tables=True)      # warm-up: allocator, tables
+        a_runs, b_runs = [], []
+        for _ in range(args.reps):
+            w, m, cs_a, syn_a = parent_path()
+            a_runs.append((w + m, w, m))
+            t, cs_t, syn_t = driver()
+            b_runs.append(t)
+        D.assert_same(cs_t.as_dict(), cs_a, 'cs')                 # both paths computed the same thing
+        D.assert_same(syn_t.as_dict(), syn_a, 'syn')
+        stages = min((driver_stages() for _ in range(args.reps)), key=lambda d: d['ms_wall'])
+        stages.update(merge_only())
+        a_tot = [r[0] for r in a_runs]
+        best_a = min(a_runs)
+        res = dict(box=list(box), chunk=list(chunk), chunks=len(chunks), tmpdir_on_tmpfs=tmp.startswith('/dev/shm'), cs_objects=len(cs_t),
+                   syn_objects=len(syn_t), syn_voxels=int(len(syn_t.voxels)),
+                   a_worker_plus_host_merge_ms=[round(v * 1e3, 1) for v in a_tot], a_min_ms=round(best_a[0] * 1e3, 1),
+                   a_min_worker_ms=round(best_a[1] * 1e3, 1), a_min_host_merge_ms=round(best_a[2] * 1e3, 1),
+                   a_spread_ms=round((max(a_tot) - min(a_tot)) * 1e3, 1),
+                   b_extract_contact_sites_ms=[round(v * 1e3, 1) for v in b_runs], b_min_ms=round(min(b_runs) * 1e3, 1),
+                   b_over_a=round(min(b_runs) / best_a[0], 3),
+                   b_stages={k: ([round(x, 3) for x in v] if isinstance(v, list) and v and isinstance(v[0], float) else
+                                 (round(v, 3) if isinstance(v, float) else v)) for k, v in stages.items()},
+                   device=torch.cuda.get_device_name(0))
+        line = json.dumps(res)
+        print(line)
+        if args.out:
+            os.makedirs(os.path.dirname(args.out) or '.', exist_ok=True)
+            with open(args.out, 'w') as f:
+                f.write(line + '\n')
+    finally:
+        global_params.wd = saved
+        shutil.rmtree(tmp, ignore_errors=True)
 
 
 if __name__ == '__main__':
