@@ -471,6 +471,38 @@ int sd_cs_merge_synapses(const uint64_t* ids_dev, const uint64_t* sizes_dev, con
                          uint64_t* sym_tot_dev, uint64_t* cs_size_dev, uint32_t* vox_begin_dev, uint32_t* vox_out_dev,
                          uint64_t* counts_dev, void* temp_dev, size_t temp_bytes, void* stream);
 
+/* Synapse agglomeration: supervoxel-level syn fragments -> cell-level synapses (/root/reference/syconn/extraction/
+ * cs_processing_steps.py: connected_cluster_kdtree :552-602 and the per-component half of _combine_and_split_syn_thread :453-474),
+ * for all cell pairs ("groups") of a dataset in one set of launches.  vox_dev int32[n_vox][3] holds the voxels in the reference's flat
+ * order (group-major, the fragments of a group in list order, stored order inside a fragment), vox_frag_dev[n_vox] the fragment
+ * number of every voxel (ascending), frag_group_dev[n_frag] the group of every fragment, group_origin_dev int32[n_group][3] the
+ * smallest coordinate of every group.
+ *   sd_syn_ssv_components  replaces :552-602: labels_dev[n_vox] = the component of every voxel, numbered over the whole input in
+ *                          ascending order of the component's smallest flat index (the reference's order inside a group; groups in
+ *                          input order).  Two voxels of a group are joined when their scaled distance (float64 of voxel * scale) is
+ *                          strictly below gap_nm.  cell_host[3] = the binning cell in voxels (its scaled diagonal must be below the
+ *                          gap), bits_host[3] = key bits per axis for the cell coordinates relative to the group origin.  stages: bit 0
+ *                          cells, bit 1 link, bit 2 number (7 = all; a probe times them apart on one scratch).  counts_dev uint64[8] =
+ *                          components, cells, neighbour cells found, of those: too far by their boxes, joined by their boxes alone,
+ *                          in one set already, voxel-tested; [7] != 0: an input row was out of range (results invalid).
+ *   sd_syn_ssv_stats       replaces :456-474: comp_begin_dev[n_comp + 1] = offsets of the components in the (component, flat index)
+ *                          order (sizes are the differences), bbox_dev int32[n_comp][6] (min | max, inclusive), rep_flat_dev[n_comp] =
+ *                          flat index of the voxel nearest the scaled mean of all voxels (ties: the smallest flat index), the voxel
+ *                          count of every (component, fragment) that occurs: pair_comp / pair_frag / pair_begin (n_vox + 1 rows
+ *                          reserved, counts_dev[0] used, pair_begin has one more), and vox_out_dev uint32[.][3] = the voxels of the
+ *                          components with >= min_obj_vx voxels, component-major, ascending flat index inside (counts_dev[1] rows).
+ *                          counts_dev uint64[4]; [3] != 0: a label was >= n_comp.
+ * Scratch for either: sd_syn_ssv_temp_bytes(n_vox).  Limits: n_vox < 2^31, group bits + cell bits <= 63 (SD_ERR_INVALID otherwise). */
+size_t sd_syn_ssv_temp_bytes(size_t n_vox);
+int sd_syn_ssv_components(const int32_t* vox_dev, const uint32_t* vox_frag_dev, const uint32_t* frag_group_dev, const int32_t* group_origin_dev,
+                          size_t n_vox, size_t n_frag, size_t n_group, const double* scale_host, double gap_nm, const int32_t* cell_host,
+                          const int32_t* bits_host, int stages, int32_t* labels_dev, uint64_t* counts_dev, void* temp_dev, size_t temp_bytes,
+                          void* stream);
+int sd_syn_ssv_stats(const int32_t* vox_dev, const uint32_t* vox_frag_dev, const int32_t* labels_dev, size_t n_vox, size_t n_comp,
+                     const double* scale_host, uint64_t min_obj_vx, uint32_t* comp_begin_dev, int32_t* bbox_dev, uint32_t* rep_flat_dev,
+                     uint32_t* pair_comp_dev, uint32_t* pair_frag_dev, uint32_t* pair_begin_dev, uint32_t* vox_out_dev, uint64_t* counts_dev,
+                     void* temp_dev, size_t temp_bytes, void* stream);
+
 /* ---- host-side helpers of the chunk pipeline (no GPU) -----------------------------------------------------------------
  * Multi-threaded strided copy of an (nz, ny, nx)-byte box between two uint8 host arrays whose x-rows are contiguous
  * (strides in bytes), and a multi-threaded memset: what numpy slicing does on one core when the reference cuts a chunk

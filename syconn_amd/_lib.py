@@ -30,7 +30,7 @@ EXPORTS = ['sd_init', 'sd_device_count', 'sd_model_create', 'sd_model_destroy', 
            'sd_seg_boundaries', 'sd_contact_partners_workspace_bytes', 'sd_contact_partners', 'sd_cs_close_dilate',
            'sd_binary_morphology', 'sd_cs_syntype_table_bytes', 'sd_cs_syntype_scan', 'sd_cs_syntype_compact', 'sd_cs_syntype_records',
            'sd_cs_syntype_voxels', 'sd_syntype_masks', 'sd_cs_merge_append', 'sd_cs_merge_temp_bytes', 'sd_cs_merge_objects',
-           'sd_cs_merge_synapses']
+           'sd_cs_merge_synapses', 'sd_syn_ssv_temp_bytes', 'sd_syn_ssv_components', 'sd_syn_ssv_stats']
 
 
 class OpDesc(C.Structure):
@@ -154,6 +154,13 @@ def load():
     lib.sd_cs_merge_objects.argtypes = [vp, vp, vp, vp, sz, C.c_uint64] + [vp] * 8 + [sz, vp]; lib.sd_cs_merge_objects.restype = i32
     lib.sd_cs_merge_synapses.argtypes = [vp] * 7 + [sz, vp, sz, vp, vp, sz, C.c_uint64] + [vp] * 13 + [sz, vp]
     lib.sd_cs_merge_synapses.restype = i32
+    # cs_processing_steps.py:552-602 (connected_cluster_kdtree) and :453-474 (per-component attributes of syn_ssv)
+    lib.sd_syn_ssv_temp_bytes.argtypes = [sz]; lib.sd_syn_ssv_temp_bytes.restype = sz
+    lib.sd_syn_ssv_components.argtypes = [vp, vp, vp, vp, sz, sz, sz, C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_int32),
+                                          C.POINTER(C.c_int32), i32, vp, vp, vp, sz, vp]
+    lib.sd_syn_ssv_components.restype = i32
+    lib.sd_syn_ssv_stats.argtypes = [vp, vp, vp, sz, sz, C.POINTER(C.c_double), C.c_uint64] + [vp] * 8 + [vp, sz, vp]
+    lib.sd_syn_ssv_stats.restype = i32
     _lib = lib
     return lib
 

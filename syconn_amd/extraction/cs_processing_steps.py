@@ -1,0 +1,365 @@
+"""Synapse agglomeration on the MI355X: the device form of ``combine_and_split_syn`` of
+/root/reference/syconn/extraction/cs_processing_steps.py (:239-602), the call that follows ``extract_contact_sites`` in the reference's
+``exec_syns.py`` (:111-116) and turns the supervoxel-level ``syn`` fragments into the cell-level synapses (``syn_ssv``).
+
+``filter_relevant_syn`` (numpy, :260-317) groups the fragments by cell pair; ``connected_cluster`` is the array form of
+``connected_cluster_kdtree`` (:552-602) for one group; ``combine_and_split_syn`` runs all groups of a ``SynTable`` through one set of
+launches (``csrc/sd_syn_ssv.hip``: components, then per-component statistics) and finishes on the host with the reference's own
+arithmetic on a few values per synapse (:458-509).  Where this departs from the reference -- no ``dist_inter_object`` prefilter, a
+lower bound on the gap, all voxels for ``rep_coord``, no meshes, storages or ids -- is written down in DESIGN.md section 7.
+There is no CPU fallback for the device parts.
+"""
+import ctypes as C
+
+import numpy as np
+
+from .. import _lib as L
+
+# the 32 offsets of the reference's first stage (``query_pairs(r=2)`` on voxel coordinates, :581): dx^2 + dy^2 + dz^2 <= 4
+_R2_OFFSETS = np.array([(x, y, z) for x in range(-2, 3) for y in range(-2, 3) for z in range(-2, 3) if 0 < x * x + y * y + z * z <= 4])
+
+
+def min_gap_nm(scaling) -> float:
+    """The longest scaled length of the first-stage offsets.  A gap above it makes the reference's same-fragment edges (voxel
+    distance <= 2) a subset of its gap edges, so that one edge rule describes the partition."""
+    s = np.asarray(scaling, np.float64)
+    return float(np.sqrt(((_R2_OFFSETS * s) ** 2).sum(1)).max())
+
+
+def _check_gap(cs_gap_nm, scaling):
+    s = np.asarray(scaling, np.float64).reshape(-1)
+    if s.shape != (3,) or not np.all(s > 0):
+        raise ValueError(f'scaling must be three positive voxel sizes, got {scaling}')
+    gap = float(cs_gap_nm)
+    if not gap > min_gap_nm(s):
+        raise ValueError(f'cs_gap_nm = {gap} must exceed {min_gap_nm(s)} nm, the longest scaled offset within two voxels at scaling '
+                         f'{s.tolist()}: below it the reference joins voxels of one fragment that the gap would not')
+    return gap, s
+
+
+def choose_cell(scaling, cs_gap_nm):
+    """The binning cell (voxels per axis) of the component search: per axis the largest extent whose share of the scaled diagonal is
+    gap / sqrt(3), shrunk until ``||(c - 1) * scaling||`` (float64) is strictly below the gap -- all voxels of a group inside one cell
+    are then connected without a test.  The largest such cell keeps the neighbourhood a wave has to walk smallest."""
+    gap, s = _check_gap(cs_gap_nm, scaling)
+    c = np.maximum(np.floor(gap / (np.sqrt(3.0) * s)).astype(np.int64), 0) + 1
+    while not np.sqrt((((c - 1) * s) ** 2).sum()) < gap:
+        a = int(np.argmax((c - 1) * s))
+        c[a] -= 1
+    return c
+
+
+def _mapping_arrays(sv_ids, ssv_ids):
+    if ssv_ids is None:                                    # a dict sv -> ssv
+        items = sorted(dict(sv_ids).items())
+        sv = np.array([k for k, _ in items], np.uint64)
+        ssv = np.array([v for _, v in items], np.int64)
+    else:
+        sv, ssv = np.asarray(sv_ids).astype(np.uint64), np.asarray(ssv_ids).astype(np.int64)
+        if sv.shape != ssv.shape or sv.ndim != 1:
+            raise ValueError('sv_ids and ssv_ids must be two 1D arrays of equal length')
+        order = np.argsort(sv, kind='stable')
+        sv, ssv = sv[order], ssv[order]
+    if len(sv) > 1 and np.any(sv[1:] == sv[:-1]):
+        raise ValueError('a supervoxel id occurs twice in the sv -> ssv mapping')
+    return sv, ssv
+
+
+def filter_relevant_syn(syn_ids, sv_ids, ssv_ids=None):
+    """``filter_relevant_syn`` (:260-317) for ``syn`` objects, on arrays: the partner supervoxels of every id are decoded as
+    ``cs_id_to_partner_ids_vec`` does (``id >> 32``, the rest), a supervoxel above the largest mapped id becomes 0, every supervoxel is
+    mapped to its cell (unmapped: 0), rows whose two cells are both > 0 and differ are kept and keyed by ``(max << 32) + min``.
+    The sv -> ssv mapping is two arrays, or a dict as `sv_ids`.
+
+    -> ``(enc_keys, group_begin, syn_rows)``: the keys in order of first appearance (uint64), offsets (groups + 1) into `syn_rows`,
+    and the rows of `syn_ids` group by group, in input order inside a group -- the reference's ``defaultdict(list)`` as arrays."""
+    ids = np.asarray(syn_ids).astype(np.uint64).reshape(-1)
+    sv_map, ssv_map = _mapping_arrays(sv_ids, ssv_ids)
+    hi = ids >> np.uint64(32)
+    sv = np.stack([hi, ids - (hi << np.uint64(32))], 1)
+    if len(sv_map):
+        sv[sv > sv_map[-1]] = 0
+        at = np.minimum(np.searchsorted(sv_map, sv), len(sv_map) - 1)
+        mapped = np.where(sv_map[at] == sv, ssv_map[at], 0)
+    else:
+        mapped = np.zeros(sv.shape, np.int64)
+    rows = np.flatnonzero(np.all(mapped > 0, axis=1) & (mapped[:, 0] != mapped[:, 1]))
+    pairs = mapped[rows].astype(np.uint64)
+    enc = (pairs.max(1) << np.uint64(32)) + pairs.min(1) if len(rows) else np.zeros(0, np.uint64)
+    uniq, first, inv = np.unique(enc, return_index=True, return_inverse=True)
+    rank_of_uniq = np.empty(len(uniq), np.int64)
+    appearance = np.argsort(first, kind='stable')
+    rank_of_uniq[appearance] = np.arange(len(uniq))
+    rank = rank_of_uniq[inv.reshape(-1)]
+    order = np.argsort(rank, kind='stable')
+    group_begin = np.concatenate(([0], np.cumsum(np.bincount(rank, minlength=len(uniq))))).astype(np.int64)
+    return uniq[appearance], group_begin, rows[order].astype(np.int64)
+
+
+class SynSsvTable:
+    """Cell-level synapses that passed ``min_obj_vx['syn_ssv']`` (plain numpy), in the reference's processing order: groups (cell pairs)
+    in first-appearance order, the components of a group in ascending order of their smallest flat voxel index.
+
+    ``neuron_partners`` (n, 2) uint64 = (larger, smaller) cell id; ``sizes`` int64; ``rep_coords`` (n, 3) int32; ``bounding_boxes``
+    (n, 2, 3) int32 = [min, max] inclusive; ``voxels`` (v, 3) uint32 / ``vox_begin`` (n + 1), ascending flat index inside a row;
+    ``cs_ids`` uint64 / ``cs_begin`` (n + 1) = the fragment ids the reference aggregates (its ``synix_list`` indexing unless
+    ``reference_indexing=False``); ``frag_ids`` / ``frag_counts`` / ``frag_begin`` = the fragments that really contribute and their exact
+    voxel counts, whatever the indexing; ``sym_prop``, ``asym_prop``, ``syn_type_sym_ratio`` float64, ``syn_sign`` int64;
+    ``ordinal`` int64 = the row's count among ALL components of the run before the size filter (dropped components consume an id
+    in the reference), ``group`` / ``group_ordinal`` = the row's group and its count inside that group."""
+
+    COLUMNS = ('neuron_partners', 'sizes', 'rep_coords', 'bounding_boxes', 'voxels', 'vox_begin', 'cs_ids', 'cs_begin', 'frag_ids',
+               'frag_counts', 'frag_begin', 'sym_prop', 'asym_prop', 'syn_type_sym_ratio', 'syn_sign', 'ordinal', 'group', 'group_ordinal')
+
+    def __init__(self, **columns):
+        for name in self.COLUMNS:
+            setattr(self, name, columns[name])
+        self.n_components = int(columns.get('n_components', len(self.sizes)))     # before the size filter
+
+    def __len__(self):
+        return len(self.sizes)
+
+    def as_dict(self) -> list:
+        """One attribute dict per row with the keys ``_combine_and_split_syn_thread`` stores (:470-513) except the mesh entries:
+        ``neuron_partners``, ``rep_coord`` (int32), ``bounding_box`` (uint32, as ``np.min`` / ``np.max`` of the voxel cache), ``size``,
+        ``cs_ids`` (list), ``sym_prop``, ``asym_prop``, ``syn_type_sym_ratio``, ``syn_sign``; and ``voxels``, what it puts into the voxel
+        storage."""
+        c, v = self.cs_begin.tolist(), self.vox_begin.tolist()
+        bb = self.bounding_boxes.astype(np.uint32)
+        out = []
+        for i in range(len(self)):
+            ratio = self.syn_type_sym_ratio[i]
+            out.append(dict(neuron_partners=self.neuron_partners[i], rep_coord=self.rep_coords[i], bounding_box=bb[i],
+                            size=int(self.sizes[i]), cs_ids=self.cs_ids[c[i]:c[i + 1]].tolist(), sym_prop=self.sym_prop[i],
+                            asym_prop=self.asym_prop[i], syn_type_sym_ratio=-1 if ratio == -1 else ratio,
+                            syn_sign=int(self.syn_sign[i]), voxels=self.voxels[v[i]:v[i + 1]]))
+        return out
+
+
+def build_syn_ssv_table(enc_keys, group_frag_begin, frag_ids, frag_sym_prop, frag_asym_prop, comp_group, comp_sizes, comp_bbox, comp_rep_vox,
+                        pair_comp, pair_frag, pair_cnt, voxels, scaling, min_obj_vx: int, sym_thresh: float, reference_indexing: bool = True):
+    """The host edge (:458-509), numpy only: from the per-component statistics of ALL components (in processing order: `comp_group`,
+    `comp_sizes`, `comp_bbox` (k, 2, 3), `comp_rep_vox` (k, 3) = the voxel nearest the centre of mass), the voxel count of every
+    (component, fragment) that occurs (`pair_comp` ascending, `pair_frag` = fragment number over all groups, ascending inside a
+    component) and the voxel rows of the kept components, to the ``SynSsvTable``.  The fragments' attributes come group by group
+    (`group_frag_begin` offsets into `frag_ids` / `frag_sym_prop` / `frag_asym_prop`).
+
+    The weights ``cnt / np.sum(cnt)``, ``np.sum(w * props)``, the ratio and the sign are the reference's expressions.  With
+    `reference_indexing` fragment j of a group is looked up as ``max(j - 1, 0)``, as the reference's ``synix_list`` has it (:434-440):
+    fragments 0 and 1 share fragment 0's attributes and fold their counts, the last fragment's attributes are never read."""
+    enc_keys = np.asarray(enc_keys, np.uint64)
+    gfb = np.asarray(group_frag_begin, np.int64)
+    frag_ids = np.asarray(frag_ids, np.uint64)
+    frag_sym_prop, frag_asym_prop = np.asarray(frag_sym_prop, np.float64), np.asarray(frag_asym_prop, np.float64)
+    comp_group, comp_sizes = np.asarray(comp_group, np.int64), np.asarray(comp_sizes, np.int64)
+    pair_comp, pair_frag, pair_cnt = np.asarray(pair_comp, np.int64), np.asarray(pair_frag, np.int64), np.asarray(pair_cnt, np.int64)
+    scaling = np.asarray(scaling, np.float32)               # SegmentationDataset.scaling is float32 (segmentation.py:1747)
+    K = len(comp_sizes)
+    keep = comp_sizes >= int(min_obj_vx)                    # :462 ``np.sum(cnt) < min_obj_vx -> continue``
+    rows = np.flatnonzero(keep)
+    n = len(rows)
+    row_of_comp = np.full(K, -1, np.int64)
+    row_of_comp[rows] = np.arange(n)
+    first_of_group = np.concatenate(([0], np.cumsum(np.bincount(comp_group, minlength=len(enc_keys)))))[:-1] if K else np.zeros(0, np.int64)
+    # the pairs of the kept rows
+    pk = keep[pair_comp] if len(pair_comp) else np.zeros(0, bool)
+    p_row, p_frag, p_cnt = row_of_comp[pair_comp[pk]], pair_frag[pk], pair_cnt[pk]
+    frag_begin = np.concatenate(([0], np.cumsum(np.bincount(p_row, minlength=n)))).astype(np.int64)
+    # the index the reference reads the attributes at
+    j = p_frag - gfb[comp_group[rows]][p_row] if n else np.zeros(0, np.int64)
+    ix = np.maximum(j - 1, 0) if reference_indexing else j
+    head = np.ones(len(ix), bool)
+    if len(ix) > 1:
+        head[1:] = (p_row[1:] != p_row[:-1]) | (ix[1:] != ix[:-1])
+    starts = np.flatnonzero(head)
+    a_row, a_ix = p_row[starts], (ix + gfb[comp_group[rows]][p_row])[starts] if n else np.zeros(0, np.int64)
+    a_cnt = np.add.reduceat(p_cnt, starts) if len(starts) else np.zeros(0, np.int64)       # np.unique(..., return_counts=True)
+    cs_begin = np.concatenate(([0], np.cumsum(np.bincount(a_row, minlength=n)))).astype(np.int64)
+    sym, asym = np.zeros(n, np.float64), np.zeros(n, np.float64)
+    m = np.diff(cs_begin)
+    one = np.flatnonzero(m == 1)                             # a single entry: weight cnt / cnt = 1.0, the sum of one product is itself
+    sym[one], asym[one] = frag_sym_prop[a_ix[cs_begin[one]]], frag_asym_prop[a_ix[cs_begin[one]]]
+    for r in np.flatnonzero(m != 1).tolist():
+        sl = slice(cs_begin[r], cs_begin[r + 1])
+        this_syn_ids_cnt = a_cnt[sl]
+        this_agg_syn_weights = this_syn_ids_cnt / np.sum(this_syn_ids_cnt)
+        sym[r] = np.sum(this_agg_syn_weights * np.array(frag_sym_prop[a_ix[sl]].tolist()))
+        asym[r] = np.sum(this_agg_syn_weights * np.array(frag_asym_prop[a_ix[sl]].tolist()))
+    zero = sym + asym == 0
+    with np.errstate(divide='ignore', invalid='ignore'):
+        ratio = np.where(zero, -1.0, sym / (asym + sym))
+    sign = np.where(ratio > sym_thresh, -1, 1).astype(np.int64)
+    rep_vox = np.asarray(comp_rep_vox)[rows].astype(np.uint32).reshape(n, 3)
+    rep = (rep_vox * scaling // scaling).astype(np.int32)    # :472 on the chosen voxel
+    hi = enc_keys[comp_group[rows]] >> np.uint64(32)
+    partners = np.stack([hi, enc_keys[comp_group[rows]] - (hi << np.uint64(32))], 1) if n else np.zeros((0, 2), np.uint64)
+    sizes = comp_sizes[rows]
+    return SynSsvTable(neuron_partners=partners, sizes=sizes, rep_coords=rep, bounding_boxes=np.asarray(comp_bbox, np.int32).reshape(K, 2, 3)[rows],
+                       voxels=np.asarray(voxels, np.uint32).reshape(-1, 3), vox_begin=np.concatenate(([0], np.cumsum(sizes))).astype(np.int64),
+                       cs_ids=frag_ids[a_ix], cs_begin=cs_begin, frag_ids=frag_ids[p_frag], frag_counts=p_cnt, frag_begin=frag_begin,
+                       sym_prop=sym, asym_prop=asym, syn_type_sym_ratio=ratio, syn_sign=sign, ordinal=rows.astype(np.int64),
+                       group=comp_group[rows], group_ordinal=rows - first_of_group[comp_group[rows]] if n else np.zeros(0, np.int64),
+                       n_components=K)
+
+
+# ---- the device part ------------------------------------------------------------------------------------------------------------------
+class _Agglomerator:
+    """The launches of ``csrc/sd_syn_ssv.hip`` over one flat voxel array: `vox` (N, 3) int32 in the reference's flat order, `vox_frag` (N)
+    the fragment number of every voxel (ascending), `frag_group` (F) the group of every fragment.  The voxel rows are uploaded once."""
+
+    def __init__(self, vox, vox_frag, frag_group, n_group, scaling, cs_gap_nm, device=None):
+        import torch
+        from .find_object_properties import _cs_device
+        self.gap, self.scale = _check_gap(cs_gap_nm, scaling)
+        self.lib = L.load()
+        self.dev = _cs_device(device)
+        self.torch = torch
+        vox = np.ascontiguousarray(vox, dtype=np.int32).reshape(-1, 3)
+        self.n, self.n_frag, self.n_group = len(vox), len(frag_group), int(n_group)
+        self.cell = choose_cell(self.scale, self.gap)
+        self.counts = np.zeros(8, np.int64)
+        if not self.n:
+            return
+        if self.n >= 2 ** 31:
+            raise ValueError('combine_and_split_syn: fewer than 2^31 voxel rows per call')
+        vox_frag = np.ascontiguousarray(vox_frag, dtype=np.uint32)
+        frag_group = np.ascontiguousarray(frag_group, dtype=np.uint32)
+        vgroup = frag_group[vox_frag]
+        gstart = np.flatnonzero(np.concatenate(([True], vgroup[1:] != vgroup[:-1])))
+        if len(gstart) != self.n_group or np.any(np.diff(vgroup.astype(np.int64)) < 0):
+            raise ValueError('combine_and_split_syn: the voxels must come group by group, every group non-empty')
+        lo, hi = np.minimum.reduceat(vox, gstart, axis=0), np.maximum.reduceat(vox, gstart, axis=0)
+        n_cells = ((hi.astype(np.int64) - lo) // self.cell).max(0) + 1
+        self.bits = np.array([int(v - 1).bit_length() for v in n_cells.tolist()], np.int32)
+        if int(self.bits.sum()) + int(self.n_group - 1).bit_length() > 63:
+            raise ValueError(f'combine_and_split_syn: {self.n_group} groups spanning up to {n_cells.tolist()} cells do not fit a 63-bit key')
+        up = lambda a: torch.from_numpy(a).to(self.dev)
+        self.vox_d, self.frag_d, self.fgroup_d, self.origin_d = up(vox), up(vox_frag.view(np.int32)), up(frag_group.view(np.int32)), up(lo)
+        self.tmp = torch.empty(self.lib.sd_syn_ssv_temp_bytes(self.n), dtype=torch.uint8, device=self.dev)
+        self.labels_d = torch.empty(self.n, dtype=torch.int32, device=self.dev)
+        self.counts_d = torch.zeros(8, dtype=torch.int64, device=self.dev)
+        self._scale_c = (C.c_double * 3)(*self.scale.tolist())
+        self._cell_c = (C.c_int32 * 3)(*self.cell.tolist())
+        self._bits_c = (C.c_int32 * 3)(*self.bits.tolist())
+
+    def components(self, stages: int = 7):
+        """Launch the stages (bit 0 cells, bit 1 link, bit 2 number) on the current stream; asynchronous."""
+        if not self.n:
+            return
+        stream = self.torch.cuda.current_stream(self.dev).cuda_stream
+        L.check(self.lib.sd_syn_ssv_components(self.vox_d.data_ptr(), self.frag_d.data_ptr(), self.fgroup_d.data_ptr(), self.origin_d.data_ptr(),
+                                               self.n, self.n_frag, self.n_group, self._scale_c, self.gap, self._cell_c, self._bits_c,
+                                               int(stages), self.labels_d.data_ptr(), self.counts_d.data_ptr(), self.tmp.data_ptr(),
+                                               self.tmp.numel(), stream), 'sd_syn_ssv_components')
+
+    def read_counts(self):
+        """-> counts of ``sd_syn_ssv_components`` on the host (waits for the device)."""
+        if self.n:
+            self.counts = self.counts_d.cpu().numpy()
+            if self.counts[7]:
+                raise RuntimeError('sd_syn_ssv_components: a voxel row was outside its group box or fragment table')
+        return self.counts
+
+    def labels(self) -> np.ndarray:
+        return self.labels_d.cpu().numpy() if self.n else np.zeros(0, np.int32)
+
+    def stats(self, min_obj_vx: int):
+        """Per-component statistics of all `n_comp` components and the voxel rows of the kept ones (waits for the device).
+        -> dict of numpy arrays for ``build_syn_ssv_table``."""
+        torch, dev, n = self.torch, self.dev, self.n
+        K = int(self.counts[0])
+        if not n:
+            z = np.zeros(0, np.int64)
+            return dict(comp_sizes=z, comp_bbox=np.zeros((0, 2, 3), np.int32), comp_rep_flat=z, pair_comp=z, pair_frag=z, pair_cnt=z,
+                        voxels=np.zeros((0, 3), np.uint32))
+        new = lambda m, dt: torch.empty(m, dtype=dt, device=dev)
+        i32 = torch.int32
+        comp_begin, bbox, rep = new(K + 1, i32), new((K, 6), i32), new(K, i32)
+        p_comp, p_frag, p_begin, vout = new(n + 1, i32), new(n + 1, i32), new(n + 1, i32), new((n, 3), i32)
+        cnt = torch.zeros(4, dtype=torch.int64, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        L.check(self.lib.sd_syn_ssv_stats(self.vox_d.data_ptr(), self.frag_d.data_ptr(), self.labels_d.data_ptr(), n, K, self._scale_c,
+                                          int(min_obj_vx), comp_begin.data_ptr(), bbox.data_ptr(), rep.data_ptr(), p_comp.data_ptr(),
+                                          p_frag.data_ptr(), p_begin.data_ptr(), vout.data_ptr(), cnt.data_ptr(), self.tmp.data_ptr(),
+                                          self.tmp.numel(), stream), 'sd_syn_ssv_stats')
+        P, n_kept, _, bad = (int(v) for v in cnt.cpu().numpy())
+        if bad:
+            raise RuntimeError('sd_syn_ssv_stats: a component label was out of range')
+        u = lambda t: t.cpu().numpy().view(np.uint32).astype(np.int64)
+        begin = u(comp_begin)
+        pb = u(p_begin[:P + 1])
+        return dict(comp_sizes=np.diff(begin), comp_bbox=bbox.cpu().numpy().reshape(K, 2, 3), comp_rep_flat=u(rep), pair_comp=u(p_comp[:P]),
+                    pair_frag=u(p_frag[:P]), pair_cnt=np.diff(pb), voxels=vout[:n_kept].cpu().numpy().view(np.uint32))
+
+
+def _flatten(voxel_lists):
+    lists = [np.asarray(v).reshape(-1, 3) for v in voxel_lists]
+    vox = np.concatenate(lists).astype(np.int64) if lists else np.zeros((0, 3), np.int64)
+    if len(vox) and (vox.min() < -2 ** 31 or vox.max() >= 2 ** 31):
+        raise ValueError('voxel coordinates must fit int32')
+    return vox.astype(np.int32), np.repeat(np.arange(len(lists), dtype=np.uint32), [len(v) for v in lists])
+
+
+def connected_cluster(voxel_lists, cs_gap_nm, scaling, device=None) -> np.ndarray:
+    """The array form of ``connected_cluster_kdtree(voxel_lists, dist_intra_object=cs_gap_nm, dist_inter_object=20000, scale=scaling)``
+    (:552-602) for one group: `voxel_lists` = one (n_i, 3) voxel array per fragment.  -> int32 component number of every voxel of
+    ``np.concatenate(voxel_lists)``; components are numbered in ascending order of their smallest flat index, the order of the
+    reference's list of sets.  Two voxels are joined when their scaled distance is strictly below `cs_gap_nm`; there is no
+    ``dist_inter_object`` prefilter.  Raises ValueError for a gap that does not exceed ``min_gap_nm(scaling)``."""
+    _check_gap(cs_gap_nm, scaling)
+    vox, vfrag = _flatten(voxel_lists)
+    if not len(vox):
+        return np.zeros(0, np.int32)
+    agg = _Agglomerator(vox, vfrag, np.zeros(len(voxel_lists), np.uint32), 1, scaling, cs_gap_nm, device)
+    agg.components()
+    agg.read_counts()
+    return agg.labels()
+
+
+def combine_and_split_syn(syn_table, sv_ids, ssv_ids=None, scaling=None, cs_gap_nm=None, min_obj_vx=None, sym_thresh=None,
+                          reference_indexing: bool = True, device=None, return_stats: bool = False):
+    """``combine_and_split_syn`` (:320-387) with its worker ``_combine_and_split_syn_thread`` (:390-549) on the ``SynTable`` that
+    ``extract_contact_sites(as_tables=True)`` returns: the fragments are grouped by cell pair (``filter_relevant_syn``; `sv_ids` /
+    `ssv_ids` = the supervoxel -> cell mapping as two arrays, or a dict as `sv_ids`), the voxels of every pair are split into
+    components closer than `cs_gap_nm` (all pairs in one set of launches), and every component with at least
+    ``min_obj_vx['syn_ssv']`` voxels becomes a row of the returned ``SynSsvTable``.  `scaling` falls back to ``config['scaling']``,
+    `cs_gap_nm`, `min_obj_vx` (a dict or a number) and `sym_thresh` to ``config['cell_objects']``.  ``reference_indexing=False`` looks
+    every fragment's attributes up at its own index instead of the reference's ``max(j - 1, 0)``.
+
+    Not built: meshes (``mesh_bb``, ``mesh_area``), the storages, the id assignment (``ordinal`` is what it
+    needs) and the batch jobs."""
+    from .. import global_params
+    cfg = global_params.config
+    if scaling is None:
+        scaling = cfg['scaling']
+    cobj = cfg['cell_objects']
+    cs_gap_nm = cobj['cs_gap_nm'] if cs_gap_nm is None else cs_gap_nm
+    min_obj_vx = cobj['min_obj_vx'] if min_obj_vx is None else min_obj_vx
+    min_vx = int(min_obj_vx['syn_ssv'] if isinstance(min_obj_vx, dict) else min_obj_vx)
+    sym_thresh = cobj['sym_thresh'] if sym_thresh is None else sym_thresh
+    gap, scale = _check_gap(cs_gap_nm, scaling)
+    enc_keys, group_begin, syn_rows = filter_relevant_syn(syn_table.ids, sv_ids, ssv_ids)
+    vb = np.asarray(syn_table.vox_begin, np.int64)
+    run_start, run_len = vb[:-1][syn_rows], np.diff(vb)[syn_rows]
+    if np.any(np.add.reduceat(run_len, group_begin[:-1]) == 0) if len(enc_keys) else False:
+        raise ValueError('Voxels not available for syn-objects of a cell pair.')                     # :444-447
+    begin = np.concatenate(([0], np.cumsum(run_len)))
+    src = np.repeat(run_start - begin[:-1], run_len) + np.arange(begin[-1])
+    vox = np.asarray(syn_table.voxels).reshape(-1, 3)[src]
+    if len(vox) and int(vox.max()) >= 2 ** 31:
+        raise ValueError('voxel coordinates must fit int32')
+    vox_frag = np.repeat(np.arange(len(syn_rows), dtype=np.uint32), run_len)
+    frag_group = np.repeat(np.arange(len(enc_keys), dtype=np.uint32), np.diff(group_begin))
+    agg = _Agglomerator(vox.astype(np.int32), vox_frag, frag_group, len(enc_keys), scale, gap, device)
+    agg.components()
+    counts = agg.read_counts()
+    st = agg.stats(min_vx)
+    # the group of every component is the group of any of its voxels: take the representative
+    comp_group = frag_group[vox_frag[st['comp_rep_flat']]].astype(np.int64) if agg.n else np.zeros(0, np.int64)
+    table = build_syn_ssv_table(enc_keys, group_begin, np.asarray(syn_table.ids)[syn_rows], np.asarray(syn_table.sym_prop)[syn_rows],
+                                np.asarray(syn_table.asym_prop)[syn_rows], comp_group, st['comp_sizes'], st['comp_bbox'],
+                                vox[st['comp_rep_flat']] if agg.n else np.zeros((0, 3), np.uint32), st['pair_comp'], st['pair_frag'],
+                                st['pair_cnt'], st['voxels'], scale, min_vx, float(sym_thresh), reference_indexing)
+    if return_stats:
+        return table, dict(counts=counts, cell=agg.cell, n_vox=agg.n, n_groups=len(enc_keys))
+    return table

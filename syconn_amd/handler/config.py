@@ -67,6 +67,10 @@ DEFAULTS = {
         # data, thresholded at 123 (cs_extraction_steps.py:414-424)
         'sym_label': None,
         'asym_label': None,
+        # synapse agglomeration (config.yml:152, :164): fragments of one cell pair closer than cs_gap_nm form one syn_ssv object;
+        # a symmetric ratio above sym_thresh gives syn_sign -1
+        'cs_gap_nm': 250,
+        'sym_thresh': 0.225,
     },
 }
 
