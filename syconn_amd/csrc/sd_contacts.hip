@@ -1,10 +1,8 @@
 // Contact-site extraction: the stencil of block_processing_C.pyx and the per-site closing of
 // _contact_site_extraction_thread on the MI355X.  Volumes are (X,Y,Z) with z fastest; every call is asynchronous on `stream`.
 #include "../../include/syconn_dense.h"
-#include <hip/hip_runtime.h>
+#include "sd_host_util.h"
 #include <stdint.h>
-
-extern int sd_fail_msg(int code, const char* msg);      // sd_api.hip: sets sd_last_error()
 
 namespace {
 
@@ -246,18 +244,13 @@ __global__ __launch_bounds__(256) void k_claim_finish(uint64_t* __restrict__ out
         if (out[i] == ~0ull) out[i] = 0;
 }
 
-inline int grid_of(int64_t total, int cap = 256 * 64) {
-    int64_t g = (total + 255) / 256;
-    return (int)(g < 1 ? 1 : g > cap ? cap : g);
-}
-
 }  // namespace
 
 int sd_seg_boundaries(const uint32_t* seg_dev, int X, int Y, int Z, uint8_t* mask_dev, void* stream) {
     if (!seg_dev || !mask_dev || X <= 0 || Y <= 0 || Z <= 0) return sd_fail_msg(SD_ERR_INVALID, "sd_seg_boundaries: bad argument");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(k_seg_boundaries, dim3(grid_of((int64_t)X * Y * Z)), dim3(256), 0, s, seg_dev, X, Y, Z, mask_dev);
-    return hipGetLastError() == hipSuccess ? SD_OK : sd_fail_msg(SD_ERR_HIP, "sd_seg_boundaries: launch failed");
+    hipLaunchKernelGGL(k_seg_boundaries, dim3(grid_for((int64_t)X * Y * Z, 256 * 64)), dim3(256), 0, s, seg_dev, X, Y, Z, mask_dev);
+    return launch_status("sd_seg_boundaries: launch failed");
 }
 
 size_t sd_contact_partners_workspace_bytes(void) { return 256; }
@@ -280,9 +273,9 @@ int sd_contact_partners(const uint8_t* edges_dev, const uint32_t* seg_dev, int X
     const dim3 grid((OX + CP_TX - 1) / CP_TX, (OY + CP_TY - 1) / CP_TY, (OZ + CP_TZ - 1) / CP_TZ);
     hipLaunchKernelGGL(k_contact_partners, grid, dim3(256), lds, s, edges_dev, seg_dev, X, Y, Z, sx, sy, sz, out_dev, OX, OY, OZ,
                        n_ovf);
-    hipLaunchKernelGGL(k_contact_partners_exact, dim3(grid_of((int64_t)OX * OY * OZ, 2048)), dim3(256), 0, s, seg_dev, X, Y, Z,
+    hipLaunchKernelGGL(k_contact_partners_exact, dim3(grid_for((int64_t)OX * OY * OZ, 2048)), dim3(256), 0, s, seg_dev, X, Y, Z,
                        sx, sy, sz, out_dev, OX, OY, OZ, n_ovf);
-    return hipGetLastError() == hipSuccess ? SD_OK : sd_fail_msg(SD_ERR_HIP, "sd_contact_partners: launch failed");
+    return launch_status("sd_contact_partners: launch failed");
 }
 
 int sd_cs_close_dilate(const uint64_t* c0_dev, int X, int Y, int Z, const int64_t* table_dev, int64_t n_obj, int64_t tot_vox,
@@ -293,12 +286,12 @@ int sd_cs_close_dilate(const uint64_t* c0_dev, int X, int Y, int Z, const int64_
     if (n_obj > 0 && ws_bytes < 2 * (size_t)tot_vox) return sd_fail_msg(SD_ERR_NOMEM, "sd_cs_close_dilate: workspace too small");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const size_t n = (size_t)X * Y * Z;
-    if (flags & SD_CS_FIRST) hipLaunchKernelGGL(k_claim_init, dim3(grid_of((int64_t)n)), dim3(256), 0, s, c0_dev, n, out_dev);
+    if (flags & SD_CS_FIRST) hipLaunchKernelGGL(k_claim_init, dim3(grid_for(n, 256 * 64)), dim3(256), 0, s, c0_dev, n, out_dev);
     if (n_obj > 0 && tot_vox > 0) {
         uint8_t* A = reinterpret_cast<uint8_t*>(workspace_dev);
         uint8_t* B = A + tot_vox;
         CdArgs a{table_dev, n_obj, tot_vox, c0_dev, X, Y, Z, nullptr, nullptr, 0, 0, 0, 0, 0, 0};
-        const dim3 g(grid_of(tot_vox)), b(256);
+        const dim3 g(grid_for(tot_vox, 256 * 64)), b(256);
         // one truncated L1 distance transform (three 1D passes) of the set given by (src, thr) on `from`; result in the returned plane
         auto dt = [&](int src, int thr, const uint8_t* from, int win, int outside) -> uint8_t* {
             uint8_t* bufs[2] = {A, B};
@@ -330,6 +323,6 @@ int sd_cs_close_dilate(const uint64_t* c0_dev, int X, int Y, int Z, const int64_
             hipLaunchKernelGGL(k_box_claim, g, b, 0, s, a, out_dev);
         }
     }
-    if (flags & SD_CS_LAST) hipLaunchKernelGGL(k_claim_finish, dim3(grid_of((int64_t)n)), dim3(256), 0, s, out_dev, n);
-    return hipGetLastError() == hipSuccess ? SD_OK : sd_fail_msg(SD_ERR_HIP, "sd_cs_close_dilate: launch failed");
+    if (flags & SD_CS_LAST) hipLaunchKernelGGL(k_claim_finish, dim3(grid_for(n, 256 * 64)), dim3(256), 0, s, out_dev, n);
+    return launch_status("sd_cs_close_dilate: launch failed");
 }

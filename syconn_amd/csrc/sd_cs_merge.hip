@@ -20,8 +20,6 @@
 #include "../../include/syconn_dense.h"
 #include "sd_sortseg.h"
 
-extern int sd_fail_msg(int code, const char* msg);      // sd_api.hip: sets sd_last_error()
-
 namespace {
 
 // cursors[0] cs records, [1] syn records, [2] voxel rows.  Records are counted past their maximum (the caller sees the overrun);
@@ -166,17 +164,12 @@ __global__ __launch_bounds__(256) void k_csm_copy_runs(const u32* perm, const u3
     }
 }
 
-// carve the caller's scratch: [u64 n x 2 | u32 n x 11 | rocPRIM]
-struct CsmScratch { u64 *skey, *joined; u32 *i0, *perm, *head, *seg, *keepseg, *f_head, *f_rec, *f_vox, *s_head, *s_rec, *s_vox; void* prim; size_t prim_n; };
-size_t csm_scratch_bytes(size_t n) { return 2 * up256(n * 8) + 11 * up256(n * 4) + prim_bytes(n); }
-CsmScratch csm_carve(void* base, size_t n) {
-    CsmScratch s; char* p = reinterpret_cast<char*>(base);
-    s.skey = reinterpret_cast<u64*>(p); p += up256(n * 8);
-    s.joined = reinterpret_cast<u64*>(p); p += up256(n * 8);
-    u32** u[11] = {&s.i0, &s.perm, &s.head, &s.seg, &s.keepseg, &s.f_head, &s.f_rec, &s.f_vox, &s.s_head, &s.s_rec, &s.s_vox};
-    for (int k = 0; k < 11; ++k) { *u[k] = reinterpret_cast<u32*>(p); p += up256(n * 4); }
-    s.prim = p; s.prim_n = prim_bytes(n);
-    return s;
+struct CsmScratch { u64 *skey, *joined; u32 *i0, *perm, *head, *seg, *keepseg, *f_head, *f_rec, *f_vox, *s_head, *s_rec, *s_vox; PrimScratch prim; };
+size_t layout(CsmScratch& w, void* base, size_t n) {
+    ScratchAlloc a(base);
+    a.take_into(n, w.skey, w.joined, w.i0, w.perm, w.head, w.seg, w.keepseg, w.f_head, w.f_rec, w.f_vox, w.s_head, w.s_rec, w.s_vox);
+    w.prim = take_prim(a, n);
+    return a.used;
 }
 
 struct CsmIn {
@@ -191,35 +184,25 @@ int csm_merge(const char* what, const CsmIn& in, size_t n, u64 min_vx, const Csm
     if (hipMemsetAsync(o.counts, 0, 4 * sizeof(u64), s) != hipSuccess) return sd_fail_msg(SD_ERR_HIP, "memset failed");
     if (n == 0) return SD_OK;
     if (n >= (1ull << 32) || in.n_vox >= (1ull << 32)) return sd_fail_msg(SD_ERR_INVALID, "sd_cs_merge: < 2^32 records and voxel rows per call");
-    if (!temp || temp_bytes < csm_scratch_bytes(n)) return sd_fail_msg(SD_ERR_INVALID, "sd_cs_merge: scratch smaller than sd_cs_merge_temp_bytes(n)");
-    CsmScratch w = csm_carve(temp, n);
-    const int g = grid_for(n);
-    hipLaunchKernelGGL(k_iota, dim3(g), dim3(256), 0, s, w.i0, (u64)n);
-    size_t pb = w.prim_n;
-    if (rocprim::radix_sort_pairs(w.prim, pb, in.ids, w.skey, w.i0, w.perm, n, 0, 64, s) != hipSuccess)
-        return sd_fail_msg(SD_ERR_HIP, "sd_cs_merge: radix sort failed");
-    hipLaunchKernelGGL(k_heads, dim3(g), dim3(256), 0, s, w.skey, (const u64*)nullptr, w.head, (u64)n);
-    pb = w.prim_n;
-    if (rocprim::inclusive_scan(w.prim, pb, w.head, w.seg, n, rocprim::plus<u32>(), s) != hipSuccess)
-        return sd_fail_msg(SD_ERR_HIP, "sd_cs_merge: scan failed");
+    CsmScratch w;
+    if (!temp || temp_bytes < layout(w, temp, n)) return sd_fail_msg(SD_ERR_INVALID, "sd_cs_merge: scratch smaller than sd_cs_merge_temp_bytes(n)");
+    const char* who = "sd_cs_merge";
+    const int g = grid_for(n, 4096);
+    if (int rc = sort_by_key(who, w.prim, in.ids, w.skey, w.i0, w.perm, n, 64, s); rc != SD_OK) return rc;
+    if (int rc = number_segments(who, w.prim, w.skey, nullptr, w.head, w.seg, n, s); rc != SD_OK) return rc;
     hipLaunchKernelGGL(k_csm_keep, dim3(g), dim3(256), 0, s, w.skey, w.perm, w.head, w.seg, in.sizes, (u64)n, min_vx, in.join_ids,
                        in.join_sizes, in.n_join, in.join, w.keepseg, w.joined);
     hipLaunchKernelGGL(k_csm_flags, dim3(g), dim3(256), 0, s, w.perm, w.head, w.seg, w.keepseg, in.sizes, in.vpos ? 1 : 0, (u64)n, w.f_head,
                        w.f_rec, w.f_vox);
-    u32* fl[3] = {w.f_head, w.f_rec, w.f_vox};
-    u32* sc[3] = {w.s_head, w.s_rec, w.s_vox};
-    for (int k = 0; k < 3; ++k) {
-        pb = w.prim_n;
-        if (rocprim::inclusive_scan(w.prim, pb, fl[k], sc[k], n, rocprim::plus<u32>(), s) != hipSuccess)
-            return sd_fail_msg(SD_ERR_HIP, "sd_cs_merge: scan failed");
-    }
+    if (int rc = scan_u32(who, w.prim, w.f_head, w.s_head, n, s); rc != SD_OK) return rc;
+    if (int rc = scan_u32(who, w.prim, w.f_rec, w.s_rec, n, s); rc != SD_OK) return rc;
+    if (int rc = scan_u32(who, w.prim, w.f_vox, w.s_vox, n, s); rc != SD_OK) return rc;
     hipLaunchKernelGGL(k_csm_reduce, dim3(g), dim3(256), 0, s, w.skey, w.perm, w.head, w.seg, w.keepseg, w.s_head, w.s_rec, w.s_vox, w.joined,
                        in.sizes, in.rc, in.bb, in.asym, in.sym, (u64)n, o);
     if (in.vpos && in.n_vox)
-        hipLaunchKernelGGL(k_csm_copy_runs, dim3(grid_for(in.n_vox)), dim3(256), 0, s, w.perm, w.s_vox, in.sizes, in.vpos, (u64)n, in.vox,
+        hipLaunchKernelGGL(k_csm_copy_runs, dim3(grid_for(in.n_vox, 4096)), dim3(256), 0, s, w.perm, w.s_vox, in.sizes, in.vpos, (u64)n, in.vox,
                            in.n_vox, vox_out);
-    if (hipGetLastError() != hipSuccess) return sd_fail_msg(SD_ERR_HIP, what);
-    return SD_OK;
+    return launch_status(what);
 }
 
 }  // namespace
@@ -240,19 +223,19 @@ int sd_cs_merge_append(const int64_t* rec_dev, size_t n, const int64_t* vox_dev,
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     u64* cur = reinterpret_cast<u64*>(cursors_dev);
     if (n)
-        hipLaunchKernelGGL(k_csm_append, dim3(grid_for(n)), dim3(256), 0, s, rec_dev, (u64)n, ox, oy, oz, reinterpret_cast<u64*>(cs_ids_dev),
+        hipLaunchKernelGGL(k_csm_append, dim3(grid_for(n, 4096)), dim3(256), 0, s, rec_dev, (u64)n, ox, oy, oz, reinterpret_cast<u64*>(cs_ids_dev),
                            cs_rc_dev, cs_bbox_dev, reinterpret_cast<u64*>(cs_sizes_dev), (u64)max_cs, reinterpret_cast<u64*>(syn_ids_dev),
                            syn_rc_dev, syn_bbox_dev, reinterpret_cast<u64*>(syn_sizes_dev), reinterpret_cast<u64*>(syn_asym_dev),
                            reinterpret_cast<u64*>(syn_sym_dev), reinterpret_cast<u64*>(syn_vpos_dev), (u64)max_syn, cur);
     if (n_vox) {
-        hipLaunchKernelGGL(k_csm_vox_append, dim3(grid_for(3 * (u64)n_vox)), dim3(256), 0, s, vox_dev, (u64)n_vox, vox_all_dev, (u64)max_vox,
+        hipLaunchKernelGGL(k_csm_vox_append, dim3(grid_for(3 * (u64)n_vox, 4096)), dim3(256), 0, s, vox_dev, (u64)n_vox, vox_all_dev, (u64)max_vox,
                            cur);
         hipLaunchKernelGGL(k_csm_vox_advance, dim3(1), dim3(1), 0, s, cur, (u64)n_vox);
     }
-    return hipGetLastError() == hipSuccess ? SD_OK : sd_fail_msg(SD_ERR_HIP, "sd_cs_merge_append: launch failed");
+    return launch_status("sd_cs_merge_append: launch failed");
 }
 
-size_t sd_cs_merge_temp_bytes(size_t n_records) { return csm_scratch_bytes(n_records ? n_records : 1); }
+size_t sd_cs_merge_temp_bytes(size_t n_records) { CsmScratch w; return layout(w, nullptr, n_records ? n_records : 1); }
 
 int sd_cs_merge_objects(const uint64_t* ids_dev, const uint64_t* sizes_dev, const int32_t* rc_dev, const int32_t* bbox_dev, size_t n,
                         uint64_t min_obj_vx, uint64_t* uniq_ids_dev, uint64_t* tot_sizes_dev, int32_t* last_rc_dev,

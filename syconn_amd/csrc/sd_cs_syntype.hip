@@ -13,8 +13,6 @@
 #include <stdint.h>
 #include "sd_hash.h"
 
-extern int sd_fail_msg(int code, const char* msg);      // sd_api.hip: sets sd_last_error()
-
 namespace {
 
 // Table of `cap` slots, structure of arrays in one buffer:
@@ -259,7 +257,7 @@ int sd_cs_syntype_scan(const void* cs_dev, int dtype, const uint8_t* syn_dev, co
         if (dtype == SD_U64) hipLaunchKernelGGL(k_cst_scan<uint64_t>, dim3(grid), dim3(256), 0, s, p);
         else hipLaunchKernelGGL(k_cst_scan<uint32_t>, dim3(grid), dim3(256), 0, s, p);
     }
-    return hipGetLastError() == hipSuccess ? SD_OK : sd_fail_msg(SD_ERR_HIP, "sd_cs_syntype_scan: launch failed");
+    return launch_status("sd_cs_syntype_scan: launch failed");
 }
 
 int sd_cs_syntype_compact(const void* table_dev, size_t cap, uint64_t* ids_dev, int32_t* slots_dev, size_t max_out,
@@ -270,7 +268,7 @@ int sd_cs_syntype_compact(const void* table_dev, size_t cap, uint64_t* ids_dev, 
     if (hipMemsetAsync(count_dev, 0, sizeof(uint64_t), s) != hipSuccess) return sd_fail_msg(SD_ERR_HIP, "memset failed");
     hipLaunchKernelGGL(k_cst_compact, dim3(grid_for(cap)), dim3(256), 0, s, cst_table(const_cast<void*>(table_dev), cap),
                        reinterpret_cast<u64*>(ids_dev), slots_dev, reinterpret_cast<u64*>(count_dev), (u64)max_out);
-    return hipGetLastError() == hipSuccess ? SD_OK : sd_fail_msg(SD_ERR_HIP, "sd_cs_syntype_compact: launch failed");
+    return launch_status("sd_cs_syntype_compact: launch failed");
 }
 
 int sd_cs_syntype_records(const void* table_dev, size_t cap, const int32_t* slots_dev, int64_t n, int nx, int ny, int nz,
@@ -281,7 +279,7 @@ int sd_cs_syntype_records(const void* table_dev, size_t cap, const int32_t* slot
     if (n) hipLaunchKernelGGL(k_cst_gather, dim3(grid_for((u64)n)), dim3(256), 0, s, cst_table(const_cast<void*>(table_dev), cap),
                               slots_dev, (long)n, nx, ny, nz, rec_dev);
     hipLaunchKernelGGL(k_cst_offsets, dim3(1), dim3(256), 0, s, rec_dev, (long)n, n_syn_dev);
-    return hipGetLastError() == hipSuccess ? SD_OK : sd_fail_msg(SD_ERR_HIP, "sd_cs_syntype_records: launch failed");
+    return launch_status("sd_cs_syntype_records: launch failed");
 }
 
 int sd_cs_syntype_voxels(const void* cs_dev, int dtype, const uint8_t* syn_dev, int X, int Y, int Z, int ox, int oy, int oz,
@@ -302,7 +300,7 @@ int sd_cs_syntype_voxels(const void* cs_dev, int dtype, const uint8_t* syn_dev, 
     else
         hipLaunchKernelGGL(k_cst_voxels<uint32_t>, dim3((unsigned)n), dim3(256), 0, s, reinterpret_cast<const uint32_t*>(cs_dev), syn_dev,
                            Y, Z, ox, oy, oz, rec_dev, n_syn, ofx, ofy, ofz, vox_dev, status_dev);
-    return hipGetLastError() == hipSuccess ? SD_OK : sd_fail_msg(SD_ERR_HIP, "sd_cs_syntype_voxels: launch failed");
+    return launch_status("sd_cs_syntype_voxels: launch failed");
 }
 
 int sd_syntype_masks(const void* vol_dev, int dtype, size_t n, uint64_t label_a, uint64_t label_b, uint8_t* out_a_dev,
@@ -317,7 +315,7 @@ int sd_syntype_masks(const void* vol_dev, int dtype, size_t n, uint64_t label_a,
     else
         hipLaunchKernelGGL(k_syntype_masks<uint64_t>, dim3(grid_for(n)), dim3(256), 0, s, reinterpret_cast<const uint64_t*>(vol_dev),
                            (u64)n, (u64)label_a, (u64)label_b, out_a_dev, out_b_dev, 0);
-    return hipGetLastError() == hipSuccess ? SD_OK : sd_fail_msg(SD_ERR_HIP, "sd_syntype_masks: launch failed");
+    return launch_status("sd_syntype_masks: launch failed");
 }
 
 }  // extern "C"

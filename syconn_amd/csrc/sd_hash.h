@@ -2,7 +2,7 @@
 // linear probing over u64 keys in caller-owned device memory, key 0 = empty slot (label 0 is background and never inserted),
 // and the run structure of a wave that lets a pass issue one table update per run of equal labels instead of one per voxel.
 #pragma once
-#include <hip/hip_runtime.h>
+#include "sd_host_util.h"
 #include <stdint.h>
 
 namespace {
@@ -39,7 +39,8 @@ __device__ __forceinline__ int run_length(bool head, int lane, int nvalid) {
     return next - lane;
 }
 
-inline bool pow2(u64 v) { return v && !(v & (v - 1)); }
-inline int grid_for(u64 n, int cap = 4096) { u64 g = (n + 255) / 256; return (int)(g < 1 ? 1 : (g > (u64)cap ? (u64)cap : g)); }
+// the grid-stride launches over a table or a volume in the files that include this header share one cap (sd_host_util.h defines
+// grid_for; this declaration only gives it the default, and the label-statistics tests read the figure from here)
+inline int grid_for(u64 n, int cap = 4096);
 
 }  // namespace

@@ -19,13 +19,11 @@
 // component's root is its first voxel in raster order); roots are ranked by an exclusive scan -> ids 1..N in
 // scipy.ndimage.label's order, bit-exact.
 #include "../../include/syconn_dense.h"
-#include <hip/hip_runtime.h>
+#include "sd_host_util.h"
 #include <stdint.h>
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
-
-extern int sd_fail_msg(int code, const char* msg);
 
 namespace {
 
@@ -1236,9 +1234,6 @@ __global__ __launch_bounds__(256) void k_sqrt_out(const int* g, size_t total, fl
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) out[i] = sqrtf((float)g[i]);
 }
 
-inline int grid_for(size_t n, int cap = 8192) { size_t g = (n + 255) / 256; return (int)(g < 1 ? 1 : (g > (size_t)cap ? (size_t)cap : g)); }
-inline size_t rup256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 struct WsLayout { size_t a, b, rank, blockcnt, bbox, total; };
 Dom make_dom(int X, int Y, int Z, int P) {
     Dom d{X, Y, Z, P, X + 2 * P, Y + 2 * P, Z + 2 * P, 0};
@@ -1252,10 +1247,10 @@ WsLayout ws_layout(int X, int Y, int Z, int P) {
     // (run_cc scans blocks of mask WORDS, X * Y * PZW of them: more than voxels for thin volumes with a large pad)
     const size_t nblk = (std::max(nvox, (size_t)X * Y * d.PZW) + SCAN_BLOCK - 1) / SCAN_BLOCK;
     size_t cur = 0;
-    w.a = cur; cur += rup256(pwords * 4);
-    w.b = cur; cur += rup256(pwords * 4);
-    w.rank = cur; cur += rup256(nvox * 4);
-    w.blockcnt = cur; cur += rup256((nblk + 1) * 4);
+    w.a = cur; cur += up256(pwords * 4);
+    w.b = cur; cur += up256(pwords * 4);
+    w.rank = cur; cur += up256(nvox * 4);
+    w.blockcnt = cur; cur += up256((nblk + 1) * 4);
     w.bbox = cur; cur += 256;
     w.total = cur;
     return w;
@@ -1317,7 +1312,7 @@ void run_morph(hipStream_t s, uint32_t*& A, uint32_t*& B, const Dom& d, int* bbo
         for (int k = 0; k < nfirst + nsecond; ++k) {
             const int dil = k < nfirst ? first_dilate : 1 - first_dilate;
             const int crop = (k == nfirst + nsecond - 1) ? 1 : 0;
-            hipLaunchKernelGGL(k_morph_bits, dim3(grid_for(pwords)), dim3(256), 0, s, A, B, d, bbox, wpad, dil, crop, o);
+            hipLaunchKernelGGL(k_morph_bits, dim3(grid_for(pwords, 8192)), dim3(256), 0, s, A, B, d, bbox, wpad, dil, crop, o);
             std::swap(A, B);
         }
     }
@@ -1326,17 +1321,17 @@ void run_morph(hipStream_t s, uint32_t*& A, uint32_t*& B, const Dom& d, int* bbo
 void run_cc(hipStream_t s, const uint32_t* A, const Dom& d, int* L, int* rank, int* blockcnt, int* max_label_dev, uint8_t* mask_out,
             int* cnt = nullptr) {      // cnt: voxels per label, entries 0 .. N + 1 (zeroed here, once N is known)
     const size_t nvox = (size_t)d.X * d.Y * d.Z, nwords = (size_t)d.X * d.Y * d.PZW;
-    hipLaunchKernelGGL(k_cc_init_heads, dim3(grid_for(nwords)), dim3(256), 0, s, A, d, L);
-    if (mask_out) hipLaunchKernelGGL(k_mask_bytes, dim3(grid_for(nvox)), dim3(256), 0, s, A, d, mask_out);
-    hipLaunchKernelGGL(k_cc_merge_runs, dim3(grid_for(nwords)), dim3(256), 0, s, A, d, L);
+    hipLaunchKernelGGL(k_cc_init_heads, dim3(grid_for(nwords, 8192)), dim3(256), 0, s, A, d, L);
+    if (mask_out) hipLaunchKernelGGL(k_mask_bytes, dim3(grid_for(nvox, 8192)), dim3(256), 0, s, A, d, mask_out);
+    hipLaunchKernelGGL(k_cc_merge_runs, dim3(grid_for(nwords, 8192)), dim3(256), 0, s, A, d, L);
     const int nblk = (int)((nwords + SCAN_BLOCK - 1) / SCAN_BLOCK);
     hipLaunchKernelGGL(k_cc_compress_count, dim3(nblk), dim3(256), 0, s, A, d, nwords, L, blockcnt);
     hipLaunchKernelGGL(k_cc_scan_blocks, dim3(1), dim3(1024), 0, s, blockcnt, nblk, max_label_dev);
     hipLaunchKernelGGL(k_cc_rank, dim3(nblk), dim3(256), 0, s, A, d, nwords, L, blockcnt, rank);
     if (cnt) hipLaunchKernelGGL(k_fill_ids, dim3(1024), dim3(256), 0, s, cnt, max_label_dev, 2, 0);
-    hipLaunchKernelGGL(k_cc_head_labels, dim3(grid_for(nwords)), dim3(256), 0, s, A, d, L, rank, cnt);
+    hipLaunchKernelGGL(k_cc_head_labels, dim3(grid_for(nwords, 8192)), dim3(256), 0, s, A, d, L, rank, cnt);
     (void)hipMemsetAsync(L, 0, nvox * sizeof(int), s);      // (after the head passes: they use L as the union-find array)
-    hipLaunchKernelGGL(k_cc_fill_runs, dim3(grid_for(nwords)), dim3(256), 0, s, A, d, L, rank);
+    hipLaunchKernelGGL(k_cc_fill_runs, dim3(grid_for(nwords, 8192)), dim3(256), 0, s, A, d, L, rank);
 }
 int cut_of(double threshold) {
     // (uint8 p > t) <=> p >= floor(t) + 1; threshold 0 means "already a 0/1 mask" (object_extraction_steps.py:316): cut 1
@@ -1354,15 +1349,15 @@ WsLayout2 ws_layout2(int X, int Y, int Z, int P) {
     const size_t pwords = (size_t)d.PX * d.PY * d.PZW, nvox = (size_t)X * Y * Z;
     l.T = nvox / 2 + 1026;
     size_t cur = l.w.total;
-    l.mbits = cur; cur += rup256(pwords * 4);
-    l.mk = cur; cur += rup256(nvox * 4);
-    l.comp = cur; cur += rup256(nvox * 4);
-    l.g = cur; cur += rup256(nvox * 4);
-    for (int i = 0; i < 9; ++i) { l.tab[i] = cur; cur += rup256(l.T * 4); }
-    for (int i = 0; i < 6; ++i) { l.bag[i] = cur; cur += rup256(nvox * 4); }      // the flood's pool: 48 bytes per voxel of a
-    for (int i = 0; i < 2; ++i) { l.ga[i] = cur; cur += rup256(nvox * 8); }       // multi-marker component, sized for the worst case
-    l.cl = cur; cur += rup256(nvox * 4);
-    l.wl = cur; cur += rup256(nvox * 4);
+    l.mbits = cur; cur += up256(pwords * 4);
+    l.mk = cur; cur += up256(nvox * 4);
+    l.comp = cur; cur += up256(nvox * 4);
+    l.g = cur; cur += up256(nvox * 4);
+    for (int i = 0; i < 9; ++i) { l.tab[i] = cur; cur += up256(l.T * 4); }
+    for (int i = 0; i < 6; ++i) { l.bag[i] = cur; cur += up256(nvox * 4); }      // the flood's pool: 48 bytes per voxel of a
+    for (int i = 0; i < 2; ++i) { l.ga[i] = cur; cur += up256(nvox * 8); }       // multi-marker component, sized for the worst case
+    l.cl = cur; cur += up256(nvox * 4);
+    l.wl = cur; cur += up256(nvox * 4);
     l.scal = cur; cur += 256;
     l.total = cur;
     return l;
@@ -1396,14 +1391,14 @@ WsBufs ws_bufs(char* wb, const WsLayout2& l) {
 void flood_components(hipStream_t s, const uint32_t* M, const uint32_t* seed_bits, const Dom& d, const int* mk, const WsBufs& B,
                       int32_t* max_label_dev, uint8_t* mask_out_dev) {      // seed_bits: optional, == {mk > 0}
     const size_t nvox = (size_t)d.X * d.Y * d.Z;
-    const int gt = grid_for(B.T);
+    const int gt = grid_for(B.T, 8192);
     int *rank = B.rank, *blockcnt = B.blockcnt, *comp = B.comp, *mn = B.mn, *mx = B.mx, *off = B.off, *hcnt = B.hcnt, *scal = B.scal;
     run_cc(s, M, d, comp, rank, blockcnt, scal + 1, mask_out_dev, off);      // off[c] = voxels of component c (entries 0 .. NC + 1)
     hipLaunchKernelGGL(k_fill_ids, dim3(1024), dim3(256), 0, s, mn, scal + 1, 2, 0x7fffffff);
     hipLaunchKernelGGL(k_fill_ids, dim3(1024), dim3(256), 0, s, mx, scal + 1, 2, 0);
     hipLaunchKernelGGL(k_fill_ids, dim3(1024), dim3(256), 0, s, hcnt, scal + 1, 2, 0);
     hipLaunchKernelGGL(k_fill_int, dim3(1), dim3(256), 0, s, max_label_dev, (size_t)1, 0);
-    hipLaunchKernelGGL(k_comp_markers, dim3(grid_for(seed_bits ? (size_t)d.X * d.Y * d.PZW : nvox)), dim3(256), 0, s, seed_bits, d, comp, mk, nvox, mn, mx, max_label_dev);
+    hipLaunchKernelGGL(k_comp_markers, dim3(grid_for(seed_bits ? (size_t)d.X * d.Y * d.PZW : nvox, 8192)), dim3(256), 0, s, seed_bits, d, comp, mk, nvox, mn, mx, max_label_dev);
     hipLaunchKernelGGL(k_comp_keep_multi, dim3(gt), dim3(256), 0, s, scal + 1, mn, mx, off);
     hipLaunchKernelGGL(k_scan_excl, dim3(1), dim3(1024), 0, s, off, scal + 1, 1, scal + 4);
 }
@@ -1416,7 +1411,7 @@ void flood_run(hipStream_t s, const uint32_t* M, const uint32_t* seed_bits, cons
     const WsPool& pool = B.pool;
     const bool sequential = getenv("SD_WS_SEQUENTIAL") != nullptr;
     if (sequential) {
-        hipLaunchKernelGGL(k_ws_init_seq, dim3(grid_for(nvox)), dim3(256), 0, s, comp, mk, g, nvox, mn, mx, off, hcnt, pool.ga[0], pool.cl, labels_dev);
+        hipLaunchKernelGGL(k_ws_init_seq, dim3(grid_for(nvox, 8192)), dim3(256), 0, s, comp, mk, g, nvox, mn, mx, off, hcnt, pool.ga[0], pool.cl, labels_dev);
         hipLaunchKernelGGL(k_ws_flood_seq, dim3(4096), dim3(64), 0, s, comp, g, d, scal + 1, mn, mx, off, hcnt, pool.ga[0], pool.cl, labels_dev);
     } else {
         (void)hipMemsetAsync(labels_dev, 0, nvox * sizeof(int), s);
@@ -1488,10 +1483,10 @@ int sd_object_segmentation(const uint8_t* prob_dev, int X, int Y, int Z, double 
     uint32_t* B = reinterpret_cast<uint32_t*>(wb + w.b);
     const Dom d = make_dom(X, Y, Z, P);
     const size_t pwords = (size_t)d.PX * d.PY * d.PZW;
-    hipLaunchKernelGGL(k_threshold_bits, dim3(grid_for(pwords)), dim3(256), 0, s, prob_dev, cut_of(threshold), d, A);
+    hipLaunchKernelGGL(k_threshold_bits, dim3(grid_for(pwords, 8192)), dim3(256), 0, s, prob_dev, cut_of(threshold), d, A);
     run_morph(s, A, B, d, reinterpret_cast<int*>(wb + w.bbox), ops, iterations, n_ops, o);
     run_cc(s, A, d, labels_dev, reinterpret_cast<int*>(wb + w.rank), reinterpret_cast<int*>(wb + w.blockcnt), max_label_dev, mask_out_dev);
-    return hipGetLastError() == hipSuccess ? SD_OK : sd_fail_msg(SD_ERR_HIP, "sd_object_segmentation: launch failed");
+    return launch_status("sd_object_segmentation: launch failed");
 }
 
 // apply_morphological_operations on a 0/1 mask (cs_extraction_steps.py:405-408 with image.py:358-438, 485-519): the same threshold
@@ -1516,10 +1511,10 @@ int sd_binary_morphology(const uint8_t* in_dev, int X, int Y, int Z, double thre
     uint32_t* B = reinterpret_cast<uint32_t*>(wb + w.b);
     const Dom d = make_dom(X, Y, Z, P);
     const size_t pwords = (size_t)d.PX * d.PY * d.PZW;
-    hipLaunchKernelGGL(k_threshold_bits, dim3(grid_for(pwords)), dim3(256), 0, s, in_dev, cut_of(threshold), d, A);
+    hipLaunchKernelGGL(k_threshold_bits, dim3(grid_for(pwords, 8192)), dim3(256), 0, s, in_dev, cut_of(threshold), d, A);
     run_morph(s, A, B, d, reinterpret_cast<int*>(wb + w.bbox), ops, iterations, n_ops, o);
-    hipLaunchKernelGGL(k_mask_bytes, dim3(grid_for((size_t)X * Y * Z)), dim3(256), 0, s, A, d, mask_out_dev);
-    return hipGetLastError() == hipSuccess ? SD_OK : sd_fail_msg(SD_ERR_HIP, "sd_binary_morphology: launch failed");
+    hipLaunchKernelGGL(k_mask_bytes, dim3(grid_for((size_t)X * Y * Z, 8192)), dim3(256), 0, s, A, d, mask_out_dev);
+    return launch_status("sd_binary_morphology: launch failed");
 }
 
 size_t sd_objseg_watershed_workspace_bytes(int X, int Y, int Z, int max_iterations) {
@@ -1565,10 +1560,10 @@ int sd_object_segmentation_watershed(const uint8_t* prob_dev, int X, int Y, int 
     int *cnt = tab[0], *rd = tab[1], *D = tab[2], *K = tab[3], *map = tab[4];
     const Dom d = make_dom(X, Y, Z, P);
     const size_t pwords = (size_t)d.PX * d.PY * d.PZW, nvox = (size_t)X * Y * Z;
-    const int gt = grid_for(l.T);
+    const int gt = grid_for(l.T, 8192);
 
     // tmp_data: threshold + the operations before the first erosion (:316-322)
-    hipLaunchKernelGGL(k_threshold_bits, dim3(grid_for(pwords)), dim3(256), 0, s, prob_dev, cut_of(threshold), d, A);
+    hipLaunchKernelGGL(k_threshold_bits, dim3(grid_for(pwords, 8192)), dim3(256), 0, s, prob_dev, cut_of(threshold), d, A);
     run_morph(s, A, B, d, bbox, ops, iterations, n_ops, o);
     if (hipMemcpyAsync(M, A, pwords * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return sd_fail_msg(SD_ERR_HIP, "sd_object_segmentation_watershed: copy failed");
     // markers: the erosions (and whatever follows them), scipy.ndimage.label (:323-327)
@@ -1581,8 +1576,8 @@ int sd_object_segmentation_watershed(const uint8_t* prob_dev, int X, int Y, int 
         hipLaunchKernelGGL(k_seed_lists, dim3(gt), dim3(256), 0, s, cnt, rd, scal + 0, min_seed_vx, D, K);
         hipLaunchKernelGGL(k_seed_prefix, dim3(gt), dim3(256), 0, s, D, K, scal + 0, scal + 2, scal + 3);
         hipLaunchKernelGGL(k_seed_map, dim3(gt), dim3(256), 0, s, cnt, rd, D, scal + 0, scal + 2, scal + 3, min_seed_vx, map);
-        hipLaunchKernelGGL(k_apply_map, dim3(grid_for(pwords)), dim3(256), 0, s, A, d, mk, map);
-        hipLaunchKernelGGL(k_seed_bits_sync, dim3(grid_for(pwords)), dim3(256), 0, s, A, d, mk);
+        hipLaunchKernelGGL(k_apply_map, dim3(grid_for(pwords, 8192)), dim3(256), 0, s, A, d, mk, map);
+        hipLaunchKernelGGL(k_seed_bits_sync, dim3(grid_for(pwords, 8192)), dim3(256), 0, s, A, d, mk);
     }
     if (markers_out_dev && hipMemcpyAsync(markers_out_dev, mk, nvox * 4, hipMemcpyDeviceToDevice, s) != hipSuccess)
         return sd_fail_msg(SD_ERR_HIP, "sd_object_segmentation_watershed: copy failed");
@@ -1592,12 +1587,12 @@ int sd_object_segmentation_watershed(const uint8_t* prob_dev, int X, int Y, int 
     const int* const ecomp = distance_out_dev ? nullptr : B2.comp;
     (void)hipMemsetAsync(g, 0, nvox * sizeof(int), s);          // the passes write foreground voxels only: both buffers are 0 elsewhere
     (void)hipMemsetAsync(rank, 0, nvox * sizeof(int), s);
-    hipLaunchKernelGGL(k_edt_z, dim3(grid_for(pwords)), dim3(256), 0, s, M, d, (int)pixel_pitch_xyz[2], g, ecomp, B2.mn, B2.mx);
-    hipLaunchKernelGGL(k_edt_axis, dim3(grid_for(nvox)), dim3(256), 0, s, M, g, rank, d, 1, (int)pixel_pitch_xyz[1], ecomp, B2.mn, B2.mx);
-    hipLaunchKernelGGL(k_edt_axis, dim3(grid_for(nvox)), dim3(256), 0, s, M, rank, g, d, 2, (int)pixel_pitch_xyz[0], ecomp, B2.mn, B2.mx);
-    if (distance_out_dev) hipLaunchKernelGGL(k_sqrt_out, dim3(grid_for(nvox)), dim3(256), 0, s, g, nvox, distance_out_dev);
+    hipLaunchKernelGGL(k_edt_z, dim3(grid_for(pwords, 8192)), dim3(256), 0, s, M, d, (int)pixel_pitch_xyz[2], g, ecomp, B2.mn, B2.mx);
+    hipLaunchKernelGGL(k_edt_axis, dim3(grid_for(nvox, 8192)), dim3(256), 0, s, M, g, rank, d, 1, (int)pixel_pitch_xyz[1], ecomp, B2.mn, B2.mx);
+    hipLaunchKernelGGL(k_edt_axis, dim3(grid_for(nvox, 8192)), dim3(256), 0, s, M, rank, g, d, 2, (int)pixel_pitch_xyz[0], ecomp, B2.mn, B2.mx);
+    if (distance_out_dev) hipLaunchKernelGGL(k_sqrt_out, dim3(grid_for(nvox, 8192)), dim3(256), 0, s, g, nvox, distance_out_dev);
     flood_run(s, M, A, d, mk, g, B2, labels_dev);
-    return hipGetLastError() == hipSuccess ? SD_OK : sd_fail_msg(SD_ERR_HIP, "sd_object_segmentation_watershed: launch failed");
+    return launch_status("sd_object_segmentation_watershed: launch failed");
 }
 
 int sd_marker_flood(const int32_t* d2_dev, const int32_t* markers_dev, const uint8_t* mask_dev, int X, int Y, int Z,
@@ -1611,11 +1606,11 @@ int sd_marker_flood(const int32_t* d2_dev, const int32_t* markers_dev, const uin
     char* const wb = reinterpret_cast<char*>(ws);
     const Dom d = make_dom(X, Y, Z, 0);
     uint32_t* M = reinterpret_cast<uint32_t*>(wb + l.mbits);
-    hipLaunchKernelGGL(k_threshold_bits, dim3(grid_for((size_t)d.PX * d.PY * d.PZW)), dim3(256), 0, s, mask_dev, 1, d, M);
+    hipLaunchKernelGGL(k_threshold_bits, dim3(grid_for((size_t)d.PX * d.PY * d.PZW, 8192)), dim3(256), 0, s, mask_dev, 1, d, M);
     const WsBufs B = ws_bufs(wb, l);
     flood_components(s, M, nullptr, d, markers_dev, B, max_label_dev, nullptr);
     flood_run(s, M, nullptr, d, markers_dev, d2_dev, B, labels_dev);
-    return hipGetLastError() == hipSuccess ? SD_OK : sd_fail_msg(SD_ERR_HIP, "sd_marker_flood: launch failed");
+    return launch_status("sd_marker_flood: launch failed");
 }
 
 // ---- Gaussian pre-smoothing of a probability map + threshold (object_extraction_steps.py:296-297, 316-317) -------------------
@@ -1647,13 +1642,13 @@ int sd_gaussian_threshold(const uint8_t* prob_dev, int X, int Y, int Z, const do
         for (int k = -t.r; k <= t.r; ++k) sum += (t.w[k + t.r] = std::exp(-0.5 * (double)k * k / (sg * sg)));
         for (int k = 0; k <= 2 * t.r; ++k) t.w[k] /= sum;
         float* const dst = buf[nb];
-        if (cur) hipLaunchKernelGGL(k_gauss_axis<float>, dim3(grid_for(nvox)), dim3(256), 0, s, cur, dst, nvox, n[a], stride[a], t);
-        else hipLaunchKernelGGL(k_gauss_axis<uint8_t>, dim3(grid_for(nvox)), dim3(256), 0, s, prob_dev, dst, nvox, n[a], stride[a], t);
+        if (cur) hipLaunchKernelGGL(k_gauss_axis<float>, dim3(grid_for(nvox, 8192)), dim3(256), 0, s, cur, dst, nvox, n[a], stride[a], t);
+        else hipLaunchKernelGGL(k_gauss_axis<uint8_t>, dim3(grid_for(nvox, 8192)), dim3(256), 0, s, prob_dev, dst, nvox, n[a], stride[a], t);
         cur = dst;
         nb ^= 1;
     }
-    hipLaunchKernelGGL(k_gauss_threshold, dim3(grid_for(nvox)), dim3(256), 0, s, prob_dev, cur, nvox, (float)threshold, mask_dev, smoothed_dev);
-    return hipGetLastError() == hipSuccess ? SD_OK : sd_fail_msg(SD_ERR_HIP, "sd_gaussian_threshold: launch failed");
+    hipLaunchKernelGGL(k_gauss_threshold, dim3(grid_for(nvox, 8192)), dim3(256), 0, s, prob_dev, cur, nvox, (float)threshold, mask_dev, smoothed_dev);
+    return launch_status("sd_gaussian_threshold: launch failed");
 }
 
 #ifdef SD_WS_TIMING

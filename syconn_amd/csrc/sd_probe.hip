@@ -4,11 +4,9 @@
 // No memory traffic, no LDS: 4 independent accumulators per wave, v_mfma_f32_32x32x16_bf16 back to back, on constant or on
 // pseudo-random operands.
 #include "../../include/syconn_dense.h"
-#include <hip/hip_runtime.h>
+#include "sd_host_util.h"
 #include <algorithm>
 #include <vector>
-
-extern int sd_fail_msg(int code, const char* msg);
 
 namespace {
 typedef __attribute__((ext_vector_type(8))) __bf16 v8bf;

@@ -15,8 +15,6 @@
 #include "../../include/syconn_dense.h"
 #include "sd_sortseg.h"
 
-extern int sd_fail_msg(int code, const char* msg);      // sd_api.hip: sets sd_last_error()
-
 namespace {
 
 // view of an object table as sd_segstats.hip lays it out: keys | first | size | bbmin[3][cap] | bbmax[3][cap]
@@ -111,20 +109,12 @@ __global__ __launch_bounds__(256) void k_reduce_pairs(const u64* ssub, const u64
     }
 }
 
-// carve the caller's scratch: [u64 n | u64 n | u64 n | u32 n x 4 | rocPRIM]
-struct Scratch { u64 *k0, *k1, *k2; u32 *i0, *i1, *head, *seg; void* prim; size_t prim_n; };
-size_t scratch_bytes(size_t n) { return 3 * up256(n * 8) + 4 * up256(n * 4) + prim_bytes(n); }
-Scratch carve(void* base, size_t n) {
-    Scratch s; char* p = reinterpret_cast<char*>(base);
-    s.k0 = reinterpret_cast<u64*>(p); p += up256(n * 8);
-    s.k1 = reinterpret_cast<u64*>(p); p += up256(n * 8);
-    s.k2 = reinterpret_cast<u64*>(p); p += up256(n * 8);
-    s.i0 = reinterpret_cast<u32*>(p); p += up256(n * 4);
-    s.i1 = reinterpret_cast<u32*>(p); p += up256(n * 4);
-    s.head = reinterpret_cast<u32*>(p); p += up256(n * 4);
-    s.seg = reinterpret_cast<u32*>(p); p += up256(n * 4);
-    s.prim = p; s.prim_n = prim_bytes(n);
-    return s;
+struct Scratch { u64 *k0, *k1, *k2; u32 *i0, *i1, *head, *seg; PrimScratch prim; };
+size_t layout(Scratch& w, void* base, size_t n) {
+    ScratchAlloc a(base);
+    a.take_into(n, w.k0, w.k1, w.k2, w.i0, w.i1, w.head, w.seg);
+    w.prim = take_prim(a, n);
+    return a.used;
 }
 
 }  // namespace
@@ -136,10 +126,10 @@ int sd_chunkprops_append(const void* table, size_t cap_obj, int X, int Y, int Z,
                          uint64_t* cursor_dev, void* stream) {
     if (!table || !pow2(cap_obj) || X <= 0 || Y <= 0 || Z <= 0 || !ids_dev || !rc_dev || !bbox_dev || !sizes_dev || !cursor_dev)
         return sd_fail_msg(SD_ERR_INVALID, "sd_chunkprops_append: bad argument");
-    hipLaunchKernelGGL(k_chunkprops_append, dim3(grid_for(cap_obj)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(k_chunkprops_append, dim3(grid_for(cap_obj, 4096)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                        tab_view(table, cap_obj), X, Y, Z, ox, oy, oz, (u64)min_obj_vx, reinterpret_cast<u64*>(ids_dev), rc_dev, bbox_dev,
                        reinterpret_cast<u64*>(sizes_dev), (u64)max_records, reinterpret_cast<u64*>(cursor_dev));
-    return hipGetLastError() == hipSuccess ? SD_OK : sd_fail_msg(SD_ERR_HIP, "sd_chunkprops_append: launch failed");
+    return launch_status("sd_chunkprops_append: launch failed");
 }
 
 int sd_chunkpairs_append(const void* pair_table, size_t cap_pair, const void* sub_table, const void* cell_table, size_t cap_obj,
@@ -149,14 +139,14 @@ int sd_chunkpairs_append(const void* pair_table, size_t cap_pair, const void* su
         !cell_ids_dev || !counts_dev || !cursor_dev)
         return sd_fail_msg(SD_ERR_INVALID, "sd_chunkpairs_append: bad argument");
     const u64* pk = reinterpret_cast<const u64*>(pair_table);
-    hipLaunchKernelGGL(k_chunkpairs_append, dim3(grid_for(cap_pair)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), pk,
+    hipLaunchKernelGGL(k_chunkpairs_append, dim3(grid_for(cap_pair, 4096)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), pk,
                        pk + cap_pair, (u64)cap_pair, tab_view(sub_table, cap_obj), reinterpret_cast<const u64*>(cell_table), X, Y, Z,
                        (u64)min_obj_vx, reinterpret_cast<u64*>(sub_ids_dev), reinterpret_cast<u64*>(cell_ids_dev),
                        reinterpret_cast<u64*>(counts_dev), (u64)max_records, reinterpret_cast<u64*>(cursor_dev));
-    return hipGetLastError() == hipSuccess ? SD_OK : sd_fail_msg(SD_ERR_HIP, "sd_chunkpairs_append: launch failed");
+    return launch_status("sd_chunkpairs_append: launch failed");
 }
 
-size_t sd_propmerge_temp_bytes(size_t n_records) { return scratch_bytes(n_records ? n_records : 1); }
+size_t sd_propmerge_temp_bytes(size_t n_records) { Scratch w; return layout(w, nullptr, n_records ? n_records : 1); }
 
 int sd_propmerge_objects(const uint64_t* ids_dev, const uint64_t* sizes_dev, const int32_t* rc_dev, const int32_t* bbox_dev, size_t n,
                          uint64_t* uniq_ids_dev, uint64_t* tot_sizes_dev, int32_t* last_rc_dev, uint32_t* seg_begin_dev,
@@ -166,23 +156,18 @@ int sd_propmerge_objects(const uint64_t* ids_dev, const uint64_t* sizes_dev, con
     if (hipMemsetAsync(n_unique_dev, 0, sizeof(uint64_t), s) != hipSuccess) return sd_fail_msg(SD_ERR_HIP, "memset failed");
     if (n == 0) return SD_OK;
     if (n >= (1ull << 32)) return sd_fail_msg(SD_ERR_INVALID, "sd_propmerge_objects: < 2^32 records per call");
+    Scratch w;
     if (!ids_dev || !sizes_dev || !rc_dev || !bbox_dev || !uniq_ids_dev || !tot_sizes_dev || !last_rc_dev || !seg_begin_dev ||
-        !bbox_sorted_dev || !temp_dev || temp_bytes < scratch_bytes(n))
+        !bbox_sorted_dev || !temp_dev || temp_bytes < layout(w, temp_dev, n))
         return sd_fail_msg(SD_ERR_INVALID, "sd_propmerge_objects: bad argument / scratch smaller than sd_propmerge_temp_bytes(n)");
-    Scratch w = carve(temp_dev, n);
-    const int g = grid_for(n);
-    hipLaunchKernelGGL(k_iota, dim3(g), dim3(256), 0, s, w.i0, (u64)n);
-    size_t pb = w.prim_n;
-    if (rocprim::radix_sort_pairs(w.prim, pb, reinterpret_cast<const u64*>(ids_dev), w.k0, w.i0, w.i1, n, 0, 64, s) != hipSuccess)
-        return sd_fail_msg(SD_ERR_HIP, "sd_propmerge_objects: radix sort failed");
-    hipLaunchKernelGGL(k_heads, dim3(g), dim3(256), 0, s, w.k0, (const u64*)nullptr, w.head, (u64)n);
-    pb = w.prim_n;
-    if (rocprim::inclusive_scan(w.prim, pb, w.head, w.seg, n, rocprim::plus<u32>(), s) != hipSuccess)
-        return sd_fail_msg(SD_ERR_HIP, "sd_propmerge_objects: scan failed");
+    const char* who = "sd_propmerge_objects";
+    const int g = grid_for(n, 4096);
+    if (int rc = sort_by_key(who, w.prim, reinterpret_cast<const u64*>(ids_dev), w.k0, w.i0, w.i1, n, 64, s); rc != SD_OK) return rc;
+    if (int rc = number_segments(who, w.prim, w.k0, nullptr, w.head, w.seg, n, s); rc != SD_OK) return rc;
     hipLaunchKernelGGL(k_reduce_objects, dim3(g), dim3(256), 0, s, w.k0, w.i1, w.head, w.seg, reinterpret_cast<const u64*>(sizes_dev),
                        rc_dev, bbox_dev, (u64)n, reinterpret_cast<u64*>(uniq_ids_dev), reinterpret_cast<u64*>(tot_sizes_dev), last_rc_dev,
                        seg_begin_dev, bbox_sorted_dev, reinterpret_cast<u64*>(n_unique_dev));
-    return hipGetLastError() == hipSuccess ? SD_OK : sd_fail_msg(SD_ERR_HIP, "sd_propmerge_objects: launch failed");
+    return launch_status("sd_propmerge_objects: launch failed");
 }
 
 int sd_propmerge_pairs(const uint64_t* sub_ids_dev, const uint64_t* cell_ids_dev, const uint64_t* counts_dev, size_t n,
@@ -193,31 +178,24 @@ int sd_propmerge_pairs(const uint64_t* sub_ids_dev, const uint64_t* cell_ids_dev
     if (hipMemsetAsync(n_unique_dev, 0, sizeof(uint64_t), s) != hipSuccess) return sd_fail_msg(SD_ERR_HIP, "memset failed");
     if (n == 0) return SD_OK;
     if (n >= (1ull << 32)) return sd_fail_msg(SD_ERR_INVALID, "sd_propmerge_pairs: < 2^32 records per call");
+    Scratch w;
     if (!sub_ids_dev || !cell_ids_dev || !counts_dev || !out_sub_dev || !out_cell_dev || !out_counts_dev || !temp_dev ||
-        temp_bytes < scratch_bytes(n))
+        temp_bytes < layout(w, temp_dev, n))
         return sd_fail_msg(SD_ERR_INVALID, "sd_propmerge_pairs: bad argument / scratch smaller than sd_propmerge_temp_bytes(n)");
-    Scratch w = carve(temp_dev, n);
-    const int g = grid_for(n);
+    const char* who = "sd_propmerge_pairs";
+    const int g = grid_for(n, 4096);
     const u64* sub = reinterpret_cast<const u64*>(sub_ids_dev);
     const u64* cell = reinterpret_cast<const u64*>(cell_ids_dev);
     // lexicographic (subcell id, cell id): stable sort by the minor key first, then by the major key
-    hipLaunchKernelGGL(k_iota, dim3(g), dim3(256), 0, s, w.i0, (u64)n);
-    size_t pb = w.prim_n;
-    if (rocprim::radix_sort_pairs(w.prim, pb, cell, w.k0, w.i0, w.i1, n, 0, 64, s) != hipSuccess)
-        return sd_fail_msg(SD_ERR_HIP, "sd_propmerge_pairs: radix sort failed");
+    if (int rc = sort_by_key(who, w.prim, cell, w.k0, w.i0, w.i1, n, 64, s); rc != SD_OK) return rc;
     hipLaunchKernelGGL(k_gather64, dim3(g), dim3(256), 0, s, sub, w.i1, w.k1, (u64)n);
-    pb = w.prim_n;
-    if (rocprim::radix_sort_pairs(w.prim, pb, w.k1, w.k2, w.i1, w.i0, n, 0, 64, s) != hipSuccess)
-        return sd_fail_msg(SD_ERR_HIP, "sd_propmerge_pairs: radix sort failed");
+    if (int rc = sort_carry(who, w.prim, w.k1, w.k2, w.i1, w.i0, n, 64, s); rc != SD_OK) return rc;
     hipLaunchKernelGGL(k_gather64, dim3(g), dim3(256), 0, s, cell, w.i0, w.k0, (u64)n);       // k2 = sorted subcell ids, k0 = their cell ids
-    hipLaunchKernelGGL(k_heads, dim3(g), dim3(256), 0, s, w.k2, w.k0, w.head, (u64)n);
-    pb = w.prim_n;
-    if (rocprim::inclusive_scan(w.prim, pb, w.head, w.seg, n, rocprim::plus<u32>(), s) != hipSuccess)
-        return sd_fail_msg(SD_ERR_HIP, "sd_propmerge_pairs: scan failed");
+    if (int rc = number_segments(who, w.prim, w.k2, w.k0, w.head, w.seg, n, s); rc != SD_OK) return rc;
     hipLaunchKernelGGL(k_reduce_pairs, dim3(g), dim3(256), 0, s, w.k2, w.k0, w.i0, w.head, w.seg, reinterpret_cast<const u64*>(counts_dev),
                        (u64)n, reinterpret_cast<u64*>(out_sub_dev), reinterpret_cast<u64*>(out_cell_dev),
                        reinterpret_cast<u64*>(out_counts_dev), reinterpret_cast<u64*>(n_unique_dev));
-    return hipGetLastError() == hipSuccess ? SD_OK : sd_fail_msg(SD_ERR_HIP, "sd_propmerge_pairs: launch failed");
+    return launch_status("sd_propmerge_pairs: launch failed");
 }
 
 }  // extern "C"

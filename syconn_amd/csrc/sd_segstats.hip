@@ -15,8 +15,6 @@
 #include <string>
 #include "sd_hash.h"
 
-extern int sd_fail_msg(int code, const char* msg);      // sd_api.hip: sets sd_last_error()
-
 namespace {
 
 // Object table of `cap` slots (power of two), structure of arrays in one buffer:
@@ -531,7 +529,7 @@ int sd_segstats_scan(const void* cell_dev, const void* const* sub_devs, int n_su
         hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, s, p, lcap);
     };
     if (dtype == SD_U64) launch(SegTag<uint64_t>{}); else launch(SegTag<uint32_t>{});
-    return hipGetLastError() == hipSuccess ? SD_OK : sd_fail_msg(SD_ERR_HIP, "sd_segstats_scan: launch failed");
+    return launch_status("sd_segstats_scan: launch failed");
 }
 
 int sd_labels_make_unique(const int32_t* labels_dev, size_t n, uint64_t offset, uint64_t* out_dev, void* stream) {
@@ -539,7 +537,7 @@ int sd_labels_make_unique(const int32_t* labels_dev, size_t n, uint64_t offset, 
     if (n == 0) return SD_OK;
     hipLaunchKernelGGL(k_labels_offset, dim3(grid_for(n)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), labels_dev, (u64)n,
                        (u64)offset, reinterpret_cast<u64*>(out_dev));
-    return hipGetLastError() == hipSuccess ? SD_OK : sd_fail_msg(SD_ERR_HIP, "sd_labels_make_unique: launch failed");
+    return launch_status("sd_labels_make_unique: launch failed");
 }
 
 int sd_labels_box_lut(const uint64_t* src_dev, int X, int Y, int Z, int x0, int y0, int z0, int nx, int ny, int nz,
@@ -554,7 +552,7 @@ int sd_labels_box_lut(const uint64_t* src_dev, int X, int Y, int Z, int x0, int 
     if (status_dev && hipMemsetAsync(status_dev, 0, sizeof(int32_t), s) != hipSuccess) return sd_fail_msg(SD_ERR_HIP, "memset failed");
     hipLaunchKernelGGL(k_labels_box_lut, dim3(grid_for(n)), dim3(256), 0, s, reinterpret_cast<const u64*>(src_dev), Y, Z, x0, y0, z0, nx, ny,
                        nz, reinterpret_cast<const u64*>(lut_dev), (u64)lut_len, reinterpret_cast<u64*>(dst_dev), status_dev);
-    return hipGetLastError() == hipSuccess ? SD_OK : sd_fail_msg(SD_ERR_HIP, "sd_labels_box_lut: launch failed");
+    return launch_status("sd_labels_box_lut: launch failed");
 }
 
 int sd_segstats_compact_objects(const void* table, size_t cap_obj, uint64_t* ids_dev, uint64_t* first_dev, uint64_t* size_dev,
@@ -566,7 +564,7 @@ int sd_segstats_compact_objects(const void* table, size_t cap_obj, uint64_t* ids
     hipLaunchKernelGGL(k_obj_compact, dim3(grid_for(cap_obj)), dim3(256), 0, s, obj_table(const_cast<void*>(table), cap_obj),
                        reinterpret_cast<u64*>(ids_dev), reinterpret_cast<u64*>(first_dev), reinterpret_cast<u64*>(size_dev),
                        bbox_dev, reinterpret_cast<u64*>(count_dev), (u64)max_out);
-    return hipGetLastError() == hipSuccess ? SD_OK : sd_fail_msg(SD_ERR_HIP, "sd_segstats_compact_objects: launch failed");
+    return launch_status("sd_segstats_compact_objects: launch failed");
 }
 
 int sd_segstats_compact_pairs(const void* pair_table, size_t cap_pair, const void* sub_table, const void* cell_table,
@@ -582,7 +580,7 @@ int sd_segstats_compact_pairs(const void* pair_table, size_t cap_pair, const voi
                        reinterpret_cast<const u64*>(sub_table), reinterpret_cast<const u64*>(cell_table),
                        reinterpret_cast<u64*>(sub_ids_dev), reinterpret_cast<u64*>(cell_ids_dev),
                        reinterpret_cast<u64*>(counts_dev), reinterpret_cast<u64*>(count_dev), (u64)max_out);
-    return hipGetLastError() == hipSuccess ? SD_OK : sd_fail_msg(SD_ERR_HIP, "sd_segstats_compact_pairs: launch failed");
+    return launch_status("sd_segstats_compact_pairs: launch failed");
 }
 
 }  // extern "C"

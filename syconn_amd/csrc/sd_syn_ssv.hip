@@ -29,8 +29,6 @@
 #include "sd_sortseg.h"
 #include <cmath>
 
-extern int sd_fail_msg(int code, const char* msg);      // sd_api.hip: sets sd_last_error()
-
 namespace {
 
 struct SsvGeom {
@@ -394,28 +392,27 @@ __global__ __launch_bounds__(256) void k_ssv_stat_gather(const int* __restrict__
     }
 }
 
-// scratch of both entry points, carved from one allocation of sd_syn_ssv_temp_bytes(n):
-//   components  u64 key, skey, cell_key | u32 i0, perm, head, seg, cell_start (n + 1), parent, minflat, flag, fscan | int svox[3n], box[6n]
-//   statistics  u64 key, skey, d2bits, best, sums[3n] | u32 i0, sflat, headp, pscan, keep, kscan
-struct SsvScratch {
-    u64 *key, *skey, *k3, *k4, *sums;
-    u32* u[9];
-    int *svox, *box;
-    void* prim; size_t prim_n;
-};
-size_t ssv_scratch_bytes(size_t n) {
-    return 4 * up256(n * 8) + up256(3 * n * 8) + 9 * up256((n + 1) * 4) + up256(3 * n * 4) + up256(6 * n * 4) + prim_bytes(n);
+// scratch of the two entry points, laid over the same allocation of sd_syn_ssv_temp_bytes(n): sd_syn_ssv_stats writes every array
+// before it reads it, and the staged calls of sd_syn_ssv_components need only their own layout to last from one to the next
+struct SsvCompScratch { u64 *key, *skey, *cell_key; u32 *i0, *perm, *head, *seg, *cell_start, *parent, *minflat, *flag, *fscan; int *svox, *box; PrimScratch prim; };
+size_t layout(SsvCompScratch& w, void* base, size_t n) {
+    ScratchAlloc a(base);
+    a.take_into(n, w.key, w.skey, w.cell_key, w.i0, w.perm, w.head, w.seg);
+    a.take_into(n + 1, w.cell_start);                        // one start per cell and the sentinel
+    a.take_into(n, w.parent, w.minflat, w.flag, w.fscan);
+    a.take_into(3 * n, w.svox);
+    a.take_into(6 * n, w.box);
+    w.prim = take_prim(a, n);
+    return a.used;
 }
-SsvScratch ssv_carve(void* base, size_t n) {
-    SsvScratch s; char* p = reinterpret_cast<char*>(base);
-    u64** q[4] = {&s.key, &s.skey, &s.k3, &s.k4};
-    for (int k = 0; k < 4; ++k) { *q[k] = reinterpret_cast<u64*>(p); p += up256(n * 8); }
-    s.sums = reinterpret_cast<u64*>(p); p += up256(3 * n * 8);
-    for (int k = 0; k < 9; ++k) { s.u[k] = reinterpret_cast<u32*>(p); p += up256((n + 1) * 4); }
-    s.svox = reinterpret_cast<int*>(p); p += up256(3 * n * 4);
-    s.box = reinterpret_cast<int*>(p); p += up256(6 * n * 4);
-    s.prim = p; s.prim_n = prim_bytes(n);
-    return s;
+struct SsvStatScratch { u64 *key, *skey, *d2bits, *best, *sums; u32 *i0, *sflat, *headp, *pscan, *keep, *kscan; PrimScratch prim; };
+size_t layout(SsvStatScratch& w, void* base, size_t n) {
+    ScratchAlloc a(base);
+    a.take_into(n, w.key, w.skey, w.d2bits, w.best);
+    a.take_into(3 * n, w.sums);
+    a.take_into(n, w.i0, w.sflat, w.headp, w.pscan, w.keep, w.kscan);
+    w.prim = take_prim(a, n);
+    return a.used;
 }
 
 bool ssv_geom(const double* scale, double gap, const int* cell, const int* bits, SsvGeom& g) {
@@ -441,7 +438,11 @@ bool ssv_geom(const double* scale, double gap, const int* cell, const int* bits,
 
 extern "C" {
 
-size_t sd_syn_ssv_temp_bytes(size_t n_vox) { return ssv_scratch_bytes(n_vox ? n_vox : 1); }
+size_t sd_syn_ssv_temp_bytes(size_t n_vox) {
+    const size_t n = n_vox ? n_vox : 1;
+    SsvCompScratch c; SsvStatScratch t;
+    return std::max(layout(c, nullptr, n), layout(t, nullptr, n));
+}
 
 int sd_syn_ssv_components(const int32_t* vox_dev, const uint32_t* vox_frag_dev, const uint32_t* frag_group_dev, const int32_t* group_origin_dev,
                           size_t n_vox, size_t n_frag, size_t n_group, const double* scale_host, double gap_nm, const int32_t* cell_host,
@@ -462,43 +463,34 @@ int sd_syn_ssv_components(const int32_t* vox_dev, const uint32_t* vox_frag_dev, 
     while (gbits < 64 && ((u64)(n_group - 1) >> gbits)) ++gbits;
     const int kbits = gbits + g.b[0] + g.b[1] + g.b[2];
     if (kbits > 63) return sd_fail_msg(SD_ERR_INVALID, "sd_syn_ssv_components: group and cell coordinates need more than 63 key bits");
-    if (!temp_dev || temp_bytes < ssv_scratch_bytes(n_vox))
+    if (!temp_dev || temp_bytes < sd_syn_ssv_temp_bytes(n_vox))
         return sd_fail_msg(SD_ERR_INVALID, "sd_syn_ssv_components: scratch smaller than sd_syn_ssv_temp_bytes(n_vox)");
-    SsvScratch w = ssv_carve(temp_dev, n_vox);
-    u64* cell_key = w.k3;
-    u32 *i0 = w.u[0], *perm = w.u[1], *head = w.u[2], *seg = w.u[3], *cell_start = w.u[4], *parent = w.u[5], *minflat = w.u[6], *flag = w.u[7],
-        *fscan = w.u[8];
+    SsvCompScratch w;
+    layout(w, temp_dev, n_vox);
+    const char* who = "sd_syn_ssv_components";
     const u64 n = n_vox;
-    const int gv = grid_for(n);
-    size_t pb;
+    const int gv = grid_for(n, 4096);
     if (stages & 1) {
         hipLaunchKernelGGL(k_ssv_keys, dim3(gv), dim3(256), 0, s, vox_dev, vox_frag_dev, frag_group_dev, group_origin_dev, n, (u64)n_frag,
                            (u64)n_group, g, w.key, counts);
-        hipLaunchKernelGGL(k_iota, dim3(gv), dim3(256), 0, s, i0, n);
-        pb = w.prim_n;
-        if (rocprim::radix_sort_pairs(w.prim, pb, w.key, w.skey, i0, perm, n_vox, 0, kbits > 0 ? kbits : 1, s) != hipSuccess)
-            return sd_fail_msg(SD_ERR_HIP, "sd_syn_ssv_components: radix sort failed");
-        hipLaunchKernelGGL(k_heads, dim3(gv), dim3(256), 0, s, w.skey, (const u64*)nullptr, head, n);
-        pb = w.prim_n;
-        if (rocprim::inclusive_scan(w.prim, pb, head, seg, n_vox, rocprim::plus<u32>(), s) != hipSuccess)
-            return sd_fail_msg(SD_ERR_HIP, "sd_syn_ssv_components: scan failed");
-        hipLaunchKernelGGL(k_ssv_cells, dim3(gv), dim3(256), 0, s, w.skey, head, seg, n, cell_start, cell_key, parent, minflat, w.box, counts);
-        hipLaunchKernelGGL(k_ssv_cell_boxes, dim3(gv), dim3(256), 0, s, vox_dev, perm, seg, n, w.svox, w.box);
+        if (int rc = sort_by_key(who, w.prim, w.key, w.skey, w.i0, w.perm, n_vox, kbits > 0 ? kbits : 1, s); rc != SD_OK) return rc;
+        if (int rc = number_segments(who, w.prim, w.skey, nullptr, w.head, w.seg, n_vox, s); rc != SD_OK) return rc;
+        hipLaunchKernelGGL(k_ssv_cells, dim3(gv), dim3(256), 0, s, w.skey, w.head, w.seg, n, w.cell_start, w.cell_key, w.parent, w.minflat, w.box,
+                           counts);
+        hipLaunchKernelGGL(k_ssv_cell_boxes, dim3(gv), dim3(256), 0, s, vox_dev, w.perm, w.seg, n, w.svox, w.box);
     }
     if (stages & 2) {
-        hipLaunchKernelGGL(k_ssv_link, dim3(grid_for(64 * n)), dim3(256), 0, s, w.svox, cell_start, cell_key, w.box, parent, g, counts);
-        hipLaunchKernelGGL(k_ssv_compress, dim3(gv), dim3(256), 0, s, parent, counts);
+        hipLaunchKernelGGL(k_ssv_link, dim3(grid_for(64 * n, 4096)), dim3(256), 0, s, w.svox, w.cell_start, w.cell_key, w.box, w.parent, g, counts);
+        hipLaunchKernelGGL(k_ssv_compress, dim3(gv), dim3(256), 0, s, w.parent, counts);
     }
     if (stages & 4) {
-        if (hipMemsetAsync(flag, 0, n * sizeof(u32), s) != hipSuccess) return sd_fail_msg(SD_ERR_HIP, "memset failed");
-        hipLaunchKernelGGL(k_ssv_rootmin, dim3(gv), dim3(256), 0, s, parent, cell_start, perm, minflat, counts);
-        hipLaunchKernelGGL(k_ssv_flag, dim3(gv), dim3(256), 0, s, parent, minflat, flag, counts);
-        pb = w.prim_n;
-        if (rocprim::inclusive_scan(w.prim, pb, flag, fscan, n_vox, rocprim::plus<u32>(), s) != hipSuccess)
-            return sd_fail_msg(SD_ERR_HIP, "sd_syn_ssv_components: scan failed");
-        hipLaunchKernelGGL(k_ssv_labels, dim3(gv), dim3(256), 0, s, perm, seg, parent, minflat, fscan, n, labels_dev, counts);
+        if (hipMemsetAsync(w.flag, 0, n * sizeof(u32), s) != hipSuccess) return sd_fail_msg(SD_ERR_HIP, "memset failed");
+        hipLaunchKernelGGL(k_ssv_rootmin, dim3(gv), dim3(256), 0, s, w.parent, w.cell_start, w.perm, w.minflat, counts);
+        hipLaunchKernelGGL(k_ssv_flag, dim3(gv), dim3(256), 0, s, w.parent, w.minflat, w.flag, counts);
+        if (int rc = scan_u32(who, w.prim, w.flag, w.fscan, n_vox, s); rc != SD_OK) return rc;
+        hipLaunchKernelGGL(k_ssv_labels, dim3(gv), dim3(256), 0, s, w.perm, w.seg, w.parent, w.minflat, w.fscan, n, labels_dev, counts);
     }
-    return hipGetLastError() == hipSuccess ? SD_OK : sd_fail_msg(SD_ERR_HIP, "sd_syn_ssv_components: launch failed");
+    return launch_status("sd_syn_ssv_components: launch failed");
 }
 
 int sd_syn_ssv_stats(const int32_t* vox_dev, const uint32_t* vox_frag_dev, const int32_t* labels_dev, size_t n_vox, size_t n_comp,
@@ -520,34 +512,27 @@ int sd_syn_ssv_stats(const int32_t* vox_dev, const uint32_t* vox_frag_dev, const
         if (!(scale_host[a] > 0.0)) return sd_fail_msg(SD_ERR_INVALID, "sd_syn_ssv_stats: bad scale");
         g.s[a] = scale_host[a];
     }
-    if (!temp_dev || temp_bytes < ssv_scratch_bytes(n_vox))
+    if (!temp_dev || temp_bytes < sd_syn_ssv_temp_bytes(n_vox))
         return sd_fail_msg(SD_ERR_INVALID, "sd_syn_ssv_stats: scratch smaller than sd_syn_ssv_temp_bytes(n_vox)");
-    SsvScratch w = ssv_carve(temp_dev, n_vox);
-    u64 *d2bits = w.k3, *best = w.k4;
-    u32 *i0 = w.u[0], *sflat = w.u[1], *headp = w.u[2], *pscan = w.u[3], *keep = w.u[4], *kscan = w.u[5];
+    SsvStatScratch w;
+    layout(w, temp_dev, n_vox);
+    const char* who = "sd_syn_ssv_stats";
     const u64 n = n_vox, K = n_comp;
-    const int gv = grid_for(n);
+    const int gv = grid_for(n, 4096);
     hipLaunchKernelGGL(k_ssv_compkeys, dim3(gv), dim3(256), 0, s, labels_dev, n, K, w.key, counts);
-    hipLaunchKernelGGL(k_iota, dim3(gv), dim3(256), 0, s, i0, n);
-    size_t pb = w.prim_n;
-    if (rocprim::radix_sort_pairs(w.prim, pb, w.key, w.skey, i0, sflat, n_vox, 0, 32, s) != hipSuccess)
-        return sd_fail_msg(SD_ERR_HIP, "sd_syn_ssv_stats: radix sort failed");
-    hipLaunchKernelGGL(k_ssv_stat_init, dim3(grid_for(K)), dim3(256), 0, s, K, bbox_dev, w.sums, best, rep_flat_dev);
-    hipLaunchKernelGGL(k_ssv_stat_heads, dim3(gv), dim3(256), 0, s, w.skey, sflat, vox_frag_dev, n, headp, comp_begin_dev);
-    pb = w.prim_n;
-    if (rocprim::inclusive_scan(w.prim, pb, headp, pscan, n_vox, rocprim::plus<u32>(), s) != hipSuccess)
-        return sd_fail_msg(SD_ERR_HIP, "sd_syn_ssv_stats: scan failed");
-    hipLaunchKernelGGL(k_ssv_stat_pairs, dim3(gv), dim3(256), 0, s, w.skey, sflat, vox_frag_dev, headp, pscan, n, pair_comp_dev, pair_frag_dev,
-                       pair_begin_dev, counts);
-    hipLaunchKernelGGL(k_ssv_stat_reduce, dim3(gv), dim3(256), 0, s, vox_dev, w.skey, sflat, n, bbox_dev, w.sums);
-    hipLaunchKernelGGL(k_ssv_stat_dist, dim3(gv), dim3(256), 0, s, vox_dev, w.skey, sflat, comp_begin_dev, w.sums, n, g, d2bits, best);
-    hipLaunchKernelGGL(k_ssv_stat_rep, dim3(gv), dim3(256), 0, s, w.skey, sflat, d2bits, best, n, rep_flat_dev);
-    hipLaunchKernelGGL(k_ssv_stat_keep, dim3(gv), dim3(256), 0, s, w.skey, comp_begin_dev, n, (u64)min_obj_vx, keep);
-    pb = w.prim_n;
-    if (rocprim::inclusive_scan(w.prim, pb, keep, kscan, n_vox, rocprim::plus<u32>(), s) != hipSuccess)
-        return sd_fail_msg(SD_ERR_HIP, "sd_syn_ssv_stats: scan failed");
-    hipLaunchKernelGGL(k_ssv_stat_gather, dim3(gv), dim3(256), 0, s, vox_dev, sflat, keep, kscan, n, vox_out_dev, counts);
-    return hipGetLastError() == hipSuccess ? SD_OK : sd_fail_msg(SD_ERR_HIP, "sd_syn_ssv_stats: launch failed");
+    if (int rc = sort_by_key(who, w.prim, w.key, w.skey, w.i0, w.sflat, n_vox, 32, s); rc != SD_OK) return rc;
+    hipLaunchKernelGGL(k_ssv_stat_init, dim3(grid_for(K, 4096)), dim3(256), 0, s, K, bbox_dev, w.sums, w.best, rep_flat_dev);
+    hipLaunchKernelGGL(k_ssv_stat_heads, dim3(gv), dim3(256), 0, s, w.skey, w.sflat, vox_frag_dev, n, w.headp, comp_begin_dev);
+    if (int rc = scan_u32(who, w.prim, w.headp, w.pscan, n_vox, s); rc != SD_OK) return rc;
+    hipLaunchKernelGGL(k_ssv_stat_pairs, dim3(gv), dim3(256), 0, s, w.skey, w.sflat, vox_frag_dev, w.headp, w.pscan, n, pair_comp_dev,
+                       pair_frag_dev, pair_begin_dev, counts);
+    hipLaunchKernelGGL(k_ssv_stat_reduce, dim3(gv), dim3(256), 0, s, vox_dev, w.skey, w.sflat, n, bbox_dev, w.sums);
+    hipLaunchKernelGGL(k_ssv_stat_dist, dim3(gv), dim3(256), 0, s, vox_dev, w.skey, w.sflat, comp_begin_dev, w.sums, n, g, w.d2bits, w.best);
+    hipLaunchKernelGGL(k_ssv_stat_rep, dim3(gv), dim3(256), 0, s, w.skey, w.sflat, w.d2bits, w.best, n, rep_flat_dev);
+    hipLaunchKernelGGL(k_ssv_stat_keep, dim3(gv), dim3(256), 0, s, w.skey, comp_begin_dev, n, (u64)min_obj_vx, w.keep);
+    if (int rc = scan_u32(who, w.prim, w.keep, w.kscan, n_vox, s); rc != SD_OK) return rc;
+    hipLaunchKernelGGL(k_ssv_stat_gather, dim3(gv), dim3(256), 0, s, vox_dev, w.sflat, w.keep, w.kscan, n, vox_out_dev, counts);
+    return launch_status("sd_syn_ssv_stats: launch failed");
 }
 
 }  // extern "C"

@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from .. import _lib as L
+from ..proc.records import OBJECT_FIELDS, Records, segment_offsets
 from .find_object_properties import _cs_device, segstats
 
 # summed box volume (bytes per workspace plane) of one batch of sites; a single larger box gets a batch of its own
@@ -398,16 +399,14 @@ class ContactSiteMerger:
     arrays are sized from them and ``add_chunk`` neither waits for the device nor copies anything to the host."""
 
     def __init__(self, min_obj_vx: dict, device, capacity: int = 1 << 14, vox_capacity: int = 1 << 18):
-        from ..proc.sd_proc import _Records
         self.lib = L.load()
         self.device = torch.device(device)
         self.min_cs, self.min_syn = int(min_obj_vx['cs']), int(min_obj_vx['syn'])
-        obj = [('ids', torch.int64, 1), ('rc', torch.int32, 3), ('bb', torch.int32, 6), ('sizes', torch.int64, 1)]
-        syn = obj + [('asym', torch.int64, 1), ('sym', torch.int64, 1), ('vpos', torch.int64, 1)]
+        syn = OBJECT_FIELDS + [('asym', 'int64', 1), ('sym', 'int64', 1), ('vpos', 'int64', 1)]
         self.cursors = torch.zeros(3, dtype=torch.int64, device=self.device)
-        self.cs = _Records(self.device, obj, capacity, self.cursors[0:1])
-        self.syn = _Records(self.device, syn, capacity, self.cursors[1:2])
-        self.vox = _Records(self.device, [('rows', torch.int32, 3)], vox_capacity, self.cursors[2:3])
+        self.cs = Records(self.device, OBJECT_FIELDS, capacity, self.cursors[0:1])
+        self.syn = Records(self.device, syn, capacity, self.cursors[1:2])
+        self.vox = Records(self.device, [('rows', 'int32', 3)], vox_capacity, self.cursors[2:3])
         self.n_cs = self.n_vox = 0          # appended so far (the syn records are at most n_cs)
         self.n_chunks = 0
         self.n_cs_all = self.n_syn_all = 0  # ids before the size filter (set by finish: the reference's log line counts these)
@@ -460,14 +459,12 @@ class ContactSiteMerger:
 
         def table(out, u, b):
             ids, tot, rc, ubox, beg, boxes = out
-            begin = np.concatenate((beg[:u].cpu().numpy().view(np.uint32).astype(np.int64), [b]))
             return [ids[:u].cpu().numpy().view(np.uint64), tot[:u].cpu().numpy(), rc[:u].cpu().numpy(),
-                    ubox[:u].cpu().numpy().reshape(u, 2, 3), boxes[:b].cpu().numpy().reshape(b, 2, 3), begin]
+                    ubox[:u].cpu().numpy().reshape(u, 2, 3), boxes[:b].cpu().numpy().reshape(b, 2, 3), segment_offsets(beg, u, b)]
         cs_t = CsTable(*table(c_out, u_cs, b_cs))
         asym, sym, cs_size, vbeg, vout = s_more
-        vox_begin = np.concatenate((vbeg[:u_syn].cpu().numpy().view(np.uint32).astype(np.int64), [v_syn]))
         syn_t = SynTable(*table(s_out, u_syn, b_syn), asym[:u_syn].cpu().numpy(), sym[:u_syn].cpu().numpy(), cs_size[:u_syn].cpu().numpy(),
-                         vout[:v_syn].cpu().numpy().view(np.uint32), vox_begin)
+                         vout[:v_syn].cpu().numpy().view(np.uint32), segment_offsets(vbeg, u_syn, v_syn))
         return cs_t, syn_t
 
 

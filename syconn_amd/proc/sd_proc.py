@@ -25,6 +25,7 @@ from typing import Callable, Dict, List, Optional, Sequence
 import numpy as np
 
 from ..handler.basics import kd_factory
+from .records import OBJECT_FIELDS, Records, segment_offsets
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -98,37 +99,6 @@ class _TableOverflow(Exception):
         self.objects, self.pairs = objects, pairs
 
 
-class _Records:
-    """Growable device arrays appended to at a device-side cursor.  ``fields`` = [(name, dtype, inner width)]; `cursor`: a 1-element
-    view into the merger's counter tensor."""
-
-    def __init__(self, device, fields, capacity: int, cursor):
-        import torch
-        self.torch, self.device, self.fields = torch, device, fields
-        self.capacity = int(capacity)
-        self.cursor = cursor
-        self.arrays = {n: self._new(dt, w, self.capacity) for n, dt, w in fields}
-
-    def _new(self, dtype, width, n):
-        return self.torch.empty((n, width) if width > 1 else (n,), dtype=dtype, device=self.device)
-
-    def ptrs(self):
-        return [self.arrays[n].data_ptr() for n, _, _ in self.fields]
-
-    def room_for(self, stored: int, n_more: int):
-        """`stored` records are known to be in the arrays; make sure `n_more` further ones fit."""
-        need = int(stored) + int(n_more)
-        if need <= self.capacity:
-            return
-        cap = max(need, 2 * self.capacity)
-        for n, dt, w in self.fields:
-            grown = self._new(dt, w, cap)
-            keep = min(int(stored) + int(n_more), self.capacity)      # (everything that may have been written so far)
-            grown[:keep] = self.arrays[n][:keep]
-            self.arrays[n] = grown
-        self.capacity = cap
-
-
 class ChunkMerger:
     """Accumulates the per-chunk tables of one dataset pass on the device and merges them at the end.
 
@@ -145,14 +115,13 @@ class ChunkMerger:
         self.device = torch.device(device)
         self.names = list(names)
         self.min_vx = {k: int(min_obj_vx.get(k, 1)) for k in ['sv'] + self.names}
-        obj = [('ids', torch.int64, 1), ('rc', torch.int32, 3), ('bb', torch.int32, 6), ('sizes', torch.int64, 1)]
-        pair = [('sub', torch.int64, 1), ('cell', torch.int64, 1), ('cnt', torch.int64, 1)]
+        obj, pair = OBJECT_FIELDS, [('sub', 'int64', 1), ('cell', 'int64', 1), ('cnt', 'int64', 1)]
         n = len(self.names)
         self.counters = torch.zeros(1 + 2 * n, dtype=torch.int64, device=self.device)          # cursors: cell, subs, pairs
         self.status = torch.zeros((max(int(n_chunks), 1), 2), dtype=torch.int32, device=self.device)      # overflow flags of every chunk's scan
-        self.cell = _Records(self.device, obj, capacity, self.counters[0:1])
-        self.sub = [_Records(self.device, obj, capacity, self.counters[1 + i:2 + i]) for i in range(n)]
-        self.pairs = [_Records(self.device, pair, capacity, self.counters[1 + n + i:2 + n + i]) for i in range(n)]
+        self.cell = Records(self.device, obj, capacity, self.counters[0:1])
+        self.sub = [Records(self.device, obj, capacity, self.counters[1 + i:2 + i]) for i in range(n)]
+        self.pairs = [Records(self.device, pair, capacity, self.counters[1 + n + i:2 + n + i]) for i in range(n)]
         self.n_chunks = 0
         self._side = torch.cuda.Stream(device=self.device)
         ring = self.LAG + 1
@@ -229,7 +198,7 @@ class ChunkMerger:
             self._tmp = self.torch.empty(need, dtype=self.torch.uint8, device=self.device)
         return self._tmp
 
-    def _merge_objects(self, rec: _Records, n: int) -> PropTable:
+    def _merge_objects(self, rec: Records, n: int) -> PropTable:
         torch, lib = self.torch, self.lib
         assert n <= rec.capacity, 'record arrays overran (internal error: capacity bound)'
         if n == 0:
@@ -248,11 +217,10 @@ class ChunkMerger:
                                               uniq.data_ptr(), tot.data_ptr(), rc.data_ptr(), beg.data_ptr(), bbs.data_ptr(),
                                               cnt.data_ptr(), tmp.data_ptr(), tmp.numel(), stream), 'sd_propmerge_objects')
         u = int(cnt.item())
-        begin = np.concatenate((beg[:u].cpu().numpy().view(np.uint32).astype(np.int64), [n]))
         return PropTable(uniq[:u].cpu().numpy().view(np.uint64), tot[:u].cpu().numpy(), rc[:u].cpu().numpy().astype(np.int64),
-                         bbs.cpu().numpy().astype(np.int64).reshape(n, 2, 3), begin)
+                         bbs.cpu().numpy().astype(np.int64).reshape(n, 2, 3), segment_offsets(beg, u, n))
 
-    def _merge_pairs(self, rec: _Records, n: int) -> MapTable:
+    def _merge_pairs(self, rec: Records, n: int) -> MapTable:
         torch, lib = self.torch, self.lib
         assert n <= rec.capacity, 'record arrays overran (internal error: capacity bound)'
         if n == 0:

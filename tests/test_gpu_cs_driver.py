@@ -35,7 +35,8 @@ def g18():
 # ---- the C ABI, driven directly ----------------------------------------------------------------------------------------------------
 def abi_merge(gpu, chunks, min_cs, min_syn, cap_cs=None, cap_syn=None, cap_vox=None, pad=0):
     """Append `chunks` = [(rec int64 (n, 24), vox int64 (v, 3), origin)] and merge once.  Record arrays hold cap_* records (default:
-    what is needed) followed by `pad` guard records filled with -1.  -> dict of numpy arrays (merged columns, cursors, guards)."""
+    what is needed) followed by `pad` guard records filled with -1; the scratch of the merges is followed by a guard band of its own
+    that must be intact after either merge.  -> dict of numpy arrays (merged columns, cursors, guards)."""
     import torch
     from syconn_amd import _lib as L
     lib = L.load()
@@ -66,7 +67,10 @@ def abi_merge(gpu, chunks, min_cs, min_syn, cap_cs=None, cap_syn=None, cap_vox=N
     if cur[0] > cap_cs or cur[1] > cap_syn or cur[2] > cap_vox:
         return out
     n_cs, n_syn, n_vox = (int(x) for x in cur)
-    tmp = torch.empty(lib.sd_cs_merge_temp_bytes(max(n_cs, n_syn, 1)), dtype=torch.uint8, device=gpu)
+    need = lib.sd_cs_merge_temp_bytes(max(n_cs, n_syn, 1))
+    guarded = torch.empty(need + 4096, dtype=torch.uint8, device=gpu)
+    guarded[need:] = 0xA5
+    tmp = guarded[:need]                                        # the merges are told `need` bytes and may touch no more
     new = lambda n, w, dt: torch.full((max(n, 1), w) if w > 1 else (max(n, 1),), -1, dtype=dt, device=gpu)
     common = lambda n: [new(n, 1, i64), new(n, 1, i64), new(n, 3, i32), new(n, 6, i32), new(n, 1, i32), new(n, 6, i32)]
     c_out, c_cnt = common(n_cs), torch.full((4,), -1, dtype=i64, device=gpu)
@@ -74,6 +78,7 @@ def abi_merge(gpu, chunks, min_cs, min_syn, cap_cs=None, cap_syn=None, cap_vox=N
                                     *[t.data_ptr() for t in c_out], c_cnt.data_ptr(), tmp.data_ptr(), tmp.numel(), None),
             'sd_cs_merge_objects')
     u_cs, b_cs, _, all_cs = (int(x) for x in c_cnt.cpu().numpy())
+    assert bool((guarded[need:] == 0xA5).all()), 'sd_cs_merge_objects wrote behind sd_cs_merge_temp_bytes(n)'
     s_out, s_cnt = common(n_syn), torch.full((4,), -1, dtype=i64, device=gpu)
     s_more = [new(n_syn, 1, i64), new(n_syn, 1, i64), new(n_syn, 1, i64), new(n_syn, 1, i32), new(n_vox, 3, i32)]
     L.check(lib.sd_cs_merge_synapses(syn[0].data_ptr(), syn[3].data_ptr(), syn[1].data_ptr(), syn[2].data_ptr(), syn[4].data_ptr(),
@@ -81,6 +86,7 @@ def abi_merge(gpu, chunks, min_cs, min_syn, cap_cs=None, cap_syn=None, cap_vox=N
                                      c_out[1].data_ptr(), u_cs, min_syn, *[t.data_ptr() for t in s_out + s_more], s_cnt.data_ptr(),
                                      tmp.data_ptr(), tmp.numel(), None), 'sd_cs_merge_synapses')
     u_syn, b_syn, v_syn, all_syn = (int(x) for x in s_cnt.cpu().numpy())
+    assert bool((guarded[need:] == 0xA5).all()), 'sd_cs_merge_synapses wrote behind sd_cs_merge_temp_bytes(n)'
     for name, o, u, b in (('cs', c_out, u_cs, b_cs), ('syn', s_out, u_syn, b_syn)):
         h = [t.cpu().numpy() for t in o]
         out[f'{name}_ids'], out[f'{name}_size'], out[f'{name}_rep_coord'] = h[0][:u].view(np.uint64), h[1][:u], h[2][:u]
@@ -225,6 +231,18 @@ def synth_chunk(rng, ids, origin, max_syn=2, p_syn=0.6):
     rec[:, 23] = np.cumsum(ns) - ns
     vox = rng.integers(0, 2 ** 20, (int(ns.sum()), 3)) + np.asarray(origin)
     return rec, vox.astype(np.int64), np.asarray(origin, np.int64)
+
+
+def test_record_counts_at_a_scratch_boundary(gpu):
+    """33 + 31 + 1 = 65 cs records of which 64 carry syn voxels: 4 (n + 1) bytes of a u32 scratch array cross a 256-byte boundary
+    in the cs merge and 4 n bytes end on one in the synapse merge (``abi_merge`` checks the guard band behind the scratch)."""
+    rng = np.random.default_rng(40)
+    ids = rng.permutation(np.arange(1, 60, dtype=np.uint64) * np.uint64(2 ** 58 + 3))
+    chunks = [synth_chunk(rng, ids[:33], (0, 0, 0), p_syn=1.0), synth_chunk(rng, ids[20:51], (64, 0, 0), p_syn=1.0),
+              synth_chunk(rng, ids[58:], (0, 64, 0), p_syn=0.0)]
+    got, want = abi_merge(gpu, chunks, 20, 2), np_merge(chunks, 20, 2)
+    assert got['cursors'].tolist()[:2] == [65, 64] and 0 < len(want['syn_ids']) < want['n_ids'][1]
+    same_columns(got, want)
 
 
 def test_more_than_one_grid_stride(gpu):

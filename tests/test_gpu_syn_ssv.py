@@ -107,6 +107,19 @@ def random_groups(rng, n_groups, extent, max_frags=8, coord0=(0, 0, 0)):
     return groups
 
 
+def trim_to(groups, n_vox):
+    """The same groups with every fragment cut to its first voxels in stored order (at least one) so that `n_vox` are left in all."""
+    lens = np.array([len(f[1]) for _, fr in groups for f in fr])
+    keep = np.maximum(1, lens * n_vox // lens.sum())
+    i = 0
+    while keep.sum() < n_vox:
+        keep[i % len(keep)] += keep[i % len(keep)] < lens[i % len(keep)]
+        i += 1
+    assert keep.sum() == n_vox
+    it = iter(keep.tolist())
+    return [(k, [(f[0], f[1][:next(it)], f[2], f[3]) for f in fr]) for k, fr in groups]
+
+
 def table_and_mapping(groups):
     """Every fragment of group g is the pair of supervoxels (2 g + 2, 10^6 + 1000 g + f) -> cells (2 g + 2, 2 g + 3)."""
     frags = [f for _, fr in groups for f in fr]
@@ -118,19 +131,27 @@ def table_and_mapping(groups):
     return S.Table([f[0] for f in frags], [f[1] for f in frags], [f[2] for f in frags], [f[3] for f in frags]), mapping
 
 
+# seed -> (groups, most fragments per group, min_obj_vx, voxels in all) of the sets that are not 30 groups of up to 8 whole fragments
+SMALL = {6: (4, 3, 3, 64)}
+
+
 @pytest.mark.parametrize('seed, scale, gap, extent, coord0', [
     (1, (10, 10, 20), 250, (60, 60, 30), (0, 0, 0)),
     (2, (9, 9, 20), 250, (70, 70, 30), (5, 7, 11)),
     (3, (4, 4, 40), 120.5, (90, 90, 8), (100, 0, 3)),
     (4, (10, 10, 10), 20.5, (12, 12, 12), (0, 0, 0)),           # just above the two-voxel bound: cells of 2 x 2 x 2 voxels
     (5, (10, 10, 20), 1000, (200, 200, 100), (0, 0, 0)),
+    (6, (10, 10, 10), 20.5, (6, 6, 6), (0, 0, 0)),              # SMALL: 64 voxels, the n + 1 cell starts cross 256 bytes of scratch
 ])
 def test_random_groups_against_restatement(gpu, seed, scale, gap, extent, coord0):
-    from syconn_amd.extraction.cs_processing_steps import combine_and_split_syn, connected_cluster
+    import torch
+    from syconn_amd.extraction.cs_processing_steps import _Agglomerator, combine_and_split_syn, connected_cluster
+    n_groups, max_frags, min_vx, n_vox = SMALL.get(seed, (30, 8, 40, None))
     rng = np.random.default_rng(seed)
-    groups = random_groups(rng, 30, extent, coord0=coord0)
+    groups = random_groups(rng, n_groups, extent, max_frags=max_frags, coord0=coord0)
+    if n_vox:
+        groups = trim_to(groups, n_vox)
     table, mapping = table_and_mapping(groups)
-    min_vx = 40
     want, labels = S.combine(groups, scale, gap, min_vx, 0.225)
     assert sum(int(lab.max()) + 1 for lab in labels) > len(groups) + 5 and len(want) > 5       # splits and merges both happen
     got, info = combine_and_split_syn(table, mapping, scaling=scale, cs_gap_nm=gap, min_obj_vx=min_vx, sym_thresh=0.225, device=gpu,
@@ -141,9 +162,27 @@ def test_random_groups_against_restatement(gpu, seed, scale, gap, extent, coord0
     fb = got.frag_begin.tolist()
     for i, r in enumerate(want):
         assert got.frag_ids[fb[i]:fb[i + 1]].tolist() == r['frag_ids'] and got.frag_counts[fb[i]:fb[i + 1]].tolist() == r['frag_counts']
-    for g in (0, 7, 29):                                        # single groups, shifted to negative coordinates
+    for g in sorted({0, 7 % n_groups, n_groups - 1}):           # single groups, shifted to negative coordinates
         lists = [f[1].astype(np.int64) - 5000 for f in groups[g][1]]
         assert np.array_equal(connected_cluster(lists, gap, scale, device=gpu), labels[g]), (seed, g)
+    # the launches once more over a scratch with a guard band behind it: both entry points are told sd_syn_ssv_temp_bytes(n) bytes
+    frags = [f[1] for _, fr in groups for f in fr]
+    agg = _Agglomerator(np.concatenate(frags), np.repeat(np.arange(len(frags)), [len(v) for v in frags]),
+                        np.repeat(np.arange(n_groups), [len(fr) for _, fr in groups]), n_groups, scale, gap, gpu)
+    assert n_vox in (None, agg.n)
+    need = agg.tmp.numel()
+    guarded = torch.empty(need + 4096, dtype=torch.uint8, device=gpu)
+    guarded[need:] = 0xA5
+    agg.tmp = guarded[:need]
+    agg.components()
+    agg.read_counts()
+    assert bool((guarded[need:] == 0xA5).all()), 'sd_syn_ssv_components wrote behind sd_syn_ssv_temp_bytes(n)'
+    first = np.cumsum([0] + [int(lab.max()) + 1 for lab in labels])
+    flat = np.concatenate([lab + o for lab, o in zip(labels, first)])
+    assert np.array_equal(agg.labels(), flat)
+    st = agg.stats(min_vx)
+    assert bool((guarded[need:] == 0xA5).all()), 'sd_syn_ssv_stats wrote behind sd_syn_ssv_temp_bytes(n)'
+    assert np.array_equal(st['comp_sizes'], np.bincount(flat)) and len(st['voxels']) == sum(len(r['voxels']) for r in want)
 
 
 def test_refusals_and_empty(gpu):

@@ -109,11 +109,14 @@ def test_map_subcell_extract_props_over_knossos_datasets(gpu, name, tmp_path):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize('n,n_ids,seed', [(1, 1, 0), (1000, 37, 1), (200000, 5000, 2), (70000, 70000, 3), (3000000, 150000, 4)])
+@pytest.mark.parametrize('n,n_ids,seed', [(1, 1, 0), (1000, 37, 1), (200000, 5000, 2), (70000, 70000, 3), (3000000, 150000, 4)] +
+                         [(n, max(1, n // 3), 5 + i) for i, n in enumerate((32, 33, 63, 64, 65))])
 def test_propmerge_kernels_against_numpy(gpu, n, n_ids, seed):
     """sd_propmerge_objects / sd_propmerge_pairs on random records: stable order inside an id, sums, last representative.  Ids come
     from the whole uint64 range (2^63, 2^63 + 1 and 2^64 - 1 among them); 3,000,000 records are almost three grid strides of every
-    kernel of the merge, with segments of 20 records on average."""
+    kernel of the merge, with segments of 20 records on average.  At 32 / 33 records the u64 scratch arrays (8 n bytes) and at
+    63 / 64 / 65 the u32 ones (4 n bytes) cross a 256-byte boundary of the scratch layout.  The scratch is followed by a guard band
+    that both merges must leave alone: they are told sd_propmerge_temp_bytes(n) and may touch no more."""
     import torch
     from syconn_amd import _lib as L
     lib = L.load()
@@ -137,11 +140,13 @@ def test_propmerge_kernels_against_numpy(gpu, n, n_ids, seed):
     lrc, beg = torch.empty((n, 3), dtype=torch.int32, device=gpu), torch.empty(n, dtype=torch.int32, device=gpu)
     bbs, cnt = torch.empty((n, 6), dtype=torch.int32, device=gpu), torch.zeros(1, dtype=torch.int64, device=gpu)
     tb = lib.sd_propmerge_temp_bytes(n)
-    tmp = torch.empty(tb, dtype=torch.uint8, device=gpu)
+    tmp = torch.empty(tb + 4096, dtype=torch.uint8, device=gpu)
+    tmp[tb:] = 0xA5
     st = torch.cuda.current_stream().cuda_stream
     L.check(lib.sd_propmerge_objects(d_ids.data_ptr(), d_sz.data_ptr(), d_rc.data_ptr(), d_bb.data_ptr(), n, uniq.data_ptr(), tot.data_ptr(),
                                      lrc.data_ptr(), beg.data_ptr(), bbs.data_ptr(), cnt.data_ptr(), tmp.data_ptr(), tb, st))
     u = int(cnt.item())
+    assert bool((tmp[tb:] == 0xA5).all()), 'sd_propmerge_objects wrote behind sd_propmerge_temp_bytes(n)'
     order = np.argsort(ids, kind='stable')
     sid = ids[order]
     heads = np.flatnonzero(np.concatenate(([True], sid[1:] != sid[:-1])))
@@ -159,6 +164,7 @@ def test_propmerge_kernels_against_numpy(gpu, n, n_ids, seed):
     L.check(lib.sd_propmerge_pairs(d_ids.data_ptr(), d_c.data_ptr(), d_sz.data_ptr(), n, o_s.data_ptr(), o_c.data_ptr(), o_n.data_ptr(),
                                    cnt.data_ptr(), tmp.data_ptr(), tb, st))
     u = int(cnt.item())
+    assert bool((tmp[tb:] == 0xA5).all()), 'sd_propmerge_pairs wrote behind sd_propmerge_temp_bytes(n)'
     order = np.lexsort((cells, ids))
     a, b = ids[order], cells[order]
     heads = np.flatnonzero(np.concatenate(([True], (a[1:] != a[:-1]) | (b[1:] != b[:-1]))))
