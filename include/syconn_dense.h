@@ -503,6 +503,45 @@ int sd_syn_ssv_stats(const int32_t* vox_dev, const uint32_t* vox_frag_dev, const
                      uint32_t* pair_comp_dev, uint32_t* pair_frag_dev, uint32_t* pair_begin_dev, uint32_t* vox_out_dev, uint64_t* counts_dev,
                      void* temp_dev, size_t temp_bytes, void* stream);
 
+/* Organelles of the partner cells mapped to the cell-level synapses: cps.map_objects_from_synssv_partners of the reference
+ * (extraction/cs_processing_steps.py:811-1093), one organelle type per call.  A side is (synapse row i, partner slot p) = 2 i + p.
+ *   sd_synssv_map_pairs  replaces :955-965 (three cKDTrees per cell, query_ball_tree): side_cell_dev[n_sides] = the cell of every side
+ *                        (neuron_partners row-major; 0 = none), syn_rep_dev int32[n_sides / 2][3]; the organelles that have a cell,
+ *                        sorted by cell: org_cell_dev[n_org] ascending, org_row_dev[n_org] = the row that is reported for each,
+ *                        org_rep_dev int32[n_org][3].  An organelle is a candidate of a side of its cell when the float64 distance
+ *                        of rep * scale is <= max_rep_dist_nm (compared as d^2 <= D^2).  Without pair_obj_dev: side_begin_dev
+ *                        [n_sides + 1] = offsets of the sides in the pair list, counts_dev uint64[8], [0] = pairs.  With pair_obj_dev
+ *                        [pair_cap] (and the side_begin_dev of the first call): the reported rows, side-major, in the order of the
+ *                        cell's run.  Scratch: sd_synssv_map_pairs_temp_bytes(n_sides).
+ *   sd_synssv_map_query  replaces :1032-1045 (one cKDTree per synapse, queried per organelle).  vox_dev uint32[n_vox][3] /
+ *                        vox_begin_dev uint64[n_syn + 1] = the voxel runs, sampled_begin_dev uint64[n_syn + 1] = offsets of the
+ *                        sampled voxels (rows 0, f, 2 f, ... of every run: ceil(len / f) each, n_sampled_vox in all); vert_dev
+ *                        float[n_vert][3] in nm / vert_begin_dev uint64[n_org + 1] over the rows pair_obj_dev names.  stages bit 0:
+ *                        the sampled voxels as float64(voxel) * scale, sorted inside a synapse and cut into tiles of 64 with boxes
+ *                        (kept in the scratch: a later call with bit 1 alone over the same scratch, n_syn, n_sampled_vox and
+ *                        scratch_pairs reuses it); bit 1: per pair pair_len_dev = ceil(vertices / f), pair_close_dev = sampled
+ *                        vertices whose nearest sampled voxel is at d^2 < R^2 (d^2 = ((dx dx) + dy dy) + dz dz in float64, nothing
+ *                        fused), pair_min_d2_dev = bits of the smallest such d^2 (+inf if none).  Pairs are split into work items of
+ *                        SD_SYNSSV_MAP_ITEM sampled vertices; n_items_hint sizes the grid (0: the largest).  counts_dev uint64[8] =
+ *                        pairs, work items, vertices dropped by the synapse's box, tiles skipped, tiles staged, point tests, 0;
+ *                        [7] != 0: an offset or row was out of range (results invalid).
+ *                        Scratch: sd_synssv_map_query_temp_bytes(n_syn, n_sampled_vox, scratch_pairs), scratch_pairs >= n_pairs.
+ * Asynchronous on the stream.  Limits (SD_ERR_INVALID beyond): n_sides, n_org, pairs, n_sampled_vox < 2^31, n_syn < 2^30,
+ * sample_fact >= 1; on the device: < 2^32 sampled vertices per organelle and < 2^32 work items per call (counts_dev[7]). */
+#define SD_SYNSSV_MAP_ITEM 1024
+size_t sd_synssv_map_pairs_temp_bytes(size_t n_sides);
+int sd_synssv_map_pairs(const uint64_t* side_cell_dev, const int32_t* syn_rep_dev, size_t n_sides, const uint64_t* org_cell_dev,
+                        const uint32_t* org_row_dev, const int32_t* org_rep_dev, size_t n_org, const double* scale_host,
+                        double max_rep_dist_nm, uint32_t* side_begin_dev, uint32_t* pair_obj_dev, size_t pair_cap, uint64_t* counts_dev,
+                        void* temp_dev, size_t temp_bytes, void* stream);
+size_t sd_synssv_map_query_temp_bytes(size_t n_syn, size_t n_sampled_vox, size_t n_pairs);
+int sd_synssv_map_query(const uint32_t* vox_dev, const uint64_t* vox_begin_dev, const uint64_t* sampled_begin_dev, size_t n_syn, size_t n_vox,
+                        size_t n_sampled_vox, const float* vert_dev, const uint64_t* vert_begin_dev, size_t n_org, size_t n_vert,
+                        const uint32_t* side_begin_dev, const uint32_t* pair_obj_dev, size_t n_pairs, size_t scratch_pairs, int sample_fact,
+                        const double* scale_host, double max_vert_dist_nm, int stages, size_t n_items_hint, uint32_t* pair_close_dev,
+                        uint32_t* pair_len_dev, uint64_t* pair_min_d2_dev, uint64_t* counts_dev, void* temp_dev, size_t temp_bytes,
+                        void* stream);
+
 /* ---- host-side helpers of the chunk pipeline (no GPU) -----------------------------------------------------------------
  * Multi-threaded strided copy of an (nz, ny, nx)-byte box between two uint8 host arrays whose x-rows are contiguous
  * (strides in bytes), and a multi-threaded memset: what numpy slicing does on one core when the reference cuts a chunk

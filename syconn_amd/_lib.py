@@ -13,6 +13,7 @@ SD_OP_CONV, SD_OP_POOL, SD_OP_UPCONV, SD_OP_GROUPNORM, SD_OP_FINAL = 1, 2, 3, 4,
 SD_MOP_OPENING, SD_MOP_CLOSING, SD_MOP_DILATION, SD_MOP_EROSION = 1, 2, 3, 4
 SD_CS_FIRST, SD_CS_LAST = 1, 2
 SD_CST_COLS = 24
+SD_SYNSSV_MAP_ITEM = 1024
 
 LIB_NAME = 'libsyconn_dense_hip.so'
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), os.environ.get('SD_LIB_NAME', LIB_NAME))
@@ -30,7 +31,8 @@ EXPORTS = ['sd_init', 'sd_device_count', 'sd_model_create', 'sd_model_destroy', 
            'sd_seg_boundaries', 'sd_contact_partners_workspace_bytes', 'sd_contact_partners', 'sd_cs_close_dilate',
            'sd_binary_morphology', 'sd_cs_syntype_table_bytes', 'sd_cs_syntype_scan', 'sd_cs_syntype_compact', 'sd_cs_syntype_records',
            'sd_cs_syntype_voxels', 'sd_syntype_masks', 'sd_cs_merge_append', 'sd_cs_merge_temp_bytes', 'sd_cs_merge_objects',
-           'sd_cs_merge_synapses', 'sd_syn_ssv_temp_bytes', 'sd_syn_ssv_components', 'sd_syn_ssv_stats']
+           'sd_cs_merge_synapses', 'sd_syn_ssv_temp_bytes', 'sd_syn_ssv_components', 'sd_syn_ssv_stats',
+           'sd_synssv_map_pairs_temp_bytes', 'sd_synssv_map_pairs', 'sd_synssv_map_query_temp_bytes', 'sd_synssv_map_query']
 
 
 class OpDesc(C.Structure):
@@ -161,6 +163,14 @@ def load():
     lib.sd_syn_ssv_components.restype = i32
     lib.sd_syn_ssv_stats.argtypes = [vp, vp, vp, sz, sz, C.POINTER(C.c_double), C.c_uint64] + [vp] * 8 + [vp, sz, vp]
     lib.sd_syn_ssv_stats.restype = i32
+    # cs_processing_steps.py:888-1009 (candidate organelles of every synapse side) and :1012-1052 (vertices against synapse voxels)
+    lib.sd_synssv_map_pairs_temp_bytes.argtypes = [sz]; lib.sd_synssv_map_pairs_temp_bytes.restype = sz
+    lib.sd_synssv_map_pairs.argtypes = [vp, vp, sz, vp, vp, vp, sz, C.POINTER(C.c_double), C.c_double, vp, vp, sz, vp, vp, sz, vp]
+    lib.sd_synssv_map_pairs.restype = i32
+    lib.sd_synssv_map_query_temp_bytes.argtypes = [sz, sz, sz]; lib.sd_synssv_map_query_temp_bytes.restype = sz
+    lib.sd_synssv_map_query.argtypes = [vp, vp, vp, sz, sz, sz, vp, vp, sz, sz, vp, vp, sz, sz, i32, C.POINTER(C.c_double), C.c_double, i32,
+                                        sz, vp, vp, vp, vp, vp, sz, vp]
+    lib.sd_synssv_map_query.restype = i32
     _lib = lib
     return lib
 

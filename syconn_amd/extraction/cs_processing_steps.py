@@ -8,6 +8,9 @@ launches (``csrc/sd_syn_ssv.hip``: components, then per-component statistics) an
 arithmetic on a few values per synapse (:458-509).  Where this departs from the reference -- no ``dist_inter_object`` prefilter, a
 lower bound on the gap, all voxels for ``rep_coord``, no meshes, storages or ids -- is written down in DESIGN.md section 7.
 There is no CPU fallback for the device parts.
+
+``map_objects_from_synssv_partners`` (:811-1093), the call after it, maps the mitochondria and vesicle clouds of the two partner cells
+to every ``syn_ssv`` row (``csrc/sd_synssv_map.hip``) and ``synssv_o_features`` (:1404-1431) lays out the classifier's feature rows.
 """
 import ctypes as C
 
@@ -363,3 +366,332 @@ def combine_and_split_syn(syn_table, sv_ids, ssv_ids=None, scaling=None, cs_gap_
     if return_stats:
         return table, dict(counts=counts, cell=agg.cell, n_vox=agg.n, n_groups=len(enc_keys))
     return table
+
+
+# ---- organelles of the partner cells, mapped to the cell-level synapses -----------------------------------------------------------------
+# ``map_objects_from_synssv_partners`` of the reference (extraction/cs_processing_steps.py:811-1093), the call that follows
+# ``combine_and_split_syn`` in ``exec_syns.run_syn_generation``, and the classifier's feature rows (``synssv_o_features``, :1404-1431).
+# A *side* is (synapse row i, partner slot p) = 2 i + p; slot 0 is ``neuron_partners[i, 0]``, the larger cell id.
+class OrganelleTable:
+    """Objects of one organelle type (``mi``, ``vc``, ...), plain numpy: ``ids`` uint64 (m); ``cells`` uint64 (m) = the cell every
+    object is assigned to (the reference's ``ssv_o.mi_ids`` / ``vc_ids`` read the other way round), 0 = none; ``sizes`` int64 (m) in
+    voxels; ``rep_coords`` int32 (m, 3) in voxels; ``vertices`` float32 (W, 3) in nm = the mesh vertices of all objects
+    (``mesh[1].reshape(-1, 3)``), object by object; ``vert_begin`` int64 (m + 1) = their offsets.  Shapes and offsets are checked."""
+
+    def __init__(self, ids, cells, sizes, rep_coords, vertices, vert_begin):
+        self.ids = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        m = len(self.ids)
+        self.cells = np.ascontiguousarray(cells, dtype=np.uint64).reshape(-1)
+        self.sizes = np.ascontiguousarray(sizes, dtype=np.int64).reshape(-1)
+        self.rep_coords = np.ascontiguousarray(rep_coords, dtype=np.int32).reshape(-1, 3)
+        self.vertices = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+        self.vert_begin = np.ascontiguousarray(vert_begin, dtype=np.int64).reshape(-1)
+        if not (len(self.cells) == len(self.sizes) == len(self.rep_coords) == m):
+            raise ValueError(f'OrganelleTable: {m} ids but {len(self.cells)} cells, {len(self.sizes)} sizes, {len(self.rep_coords)} rep_coords')
+        _check_offsets('OrganelleTable: vert_begin', self.vert_begin, m, len(self.vertices))
+
+    def __len__(self):
+        return len(self.ids)
+
+
+def _check_offsets(what, begin, n_rows, n_items):
+    if len(begin) != n_rows + 1 or begin[0] != 0 or begin[-1] != n_items or np.any(np.diff(begin) < 0):
+        raise ValueError(f'{what} must hold {n_rows + 1} ascending offsets from 0 to {n_items}')
+
+
+class PairList:
+    """The (side, organelle) pairs of one organelle type: ``side_begin`` int64 (2 n + 1) offsets of the sides, ``pair_obj`` int64 =
+    organelle row (ascending inside a side), ``pair_close`` int64 = sampled vertices with a sampled synapse voxel strictly inside the
+    radius, ``pair_len`` int64 = sampled vertices, ``pair_min_d2`` float64 = the smallest squared distance below the squared radius
+    (inf if none)."""
+
+    def __init__(self, side_begin, pair_obj, pair_close, pair_len, pair_min_d2):
+        self.side_begin = np.asarray(side_begin, np.int64)
+        self.pair_obj, self.pair_close = np.asarray(pair_obj, np.int64), np.asarray(pair_close, np.int64)
+        self.pair_len, self.pair_min_d2 = np.asarray(pair_len, np.int64), np.asarray(pair_min_d2, np.float64)
+        P = len(self.pair_obj)
+        _check_offsets('PairList: side_begin', self.side_begin, len(self.side_begin) - 1, P)
+        if not (len(self.pair_close) == len(self.pair_len) == len(self.pair_min_d2) == P) or len(self.side_begin) % 2 != 1:
+            raise ValueError('PairList: columns of unequal length')
+
+    @classmethod
+    def empty(cls, n_syn):
+        z = np.zeros(0, np.int64)
+        return cls(np.zeros(2 * n_syn + 1, np.int64), z, z, z, np.zeros(0, np.float64))
+
+
+class SynSsvMapping:
+    """What ``map_objects_from_synssv_partners`` stores per synapse and partner: for every organelle type t ``n_{t}_objs`` and
+    ``n_{t}_vxs`` int32 (n, 2) and ``min_dst_{t}_nm`` float32 (n, 2) (attributes; column p = partner slot p), and ``pairs[t]``, the
+    ``PairList`` they were made from."""
+
+    def __init__(self, n_syn, columns, pairs):
+        self.n_syn, self.types, self.pairs = int(n_syn), tuple(columns), dict(pairs)
+        for t, (n_objs, n_vxs, min_dst) in columns.items():
+            setattr(self, f'n_{t}_objs', n_objs)
+            setattr(self, f'n_{t}_vxs', n_vxs)
+            setattr(self, f'min_dst_{t}_nm', min_dst)
+
+    def __len__(self):
+        return self.n_syn
+
+    def as_dicts(self) -> list:
+        """One dict per synapse with the keys ``_objects_from_cell_to_syn_dict`` (:1085-1090) adds to its attribute dict."""
+        out = [dict() for _ in range(self.n_syn)]
+        for t in self.types:
+            cols = ((f'n_{t}_objs', getattr(self, f'n_{t}_objs')), (f'n_{t}_vxs', getattr(self, f'n_{t}_vxs')),
+                    (f'min_dst_{t}_nm', getattr(self, f'min_dst_{t}_nm')))
+            for i, d in enumerate(out):
+                for p in (0, 1):
+                    for name, col in cols:
+                        d[f'{name}_{p}'] = col[i, p]
+        return out
+
+
+def build_synssv_mapping(n_syn: int, organelles: dict, pairs: dict) -> SynSsvMapping:
+    """The host edge (:1040-1052 and :929-934), numpy only: from the pair list of every type (`pairs`: type -> ``PairList``) and the
+    organelles' sizes and ids to the three columns per type.  Per side, over its pairs in list order: ``close_frac = close / len``,
+    ``n_obj_vxs = np.array([close_frac * size, ...])``, ``n_objects = np.sum(n_obj_vxs > 0)``, ``n_vxs = np.sum(n_obj_vxs)`` stored
+    into int32 (truncated), ``min_dist = sqrt(min d^2)`` if below 1e12 else 1e12, stored into float32.  A pair without vertices and
+    an ``n_vxs`` of 2^31 or more raise ValueError (the reference fails on the first and is undefined on the second)."""
+    columns = {}
+    for t, pl in pairs.items():
+        table = organelles[t]
+        if len(pl.side_begin) != 2 * n_syn + 1:
+            raise ValueError(f'{t}: side_begin holds {len(pl.side_begin)} offsets for {n_syn} synapses')
+        n_objs, n_vxs = np.zeros(2 * n_syn, np.int32), np.zeros(2 * n_syn, np.int32)
+        min_dst = np.full(2 * n_syn, 1e12, np.float32)
+        if len(pl.pair_obj):
+            if pl.pair_obj.min() < 0 or pl.pair_obj.max() >= len(table):
+                raise ValueError(f'{t}: an organelle row of the pair list is outside the table')
+            if np.any(pl.pair_len <= 0):
+                o = int(pl.pair_obj[np.flatnonzero(pl.pair_len <= 0)[0]])
+                raise ValueError(f'{t} object {int(table.ids[o])} (row {o}) is a candidate but has no mesh vertices')
+            close_frac = pl.pair_close / pl.pair_len
+            x = close_frac * table.sizes[pl.pair_obj]
+            m = np.diff(pl.side_begin)
+            sides = np.flatnonzero(m)
+            total = np.zeros(len(sides), np.float64)
+            single = m[sides] == 1                               # the sum of one term is the term
+            total[single] = x[pl.side_begin[sides[single]]]
+            for k in np.flatnonzero(~single).tolist():
+                n_obj_vxs = x[pl.side_begin[sides[k]]:pl.side_begin[sides[k] + 1]]
+                total[k] = np.sum(n_obj_vxs)
+            if np.any(total >= 2.0 ** 31) or np.any(total <= -2.0 ** 31 - 1):
+                s = int(sides[np.flatnonzero((total >= 2.0 ** 31) | (total <= -2.0 ** 31 - 1))[0]])
+                raise ValueError(f'{t}: n_vxs of synapse {s // 2}, partner {s % 2} does not fit int32')
+            n_vxs[sides] = total                                 # float64 into int32: truncated toward zero
+            n_objs[sides] = np.add.reduceat((x > 0).astype(np.int64), pl.side_begin[sides])
+            best = np.minimum.reduceat(pl.pair_min_d2, pl.side_begin[sides])
+            dist = np.sqrt(best)
+            min_dst[sides] = np.where(dist < 1e12, dist, 1e12)
+        columns[t] = (n_objs.reshape(n_syn, 2), n_vxs.reshape(n_syn, 2), min_dst.reshape(n_syn, 2))
+    return SynSsvMapping(n_syn, columns, pairs)
+
+
+def synssv_o_featurenames() -> list:
+    """:1427-1431."""
+    return ['size_vx', 'mesh_area_um2', 'n_mi_objs_neuron1', 'n_mi_vxs_neuron1', 'min_dst_mi_nm_neuron1', 'n_vc_objs_neuron1',
+            'n_vc_vxs_neuron1', 'min_dst_vc_nm_neuron1', 'n_mi_objs_neuron2', 'n_mi_vxs_neuron2', 'min_dst_mi_nm_neuron2',
+            'n_vc_objs_neuron2', 'n_vc_vxs_neuron2', 'min_dst_vc_nm_neuron2']
+
+
+def synssv_o_features(syn_ssv, mapping: SynSsvMapping, mesh_area) -> np.ndarray:
+    """``synssv_o_features`` (:1404-1424) for every row of `syn_ssv`: float64 (n, 14) in the order of ``synssv_o_featurenames``.
+    `mesh_area` (n) is an input, this package builds no meshes.  Needs the types ``mi`` and ``vc``."""
+    missing = [t for t in ('mi', 'vc') if t not in mapping.types]
+    if missing:
+        raise ValueError(f'synssv_o_features needs the organelle types mi and vc, the mapping lacks {missing}')
+    n = len(syn_ssv)
+    area = np.asarray(mesh_area, np.float64).reshape(-1)
+    if len(mapping) != n or len(area) != n:
+        raise ValueError(f'{n} synapses, {len(mapping)} mapped rows, {len(area)} mesh areas')
+    cols = [np.asarray(syn_ssv.sizes, np.float64), area]
+    for p in (0, 1):
+        for t in ('mi', 'vc'):
+            cols += [getattr(mapping, f'n_{t}_objs')[:, p], getattr(mapping, f'n_{t}_vxs')[:, p], getattr(mapping, f'min_dst_{t}_nm')[:, p]]
+    return np.stack([np.asarray(c, np.float64) for c in cols], 1) if n else np.zeros((0, 14), np.float64)
+
+
+MAP_COUNT_NAMES = ('pairs', 'work_items', 'vertices_rejected', 'tiles_skipped', 'tiles_staged', 'point_tests')
+
+
+class _ObjectMapper:
+    """The launches of ``csrc/sd_synssv_map.hip`` over one ``SynSsvTable``: the voxel runs are uploaded once, their sampled, sorted
+    and tiled form (``prepare``) serves every organelle type."""
+
+    def __init__(self, syn_ssv, scale, sample_fact, device=None):
+        import torch
+        from .find_object_properties import _cs_device
+        self.lib, self.dev, self.torch = L.load(), _cs_device(device), torch
+        self.scale, self.f = np.asarray(scale, np.float64), int(sample_fact)
+        self.n = n = len(syn_ssv)
+        partners = np.ascontiguousarray(syn_ssv.neuron_partners, dtype=np.uint64).reshape(n, 2)
+        rep = np.ascontiguousarray(syn_ssv.rep_coords, dtype=np.int32).reshape(n, 3)
+        vox = np.ascontiguousarray(syn_ssv.voxels, dtype=np.uint32).reshape(-1, 3)
+        vb = np.ascontiguousarray(syn_ssv.vox_begin, dtype=np.int64).reshape(-1)
+        _check_offsets('syn_ssv.vox_begin', vb, n, len(vox))
+        svb = np.concatenate(([0], np.cumsum(-(-np.diff(vb) // self.f)))).astype(np.int64)
+        self.n_vox, self.n_sv = len(vox), int(svb[-1])
+        if 2 * n >= 2 ** 31 or self.n_sv >= 2 ** 31:
+            raise ValueError('map_objects_from_synssv_partners: fewer than 2^30 synapses and 2^31 sampled voxels per call')
+        up = lambda a: torch.from_numpy(a).to(self.dev)
+        self.cell_d, self.rep_d = up(partners.view(np.int64).reshape(-1)), up(rep)
+        self.vox_d, self.vb_d, self.svb_d = up(vox.view(np.int32)), up(vb), up(svb)
+        self._scale_c = (C.c_double * 3)(*self.scale.tolist())
+        self.pair_tmp = torch.empty(self.lib.sd_synssv_map_pairs_temp_bytes(2 * n), dtype=torch.uint8, device=self.dev)
+        self.tmp, self.tmp_pairs, self.prepared = None, 0, False
+        self.vox_counts_d = torch.zeros(8, dtype=torch.int64, device=self.dev)
+
+    def _stream(self):
+        return self.torch.cuda.current_stream(self.dev).cuda_stream
+
+    def candidates(self, table: OrganelleTable, max_rep_dist_nm: float, stage: int = 3):
+        """The pair list of one type (both calls of ``sd_synssv_map_pairs``; waits for the count in between).  -> dict."""
+        torch, n = self.torch, self.n
+        keep = np.flatnonzero(table.cells != 0)
+        order = keep[np.argsort(table.cells[keep], kind='stable')]
+        c = dict(table=table, m=len(order), P=0, side_begin=np.zeros(2 * n + 1, np.int64), pair_obj=np.zeros(0, np.int64))
+        if not len(order):
+            return c
+        if len(table) >= 2 ** 31:
+            raise ValueError('map_objects_from_synssv_partners: fewer than 2^31 organelles of one type per call')
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
+        c['cell_d'], c['row_d'] = up(table.cells[order].view(np.int64)), up(order.astype(np.uint32).view(np.int32))
+        c['rep_d'] = up(table.rep_coords[order])
+        c['begin_d'] = torch.empty(2 * n + 1, dtype=torch.int32, device=self.dev)
+        c['counts_d'] = torch.zeros(8, dtype=torch.int64, device=self.dev)
+        c['D'] = float(max_rep_dist_nm)
+        self.pairs_call(c, None)
+        c['P'] = P = int(c['counts_d'][0].item())
+        if P >= 2 ** 31:
+            raise ValueError('map_objects_from_synssv_partners: fewer than 2^31 (side, organelle) pairs per type and call')
+        c['side_begin'] = c['begin_d'].cpu().numpy().view(np.uint32).astype(np.int64)
+        if P:
+            c['obj_d'] = torch.empty(P, dtype=torch.int32, device=self.dev)
+            self.pairs_call(c, c['obj_d'])
+            c['pair_obj'] = c['obj_d'].cpu().numpy().view(np.uint32).astype(np.int64)
+        return c
+
+    def pairs_call(self, c, obj_d):
+        L.check(self.lib.sd_synssv_map_pairs(self.cell_d.data_ptr(), self.rep_d.data_ptr(), 2 * self.n, c['cell_d'].data_ptr(), c['row_d'].data_ptr(),
+                                             c['rep_d'].data_ptr(), c['m'], self._scale_c, c['D'], c['begin_d'].data_ptr(),
+                                             None if obj_d is None else obj_d.data_ptr(), 0 if obj_d is None else obj_d.numel(),
+                                             c['counts_d'].data_ptr(), self.pair_tmp.data_ptr(), self.pair_tmp.numel(), self._stream()),
+                'sd_synssv_map_pairs')
+
+    def reserve(self, n_pairs: int):
+        """Scratch of the query for up to `n_pairs` pairs; a new allocation loses the prepared voxels."""
+        if self.tmp is None or n_pairs > self.tmp_pairs:
+            self.tmp_pairs = int(n_pairs)
+            self.tmp = self.torch.empty(self.lib.sd_synssv_map_query_temp_bytes(self.n, self.n_sv, self.tmp_pairs), dtype=self.torch.uint8,
+                                        device=self.dev)
+            self.prepared = False
+
+    def _query_call(self, stages, R, c=None, out=None, counts_d=None, n_items=0):
+        z = lambda k: c[k].data_ptr() if c is not None else None
+        t = c['table'] if c is not None else None
+        L.check(self.lib.sd_synssv_map_query(self.vox_d.data_ptr(), self.vb_d.data_ptr(), self.svb_d.data_ptr(), self.n, self.n_vox, self.n_sv,
+                                             z('vert_d'), z('vtb_d'), len(t) if t is not None else 0, len(t.vertices) if t is not None else 0,
+                                             z('begin_d'), z('obj_d'), c['P'] if c is not None else 0, self.tmp_pairs, self.f, self._scale_c,
+                                             float(R), int(stages), int(n_items), *(o.data_ptr() if o is not None else None for o in (out or (None,) * 3)),
+                                             counts_d.data_ptr(), self.tmp.data_ptr(), self.tmp.numel(), self._stream()), 'sd_synssv_map_query')
+
+    def prepare(self):
+        """Stage 1: the sampled voxels of all synapses, sorted and tiled, into the scratch (asynchronous)."""
+        if self.tmp is None:
+            self.reserve(1)
+        self._query_call(1, 0.0, counts_d=self.vox_counts_d)
+        self.prepared = True
+
+    def query(self, c, max_vert_dist_nm: float):
+        """Stage 2 for the pair list `c` of ``candidates`` (waits for the device).  -> (``PairList``, counts as a dict)."""
+        torch, P, table = self.torch, c['P'], c['table']
+        if not P:
+            return PairList.empty(self.n), dict.fromkeys(MAP_COUNT_NAMES, 0)
+        n_vert = -(-np.diff(table.vert_begin) // self.f)
+        plen = n_vert[c['pair_obj']]
+        if np.any(plen == 0):
+            o = int(c['pair_obj'][np.flatnonzero(plen == 0)[0]])
+            raise ValueError(f'object {int(table.ids[o])} (row {o}) is a candidate but has no mesh vertices')
+        if int(plen.max()) >= 2 ** 32:
+            raise ValueError('map_objects_from_synssv_partners: fewer than 2^32 sampled vertices per organelle')
+        n_items = int((-(-plen // L.SD_SYNSSV_MAP_ITEM)).sum())
+        if n_items >= 2 ** 32:
+            raise ValueError('map_objects_from_synssv_partners: fewer than 2^32 work items per type and call')
+        self.reserve(P)
+        if not self.prepared:
+            self.prepare()
+        if 'vert_d' not in c:
+            c['vert_d'], c['vtb_d'] = torch.from_numpy(table.vertices).to(self.dev), torch.from_numpy(table.vert_begin).to(self.dev)
+        out = (torch.empty(P, dtype=torch.int32, device=self.dev), torch.empty(P, dtype=torch.int32, device=self.dev),
+               torch.empty(P, dtype=torch.int64, device=self.dev))
+        counts_d = torch.zeros(8, dtype=torch.int64, device=self.dev)
+        self._query_call(2, max_vert_dist_nm, c, out, counts_d, n_items)
+        counts = counts_d.cpu().numpy()
+        if counts[7] or int(self.vox_counts_d.cpu().numpy()[7]):
+            raise RuntimeError('sd_synssv_map_query: an offset or an organelle row was out of range')
+        u = lambda t: t.cpu().numpy().view(np.uint32).astype(np.int64)
+        pl = PairList(c['side_begin'], c['pair_obj'], u(out[0]), u(out[1]), out[2].cpu().numpy().view(np.float64))
+        if not np.array_equal(pl.pair_len, plen) or int(counts[1]) != n_items:
+            raise RuntimeError('sd_synssv_map_query: the sampled vertex counts of the device differ from the host\'s')
+        return pl, dict(zip(MAP_COUNT_NAMES, (int(v) for v in counts[:6])))
+
+
+def map_objects_from_synssv_partners(syn_ssv, organelles: dict, scaling=None, max_vert_dist_nm=None, max_rep_coord_dist_nm=None,
+                                     sample_fact: int = 2, device=None, return_stats: bool = False):
+    """``map_objects_from_synssv_partners`` (:811-886) with its workers ``_map_objects_from_synssv_partners_thread`` (:888-1009),
+    ``_map_objects_from_synssv`` (:1012-1052) and ``_objects_from_cell_to_syn_dict`` (:1055-1093) on the ``SynSsvTable`` that
+    ``combine_and_split_syn`` returns (its ``neuron_partners``, ``rep_coords``, ``voxels`` and ``vox_begin``) and one
+    ``OrganelleTable`` per type (`organelles`: type name -> table).  For every synapse, partner and type: the organelles of the
+    partner cell whose representative coordinate is within `max_rep_coord_dist_nm` of the synapse's are candidates; of every
+    candidate, every `sample_fact`-th mesh vertex is tested against every `sample_fact`-th voxel of the synapse (strictly inside
+    `max_vert_dist_nm`: a dict by type, or a number).  `scaling` falls back to ``config['scaling']``, the distances to
+    ``config['cell_objects']``.  -> ``SynSsvMapping`` (and with `return_stats` a dict with the device's counters per type).
+
+    Not built: the meshes (vertices are an input), the ``cache_syn.pkl`` files, storages, batch jobs and the
+    classifier.  No CPU fallback."""
+    from .. import global_params
+    cfg = global_params.config
+    if scaling is None:
+        scaling = cfg['scaling']
+    cobj = cfg['cell_objects']
+    max_vert_dist_nm = cobj['max_vert_dist_nm'] if max_vert_dist_nm is None else max_vert_dist_nm
+    D = float(cobj['max_rep_coord_dist_nm'] if max_rep_coord_dist_nm is None else max_rep_coord_dist_nm)
+    if isinstance(sample_fact, bool) or int(sample_fact) != sample_fact or int(sample_fact) < 1:
+        raise ValueError(f'sample_fact must be an integer >= 1, got {sample_fact!r}')
+    scale = np.asarray(scaling, np.float32).reshape(-1).astype(np.float64)   # SegmentationDataset.scaling is float32, numpy widens it
+    if scale.shape != (3,) or not np.all(scale > 0):
+        raise ValueError(f'scaling must be three positive voxel sizes, got {scaling}')
+    radius = {}
+    for t, table in organelles.items():
+        if not isinstance(table, OrganelleTable):
+            raise TypeError(f'organelles[{t!r}] must be an OrganelleTable')
+        if isinstance(max_vert_dist_nm, dict):
+            if t not in max_vert_dist_nm:
+                raise ValueError(f'max_vert_dist_nm has no entry for {t!r}')
+            radius[t] = float(max_vert_dist_nm[t])
+        else:
+            radius[t] = float(max_vert_dist_nm)
+        if not (radius[t] >= 0 and np.isfinite(radius[t])):
+            raise ValueError(f'max_vert_dist_nm[{t!r}] = {radius[t]}')
+    if not (D >= 0 and np.isfinite(D)):
+        raise ValueError(f'max_rep_coord_dist_nm = {D}')
+    n = len(syn_ssv)
+    _check_offsets('syn_ssv.vox_begin', np.asarray(syn_ssv.vox_begin, np.int64).reshape(-1), n, len(np.asarray(syn_ssv.voxels).reshape(-1, 3)))
+    pairs = {t: PairList.empty(n) for t in organelles}
+    stats = {t: dict.fromkeys(MAP_COUNT_NAMES, 0) for t in organelles}
+    todo = [t for t, table in organelles.items() if n and np.any(table.cells != 0)]
+    if todo:
+        mapper = _ObjectMapper(syn_ssv, scale, sample_fact, device)
+        cands = {t: mapper.candidates(organelles[t], D) for t in todo}
+        mapper.reserve(max(c['P'] for c in cands.values()))
+        for t in todo:
+            try:
+                pairs[t], stats[t] = mapper.query(cands[t], radius[t])
+            except ValueError as e:
+                raise ValueError(f'{t}: {e}') from None
+    mapping = build_synssv_mapping(n, organelles, pairs)
+    if return_stats:
+        return mapping, stats
+    return mapping

@@ -71,6 +71,10 @@ DEFAULTS = {
         # a symmetric ratio above sym_thresh gives syn_sign -1
         'cs_gap_nm': 250,
         'sym_thresh': 0.225,
+        # organelles mapped to the cell-level synapses (config.yml:156-159): a mesh vertex closer than max_vert_dist_nm to a synapse
+        # voxel counts as close; organelles whose representative coordinate is farther than max_rep_coord_dist_nm are not looked at
+        'max_vert_dist_nm': {'mi': 1000, 'vc': 500},
+        'max_rep_coord_dist_nm': 4000,
     },
 }
 
