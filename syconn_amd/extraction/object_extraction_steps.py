@@ -54,7 +54,8 @@ def _count_subsequent_mops(mops: Sequence[str]) -> Tuple[List[str], List[int]]:
 
 def object_segmentation_first_stage(prob, threshold: float, morph_ops: Sequence[str] = (), scaling=(10, 10, 20),
                                     structure: Optional[np.ndarray] = None, return_mask: bool = False, device=None,
-                                    return_device: bool = False, min_seed_vx: int = 0, return_markers: bool = False):
+                                    return_device: bool = False, min_seed_vx: int = 0, return_markers: bool = False,
+                                    return_distance: bool = False):
     """One probability map of a chunk -> ``(labels int32 (x,y,z), max_label)`` (+ the binary volume after the morphology if
     `return_mask`, + the relabelled watershed markers if `return_markers`).  `prob`: uint8 (x,y,z) numpy array or device
     tensor; `threshold` in uint8 units as the reference compares it (``tmp_data > threshold``; 0: `prob` is already a 0/1
@@ -64,7 +65,9 @@ def object_segmentation_first_stage(prob, threshold: float, morph_ops: Sequence[
     the pixel pitch of the distance transform, `return_mask` returns tmp_data (the mask the flood is confined to).
     `return_device`: leave the results on the GPU (int32 label tensor, 1-element count tensor[, uint8 mask][, int32 markers])
     -- the label volume is 4 bytes per voxel, and its consumer (``find_object_properties`` / ``segstats``, which take device
-    tensors) does not need it on the host."""
+    tensors) does not need it on the host.  `return_distance` (watershed branch only, ``ValueError`` otherwise): the float32
+    (x,y,z) distance transform of tmp_data (:349-350, of the WHOLE mask -- without it only the components the flood works on are
+    transformed) is returned last."""
     lib = L.load()
     if not torch.cuda.is_available():
         raise RuntimeError('syconn_amd: no MI355X visible to PyTorch-ROCm; this package has no CPU fallback')
@@ -75,6 +78,8 @@ def object_segmentation_first_stage(prob, threshold: float, morph_ops: Sequence[
         if m not in _MOPS:
             raise NotImplementedError(f"Only erosion or dilation allowed. Attempted to use morphological operation '{m}'.")
     watershed = 'binary_erosion' in morph_ops
+    if return_distance and not watershed:
+        raise ValueError('return_distance: only the watershed branch (binary_erosion in morph_ops) computes a distance transform')
     first_erosion_ix = morph_ops.index('binary_erosion') if watershed else len(morph_ops)      # :320
     pre, seed = morph_ops[:first_erosion_ix], morph_ops[first_erosion_ix:]
     names, counts = _count_subsequent_mops(pre) if pre else ([], [])
@@ -96,6 +101,7 @@ def object_segmentation_first_stage(prob, threshold: float, morph_ops: Sequence[
     max_label = torch.zeros(1, dtype=torch.int32, device=device)
     mask = torch.empty((X, Y, Z), dtype=torch.uint8, device=device) if return_mask else None
     markers = torch.empty((X, Y, Z), dtype=torch.int32, device=device) if (return_markers and watershed) else None
+    dist = torch.empty((X, Y, Z), dtype=torch.float32, device=device) if return_distance else None
     n = len(names)
     ops_a = (C.c_int32 * max(n, 1))(*[_MOPS[m] for m in names])
     it_a = (C.c_int32 * max(n, 1))(*counts)
@@ -110,8 +116,8 @@ def object_segmentation_first_stage(prob, threshold: float, morph_ops: Sequence[
         L.check(lib.sd_object_segmentation_watershed(
             p.data_ptr(), X, Y, Z, float(threshold), ops_a, it_a, n, sops_a, sit_a, ns, st.ctypes.data_as(C.c_void_p),
             *[int(s) for s in st.shape], int(min_seed_vx), pitch, labels.data_ptr(), max_label.data_ptr(),
-            markers.data_ptr() if markers is not None else None, None, mask.data_ptr() if mask is not None else None,
-            ws.data_ptr(), ws_bytes, stream), 'sd_object_segmentation_watershed')
+            markers.data_ptr() if markers is not None else None, dist.data_ptr() if dist is not None else None,
+            mask.data_ptr() if mask is not None else None, ws.data_ptr(), ws_bytes, stream), 'sd_object_segmentation_watershed')
     else:
         ws_bytes = lib.sd_objseg_workspace_bytes(X, Y, Z, pmax)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
@@ -119,7 +125,7 @@ def object_segmentation_first_stage(prob, threshold: float, morph_ops: Sequence[
                                            st.ctypes.data_as(C.c_void_p), *[int(s) for s in st.shape], labels.data_ptr(),
                                            max_label.data_ptr(), mask.data_ptr() if mask is not None else None, ws.data_ptr(),
                                            ws_bytes, stream), 'sd_object_segmentation')
-    extra = ((mask,) if return_mask else ()) + ((markers,) if markers is not None else ())
+    extra = ((mask,) if return_mask else ()) + ((markers,) if markers is not None else ()) + ((dist,) if dist is not None else ())
     if return_device:
         return (labels, max_label) + extra
     return (labels.cpu().numpy(), int(max_label.item())) + tuple(e.cpu().numpy() for e in extra)
