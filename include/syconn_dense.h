@@ -542,6 +542,46 @@ int sd_synssv_map_query(const uint32_t* vox_dev, const uint64_t* vox_begin_dev, 
                         uint32_t* pair_len_dev, uint64_t* pair_min_d2_dev, uint64_t* counts_dev, void* temp_dev, size_t temp_bytes,
                         void* stream);
 
+/* Properties of the partner cells at every cell-level synapse and the synapse classifier (csrc/sd_syn_props.hip).
+ *   sd_syn_props_knn     replaces the two cKDTrees per cell of cps._collect_properties_from_ssv_partners_thread (/root/reference/syconn/
+ *                        extraction/cs_processing_steps.py:161-164): colorcode_vertices (reps/rep_helper.py:320-330, k nearest mesh
+ *                        vertices and a Counter vote) and attr_for_coords (reps/super_segmentation_object.py:2961-2963, the nearest
+ *                        skeleton node), for all cells in one call.  points_dev [n_points][3], float64 or (points_f32 != 0) float32
+ *                        widened exactly; cell c owns rows begin_dev[c] .. begin_dev[c + 1] (uint64[n_cells + 1], ascending from 0 to
+ *                        n_points); labels_dev int32[n_points], or NULL: the label of a point is its row.  Query q = (q_cell_dev[q],
+ *                        q_xyz_dev[q][3]).  Its neighbours are the k_eff = min(k, points of the cell) points of its cell with the
+ *                        smallest (d^2, row), d^2 = ((dx dx) + dy dy) + dz dz in float64, nothing fused.  vote_dev[q] = the label with
+ *                        the highest count among them, on equal counts the one that occurs first in that order (-1 for a cell without
+ *                        points); optional nn_idx_dev int32[n_q][k] / nn_d2_dev double[n_q][k] = the neighbours in that order, padded
+ *                        with -1 / +inf.  stages bit 0: sort the points inside every cell and cut them into tiles of 64 with boxes
+ *                        (kept in the scratch: a later call with bit 1 alone over the same scratch, points and cells reuses it); bit 1:
+ *                        the queries.  counts_dev uint64[8] = tiles visited, tiles skipped by their box, ...; [7] != 0: an offset, a
+ *                        cell row or a point row was out of range (results invalid).
+ *                        Scratch: sd_syn_props_knn_temp_bytes(n_points, n_cells).  Limits (SD_ERR_INVALID beyond): 1 <= k <=
+ *                        SD_SYN_PROPS_MAX_K, n_points, n_q, n_cells < 2^31.
+ *   sd_syn_props_forest  replaces rfc.predict_proba([feats]) per synapse (cs_processing_steps.py:1155-1156).  The packed forest: per
+ *                        node feature_dev, threshold_dev, left_dev / right_dev (rows of the node arrays, -1 at a leaf; a child's row is
+ *                        above its parent's), proba_dev double[n_nodes][n_classes] (the class fractions of the node), tree_begin_dev
+ *                        [n_trees + 1] = the root of every tree.  out_dev double[n_rows][n_classes]: rows_dev double[n_rows]
+ *                        [n_features] cast to float32, in every tree left iff x[feature] <= threshold (float32 widened), the leaves'
+ *                        fractions added in tree order, divided by n_trees.  counts_dev uint64[8]; [7] != 0: a node or feature was out
+ *                        of range.
+ * Asynchronous on the stream.  One grid stride of the kernels is SD_SYN_PROPS_CELL_GRID blocks of four cells, SD_SYN_PROPS_POINT_GRID
+ * blocks of 256 points, SD_SYN_PROPS_QUERY_GRID blocks of four queries, SD_SYN_PROPS_FOREST_GRID blocks of 256 rows. */
+#define SD_SYN_PROPS_MAX_K 64
+#define SD_SYN_PROPS_CELL_GRID 4096
+#define SD_SYN_PROPS_POINT_GRID 1024
+#define SD_SYN_PROPS_QUERY_GRID 8192
+#define SD_SYN_PROPS_FOREST_GRID 1024
+size_t sd_syn_props_knn_temp_bytes(size_t n_points, size_t n_cells);
+int sd_syn_props_knn(const void* points_dev, int points_f32, const uint64_t* begin_dev, size_t n_cells, size_t n_points,
+                     const int32_t* labels_dev, const uint32_t* q_cell_dev, const double* q_xyz_dev, size_t n_q, int k, int stages,
+                     int32_t* vote_dev, int32_t* nn_idx_dev, double* nn_d2_dev, uint64_t* counts_dev, void* temp_dev, size_t temp_bytes,
+                     void* stream);
+int sd_syn_props_forest(const double* rows_dev, size_t n_rows, int n_features, const int32_t* feature_dev, const double* threshold_dev,
+                        const int32_t* left_dev, const int32_t* right_dev, const double* proba_dev, const int32_t* tree_begin_dev, int n_trees,
+                        int n_nodes, int n_classes, double* out_dev, uint64_t* counts_dev, void* stream);
+
 /* ---- host-side helpers of the chunk pipeline (no GPU) -----------------------------------------------------------------
  * Multi-threaded strided copy of an (nz, ny, nx)-byte box between two uint8 host arrays whose x-rows are contiguous
  * (strides in bytes), and a multi-threaded memset: what numpy slicing does on one core when the reference cuts a chunk

@@ -14,6 +14,7 @@ SD_MOP_OPENING, SD_MOP_CLOSING, SD_MOP_DILATION, SD_MOP_EROSION = 1, 2, 3, 4
 SD_CS_FIRST, SD_CS_LAST = 1, 2
 SD_CST_COLS = 24
 SD_SYNSSV_MAP_ITEM = 1024
+SD_SYN_PROPS_MAX_K, SD_SYN_PROPS_CELL_GRID, SD_SYN_PROPS_POINT_GRID, SD_SYN_PROPS_QUERY_GRID, SD_SYN_PROPS_FOREST_GRID = 64, 4096, 1024, 8192, 1024
 
 LIB_NAME = 'libsyconn_dense_hip.so'
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), os.environ.get('SD_LIB_NAME', LIB_NAME))
@@ -32,7 +33,8 @@ EXPORTS = ['sd_init', 'sd_device_count', 'sd_model_create', 'sd_model_destroy', 
            'sd_binary_morphology', 'sd_cs_syntype_table_bytes', 'sd_cs_syntype_scan', 'sd_cs_syntype_compact', 'sd_cs_syntype_records',
            'sd_cs_syntype_voxels', 'sd_syntype_masks', 'sd_cs_merge_append', 'sd_cs_merge_temp_bytes', 'sd_cs_merge_objects',
            'sd_cs_merge_synapses', 'sd_syn_ssv_temp_bytes', 'sd_syn_ssv_components', 'sd_syn_ssv_stats',
-           'sd_synssv_map_pairs_temp_bytes', 'sd_synssv_map_pairs', 'sd_synssv_map_query_temp_bytes', 'sd_synssv_map_query']
+           'sd_synssv_map_pairs_temp_bytes', 'sd_synssv_map_pairs', 'sd_synssv_map_query_temp_bytes', 'sd_synssv_map_query',
+           'sd_syn_props_knn_temp_bytes', 'sd_syn_props_knn', 'sd_syn_props_forest']
 
 
 class OpDesc(C.Structure):
@@ -171,6 +173,12 @@ def load():
     lib.sd_synssv_map_query.argtypes = [vp, vp, vp, sz, sz, sz, vp, vp, sz, sz, vp, vp, sz, sz, i32, C.POINTER(C.c_double), C.c_double, i32,
                                         sz, vp, vp, vp, vp, vp, sz, vp]
     lib.sd_synssv_map_query.restype = i32
+    # cs_processing_steps.py:161-164 (the two cKDTrees per cell behind the partner properties) and :1155-1156 (predict_proba per synapse)
+    lib.sd_syn_props_knn_temp_bytes.argtypes = [sz, sz]; lib.sd_syn_props_knn_temp_bytes.restype = sz
+    lib.sd_syn_props_knn.argtypes = [vp, i32, vp, sz, sz, vp, vp, vp, sz, i32, i32, vp, vp, vp, vp, vp, sz, vp]
+    lib.sd_syn_props_knn.restype = i32
+    lib.sd_syn_props_forest.argtypes = [vp, sz, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
+    lib.sd_syn_props_forest.restype = i32
     _lib = lib
     return lib
 

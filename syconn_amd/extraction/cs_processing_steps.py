@@ -695,3 +695,491 @@ def map_objects_from_synssv_partners(syn_ssv, organelles: dict, scaling=None, ma
     if return_stats:
         return mapping, stats
     return mapping
+
+
+# -- classify_synssv_objects, collect_properties_from_ssv_partners, export_matrix (csrc/sd_syn_props.hip) ---------------------------------
+class PackedForest:
+    """A fitted random forest as flat arrays, the form ``sd_syn_props_forest`` walks: per node ``feature`` int32, ``threshold``
+    float64, ``left`` / ``right`` int32 (rows of these arrays, -1 at a leaf, a child's row above its parent's), ``proba`` float64
+    (nodes, classes) = the class fractions of the node, and ``tree_begin`` int32 (trees + 1).  ``n_features`` is the row length."""
+
+    def __init__(self, feature, threshold, left, right, proba, tree_begin, n_features):
+        self.feature = np.ascontiguousarray(feature, dtype=np.int32).reshape(-1)
+        self.threshold = np.ascontiguousarray(threshold, dtype=np.float64).reshape(-1)
+        self.left = np.ascontiguousarray(left, dtype=np.int32).reshape(-1)
+        self.right = np.ascontiguousarray(right, dtype=np.int32).reshape(-1)
+        self.proba = np.ascontiguousarray(proba, dtype=np.float64)
+        self.tree_begin = np.ascontiguousarray(tree_begin, dtype=np.int32).reshape(-1)
+        self.n_features = int(n_features)
+        n = len(self.feature)
+        if self.proba.ndim != 2 or not (len(self.threshold) == len(self.left) == len(self.right) == len(self.proba) == n):
+            raise ValueError('PackedForest: the node arrays differ in length')
+        tb = self.tree_begin
+        if len(tb) < 2 or tb[0] != 0 or tb[-1] != n or np.any(np.diff(tb) < 1):
+            raise ValueError(f'PackedForest: tree_begin must ascend from 0 to {n} nodes with at least one node per tree')
+        if self.n_features < 1 or self.proba.shape[1] < 1:
+            raise ValueError('PackedForest: at least one feature and one class')
+        leaf = self.left < 0
+        if np.any((self.right < 0) != leaf):
+            raise ValueError('PackedForest: a node with one child')
+        inner = np.flatnonzero(~leaf)
+        tree = np.searchsorted(tb, inner, side='right') - 1
+        for child in (self.left[inner], self.right[inner]):
+            if np.any(child <= inner) or np.any(child >= tb[tree + 1]):
+                raise ValueError('PackedForest: a child must lie above its parent and inside its tree')
+        if len(inner) and (self.feature[inner].min() < 0 or self.feature[inner].max() >= self.n_features):
+            raise ValueError('PackedForest: a feature index outside the row')
+        if np.isnan(self.threshold[inner]).any() or not np.isfinite(self.proba).all():
+            raise ValueError('PackedForest: NaN threshold or non-finite class fraction')
+
+    @property
+    def n_trees(self):
+        return len(self.tree_begin) - 1
+
+    @property
+    def n_classes(self):
+        return self.proba.shape[1]
+
+    @classmethod
+    def from_sklearn(cls, rfc):
+        """From a fitted ``RandomForestClassifier`` (anything with ``estimators_[i].tree_`` and one output).  The class fractions are
+        ``tree_.value`` where its rows sum to one already (sklearn >= 1.3 returns them as they are), else ``value / value.sum()``
+        (what older versions compute per prediction)."""
+        feature, threshold, left, right, proba, begin = [], [], [], [], [], [0]
+        n_features = None
+        for est in rfc.estimators_:
+            t = est.tree_
+            value = np.asarray(t.value, np.float64)
+            if value.ndim != 3 or value.shape[1] != 1:
+                raise ValueError('PackedForest.from_sklearn: one output per tree')
+            value = value[:, 0, :]
+            total = value.sum(1, keepdims=True)
+            counts = np.abs(total - 1.0) > 1e-9
+            value = np.where(counts, value / np.where(total == 0, 1.0, total), value)
+            off = begin[-1]
+            lc, rc = np.asarray(t.children_left, np.int64), np.asarray(t.children_right, np.int64)
+            feature.append(np.where(lc < 0, 0, np.asarray(t.feature)))
+            threshold.append(np.where(lc < 0, 0.0, np.asarray(t.threshold, np.float64)))
+            left.append(np.where(lc < 0, -1, lc + off))
+            right.append(np.where(rc < 0, -1, rc + off))
+            proba.append(value)
+            begin.append(off + len(lc))
+            nf = int(getattr(t, 'n_features', getattr(est, 'n_features_in_', 0)))
+            n_features = nf if n_features is None else n_features
+            if nf != n_features:
+                raise ValueError('PackedForest.from_sklearn: trees over rows of different length')
+        if not feature:
+            raise ValueError('PackedForest.from_sklearn: no trees')
+        if len({p.shape[1] for p in proba}) != 1:
+            raise ValueError('PackedForest.from_sklearn: trees with different numbers of classes')
+        return cls(np.concatenate(feature), np.concatenate(threshold), np.concatenate(left), np.concatenate(right), np.concatenate(proba),
+                   begin, n_features)
+
+    _FIELDS = ('feature', 'threshold', 'left', 'right', 'proba', 'tree_begin')
+
+    def save(self, path):
+        np.savez_compressed(path, n_features=np.int64(self.n_features), **{k: getattr(self, k) for k in self._FIELDS})
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path) as z:
+            return cls(*(z[k] for k in cls._FIELDS), int(z['n_features']))
+
+    def check_rows(self, features) -> np.ndarray:
+        """The rows as float64 (n, n_features); NaN and values that are not finite as float32 raise ValueError (sklearn refuses them)."""
+        x = np.ascontiguousarray(features, dtype=np.float64)
+        if x.ndim != 2 or x.shape[1] != self.n_features:
+            raise ValueError(f'the forest was fitted on rows of {self.n_features} features, got an array of shape {x.shape}')
+        with np.errstate(over='ignore'):
+            if not np.isfinite(x.astype(np.float32)).all():
+                raise ValueError('features hold NaN or a value that is not finite as float32')
+        return x
+
+    def predict_proba(self, features, device=None) -> np.ndarray:
+        """float64 (n, classes) on the device: ``RandomForestClassifier.predict_proba`` with ``n_jobs=1``, bit for bit."""
+        import torch
+        from .find_object_properties import _cs_device
+        x = self.check_rows(features)
+        out = np.zeros((len(x), self.n_classes), np.float64)
+        if not len(x):
+            return out
+        if len(x) >= 2 ** 31:
+            raise ValueError('PackedForest.predict_proba: fewer than 2^31 rows per call')
+        lib, dev = L.load(), _cs_device(device)
+        up = lambda a: torch.from_numpy(a).to(dev)
+        arrs = [up(a) for a in (x, self.feature, self.threshold, self.left, self.right, self.proba, self.tree_begin)]
+        out_d = torch.empty(out.shape, dtype=torch.float64, device=dev)
+        counts_d = torch.zeros(8, dtype=torch.int64, device=dev)
+        L.check(lib.sd_syn_props_forest(arrs[0].data_ptr(), len(x), self.n_features, *(a.data_ptr() for a in arrs[1:]), self.n_trees,
+                                        len(self.feature), self.n_classes, out_d.data_ptr(), counts_d.data_ptr(),
+                                        torch.cuda.current_stream(dev).cuda_stream), 'sd_syn_props_forest')
+        out = out_d.cpu().numpy()
+        if int(counts_d.cpu().numpy()[7]):
+            raise RuntimeError('sd_syn_props_forest: a node or a feature index was out of range')
+        return out
+
+
+def classify_synssv_objects(features, forest, device=None) -> np.ndarray:
+    """``classify_synssv_objects`` (:1096-1161) on the rows of ``synssv_o_features``: ``syn_prob`` float64 (n) = column 1 of the forest's
+    class probabilities, what ``rfc.predict_proba([feats])[0][1]`` gives row by row.  `forest`: a ``PackedForest`` or a fitted sklearn
+    forest.  No CPU fallback."""
+    if not isinstance(forest, PackedForest):
+        forest = PackedForest.from_sklearn(forest)
+    if forest.n_classes < 2:
+        raise ValueError('classify_synssv_objects: the forest knows one class only, there is no column 1')
+    return np.ascontiguousarray(forest.predict_proba(features, device)[:, 1])
+
+
+class CellTable:
+    """What ``collect_properties_from_ssv_partners`` reads of the cells, plain numpy.  Per cell: ``ids`` uint64 (unique), ``celltypes``
+    int32 (default -1: no ``celltype_cnn_e3``); the mesh: ``vertices`` float32 (v, 3) in nm with ``vert_begin`` (cells + 1) and
+    ``vertex_labels[key]`` int32 (v), e.g. ``'spiness'``; the skeleton: ``nodes`` (m, 3) in voxels (kept as float64) with ``node_begin``
+    (cells + 1) and ``node_attrs[key]``: an integer array (m) such as ``'axoness_avg10000'``, or float32 (m, e) for ``'latent_morph'``;
+    ``node_attr_present[key]`` bool (cells): False where the skeleton of a cell lacks the key (default: present everywhere);
+    ``spinehead_vol`` = (``sh_begin`` (cells + 1), syn_ssv ids uint64, volumes float32): the entries of every cell's ``spinehead_vol``
+    dict, or None."""
+
+    def __init__(self, ids, vertices, vert_begin, vertex_labels, nodes, node_begin, node_attrs, celltypes=None, node_attr_present=None,
+                 spinehead_vol=None):
+        self.ids = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        n = len(self.ids)
+        if len(np.unique(self.ids)) != n:
+            raise ValueError('CellTable: a cell id occurs twice')
+        self.vertices = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+        self.vert_begin = np.ascontiguousarray(vert_begin, dtype=np.int64).reshape(-1)
+        _check_offsets('CellTable: vert_begin', self.vert_begin, n, len(self.vertices))
+        self.nodes = np.ascontiguousarray(nodes, dtype=np.float64).reshape(-1, 3)
+        self.node_begin = np.ascontiguousarray(node_begin, dtype=np.int64).reshape(-1)
+        _check_offsets('CellTable: node_begin', self.node_begin, n, len(self.nodes))
+        if not (np.isfinite(self.vertices).all() and np.isfinite(self.nodes).all()):
+            raise ValueError('CellTable: a vertex or node coordinate is not finite')
+        self.celltypes = np.full(n, -1, np.int32) if celltypes is None else np.ascontiguousarray(celltypes, dtype=np.int32).reshape(-1)
+        if len(self.celltypes) != n:
+            raise ValueError(f'CellTable: {n} cells, {len(self.celltypes)} celltypes')
+        self.vertex_labels = {}
+        for key, lab in dict(vertex_labels).items():
+            lab = np.asarray(lab)
+            lab = lab.squeeze(1) if lab.ndim == 2 else lab
+            if lab.shape != (len(self.vertices),):
+                raise ValueError('Size of vertices and their labels does not match!')
+            self.vertex_labels[key] = np.ascontiguousarray(lab, dtype=np.int32)
+        self.node_attrs, self.node_attr_present = {}, {}
+        for key, a in dict(node_attrs).items():
+            a = np.asarray(a)
+            if key == 'latent_morph':
+                a = np.ascontiguousarray(a, dtype=np.float32)
+                a = a.reshape(len(self.nodes), -1) if a.ndim != 2 else a
+            else:
+                a = np.ascontiguousarray(a.reshape(-1), dtype=np.int32)
+            if len(a) != len(self.nodes):
+                raise ValueError(f'CellTable: node attribute {key!r} holds {len(a)} rows for {len(self.nodes)} nodes')
+            self.node_attrs[key] = a
+            present = np.ones(n, bool) if node_attr_present is None or key not in node_attr_present else \
+                np.ascontiguousarray(node_attr_present[key], dtype=bool).reshape(-1)
+            if len(present) != n:
+                raise ValueError(f'CellTable: node_attr_present[{key!r}] must hold one flag per cell')
+            self.node_attr_present[key] = present
+        self.spinehead_vol = None
+        if spinehead_vol is not None:
+            sb, sid, vol = spinehead_vol
+            sb, sid = np.ascontiguousarray(sb, dtype=np.int64).reshape(-1), np.ascontiguousarray(sid, dtype=np.uint64).reshape(-1)
+            vol = np.ascontiguousarray(vol, dtype=np.float32).reshape(-1)
+            _check_offsets('CellTable: spinehead_vol offsets', sb, n, len(sid))
+            if len(vol) != len(sid):
+                raise ValueError('CellTable: spinehead_vol ids and volumes differ in length')
+            self.spinehead_vol = (sb, sid, vol)
+
+    def __len__(self):
+        return len(self.ids)
+
+    @classmethod
+    def from_cells(cls, cells):
+        """From one dict per cell: ``id``, and optionally ``celltype``, ``vertices``, ``vertex_labels`` {key: array}, ``nodes``,
+        ``node_attrs`` {key: array} (a key may be missing in some cells), ``spinehead_vol`` {syn_ssv id: volume}."""
+        cells = list(cells)
+        verts = [np.asarray(c.get('vertices', np.zeros((0, 3))), np.float32).reshape(-1, 3) for c in cells]
+        nodes = [np.asarray(c.get('nodes', np.zeros((0, 3))), np.float64).reshape(-1, 3) for c in cells]
+        vkeys = sorted({k for c in cells for k in c.get('vertex_labels', {})})
+        nkeys = sorted({k for c in cells for k in c.get('node_attrs', {})})
+        vlab = {}
+        for k in vkeys:
+            for c, v in zip(cells, verts):
+                if len(v) and k not in c.get('vertex_labels', {}):
+                    raise ValueError(f'CellTable: cell {c["id"]} has vertices but no {k!r} labels')
+            vlab[k] = np.concatenate([np.asarray(c.get('vertex_labels', {}).get(k, np.zeros(0)), np.int64).reshape(-1) for c in cells])
+        nattr, present = {}, {}
+        for k in nkeys:
+            parts = [np.asarray(c['node_attrs'][k]) for c in cells if k in c.get('node_attrs', {})]
+            tail = parts[0].shape[1:] if k == 'latent_morph' else ()
+            fill = [np.asarray(c['node_attrs'][k]).reshape((len(m),) + tail) if k in c.get('node_attrs', {}) else
+                    np.zeros((len(m),) + tail, parts[0].dtype) for c, m in zip(cells, nodes)]
+            nattr[k] = np.concatenate(fill)
+            present[k] = np.array([k in c.get('node_attrs', {}) for c in cells], bool)
+        sh = None
+        if any('spinehead_vol' in c for c in cells):
+            items = [sorted(c.get('spinehead_vol', {}).items()) for c in cells]
+            sh = (np.concatenate(([0], np.cumsum([len(i) for i in items]))), np.array([k for i in items for k, _ in i], np.uint64),
+                  np.array([v for i in items for _, v in i], np.float32))
+        offs = lambda parts: np.concatenate(([0], np.cumsum([len(p) for p in parts])))
+        return cls([c['id'] for c in cells], np.concatenate(verts) if verts else np.zeros((0, 3)), offs(verts), vlab,
+                   np.concatenate(nodes) if nodes else np.zeros((0, 3)), offs(nodes), nattr, [c.get('celltype', -1) for c in cells], present, sh)
+
+
+class SynSsvProperties:
+    """What ``collect_properties_from_ssv_partners`` stores per synapse; column p = partner slot p: ``partner_axoness``,
+    ``partner_spiness``, ``partner_celltypes`` int32 (n, 2), ``partner_spineheadvol`` float32 (n, 2), ``latent_morph`` float32
+    (n, 2, e), ``syn_sign`` int64 (n)."""
+
+    COLUMNS = ('partner_axoness', 'partner_spiness', 'partner_celltypes', 'partner_spineheadvol', 'latent_morph', 'syn_sign')
+
+    def __init__(self, **columns):
+        for name in self.COLUMNS:
+            setattr(self, name, columns[name])
+
+    def __len__(self):
+        return len(self.syn_sign)
+
+    def as_dicts(self) -> list:
+        """One dict per synapse with the keys ``_from_cell_to_syn_dict`` (:222-227) adds to its attribute dict: two-element lists,
+        and ``syn_sign``."""
+        return [dict(partner_axoness=[self.partner_axoness[i, 0], self.partner_axoness[i, 1]],
+                     partner_spiness=[self.partner_spiness[i, 0], self.partner_spiness[i, 1]],
+                     partner_celltypes=[self.partner_celltypes[i, 0], self.partner_celltypes[i, 1]],
+                     partner_spineheadvol=[self.partner_spineheadvol[i, 0], self.partner_spineheadvol[i, 1]],
+                     syn_sign=int(self.syn_sign[i]), latent_morph=[self.latent_morph[i, 0], self.latent_morph[i, 1]]) for i in range(len(self))]
+
+
+def segmented_knn(points, begin, labels, q_cell, q_xyz, k: int, device=None, return_neighbours: bool = False, return_counts: bool = False):
+    """``sd_syn_props_knn``: for every query (`q_cell` = row of its cell, `q_xyz` float64 nm) the vote over the ``min(k, points of the
+    cell)`` points of cell c = ``points[begin[c]:begin[c + 1]]`` (float32 or float64, (v, 3)) with the smallest (d^2, row), d^2 =
+    ((dx dx) + dy dy) + dz dz in float64: the label (`labels` int32 per point; None: the row of the point) with the highest count, on
+    equal counts the one that occurs first in that order; -1 for a cell without points.  With `return_neighbours` also the rows
+    (n_q, k) int32, padded with -1, and d^2 (n_q, k) float64, padded with inf; with `return_counts` the device's counters."""
+    import torch
+    from .find_object_properties import _cs_device
+    pts = np.asarray(points)
+    pts = np.ascontiguousarray(pts, dtype=np.float32 if pts.dtype == np.float32 else np.float64).reshape(-1, 3)
+    begin = np.ascontiguousarray(begin, dtype=np.int64).reshape(-1)
+    n_cells = len(begin) - 1
+    if n_cells < 0:
+        raise ValueError('segmented_knn: begin must hold cells + 1 offsets')
+    _check_offsets('segmented_knn: begin', begin, n_cells, len(pts))
+    q_cell = np.ascontiguousarray(q_cell, dtype=np.int64).reshape(-1)
+    q_xyz = np.ascontiguousarray(q_xyz, dtype=np.float64).reshape(-1, 3)
+    n_q = len(q_cell)
+    if isinstance(k, bool) or int(k) != k:
+        raise ValueError(f'k must be an integer, got {k!r}')
+    k = int(k)
+    if len(q_xyz) != n_q:
+        raise ValueError(f'segmented_knn: {n_q} query cells, {len(q_xyz)} coordinates')
+    if n_q and (q_cell.min() < 0 or q_cell.max() >= n_cells):
+        raise ValueError('segmented_knn: a query names a cell row outside the table')
+    if not (np.isfinite(pts).all() and np.isfinite(q_xyz).all()):
+        raise ValueError('segmented_knn: a coordinate is not finite')
+    if labels is not None:
+        labels = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
+        if len(labels) != len(pts):
+            raise ValueError('Size of vertices and their labels does not match!')
+    lib, dev = L.load(), _cs_device(device)
+    up = lambda a: torch.from_numpy(a).to(dev)
+    pts_d, begin_d, lab_d = up(pts), up(begin), None if labels is None else up(labels)
+    qc_d, qx_d = up(q_cell.astype(np.uint32).view(np.int32)), up(q_xyz)
+    kk = max(1, min(k, L.SD_SYN_PROPS_MAX_K))
+    vote_d = torch.empty(max(n_q, 1), dtype=torch.int32, device=dev)
+    idx_d = torch.empty((max(n_q, 1), kk), dtype=torch.int32, device=dev) if return_neighbours else None
+    d2_d = torch.empty((max(n_q, 1), kk), dtype=torch.float64, device=dev) if return_neighbours else None
+    counts_d = torch.zeros(8, dtype=torch.int64, device=dev)
+    tmp = torch.empty(lib.sd_syn_props_knn_temp_bytes(len(pts), n_cells), dtype=torch.uint8, device=dev)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    L.check(lib.sd_syn_props_knn(pts_d.data_ptr(), int(pts.dtype == np.float32), begin_d.data_ptr(), n_cells, len(pts), ptr(lab_d), qc_d.data_ptr(),
+                                 qx_d.data_ptr(), n_q, k, 3, vote_d.data_ptr(), ptr(idx_d), ptr(d2_d), counts_d.data_ptr(), tmp.data_ptr(),
+                                 tmp.numel(), torch.cuda.current_stream(dev).cuda_stream), 'sd_syn_props_knn')
+    counts = counts_d.cpu().numpy()
+    if int(counts[7]):
+        raise RuntimeError('sd_syn_props_knn: an offset, a cell row or a point row was out of range')
+    out = [vote_d.cpu().numpy()[:n_q]]
+    if return_neighbours:
+        out += [idx_d.cpu().numpy()[:n_q], d2_d.cpu().numpy()[:n_q]]
+    if return_counts:
+        out.append(dict(tiles_visited=int(counts[0]), tiles_skipped=int(counts[1])))
+    return out[0] if len(out) == 1 else tuple(out)
+
+
+def spine_vertices(cells: CellTable, used, semseg_key: str, ds_vertices: int, ignore_labels):
+    """The vertices ``semseg_for_coords`` (super_segmentation_object.py:2219-2237) hands to the tree, for the cells flagged in `used`:
+    every ``ds``-th vertex of a cell (``ds = max(1, ds_vertices // 10)`` below 5e6 vertices), without the ignored labels.
+    -> (vertices float32, labels int32, begin int64 (cells + 1)); cells that are not used keep no vertex."""
+    if semseg_key not in cells.vertex_labels:
+        if len(cells.vertices):
+            raise KeyError(semseg_key)
+        lab = np.zeros(0, np.int32)
+    else:
+        lab = cells.vertex_labels[semseg_key]
+    n_vert = np.diff(cells.vert_begin)
+    ds = np.where(n_vert < 5e6, max(1, int(ds_vertices) // 10), int(ds_vertices))
+    cell_of = np.repeat(np.arange(len(cells)), n_vert)
+    local = np.arange(len(cells.vertices)) - cells.vert_begin[cell_of]
+    keep = np.asarray(used, bool)[cell_of] & (local % ds[cell_of] == 0)
+    keep &= ~np.isin(lab, np.asarray(list(ignore_labels or []), np.int64))
+    begin = np.concatenate(([0], np.cumsum(np.bincount(cell_of[keep], minlength=len(cells))))).astype(np.int64)
+    return cells.vertices[keep], lab[keep], begin
+
+
+def collect_properties_from_ssv_partners(syn_ssv, cells: CellTable, scaling=None, syn_ids=None, k=None, ds_vertices=None, ignore_labels=None,
+                                         pred_key_ax=None, n_embedding=None, sym_thresh=None, device=None) -> SynSsvProperties:
+    """``collect_properties_from_ssv_partners`` (:44-106) with its workers ``_collect_properties_from_ssv_partners_thread`` (:109-174)
+    and ``_from_cell_to_syn_dict`` (:177-229) on the ``SynSsvTable`` of ``combine_and_split_syn`` (``neuron_partners``, ``rep_coords``,
+    ``syn_type_sym_ratio``) and a ``CellTable``.  For every synapse and partner: the spine label by a vote over the `k` nearest of the
+    partner cell's mesh vertices (``semseg_for_coords``), the compartment (`pred_key_ax`) and ``latent_morph`` of the nearest
+    skeleton node (``attr_for_coords``), the cell type and the spine-head volume stored for `syn_ids` (default: the row number).
+    All cells go through two calls of ``sd_syn_props_knn``; the node attributes are gathered on the device.  The defaults come from
+    ``config['spines']['semseg2coords_spines']``, ``config['compartments']``, ``config['tcmn']`` and ``config['cell_objects']``.
+
+    A cell without mesh vertices gets zeros in every column; one without skeleton nodes -1 and inf; a skeleton without the key -1
+    (``latent_morph``: inf).  ValueError: a partner cell that is not in the table, a cell whose vertices are all ignored.
+    Not built: storages, ``cache_syn.pkl`` files, batch jobs; k <= 64.  No CPU fallback."""
+    import torch
+    from .. import global_params
+    from .find_object_properties import _cs_device
+    cfg = global_params.config
+    if scaling is None:
+        scaling = cfg['scaling']
+    sp = cfg['spines']['semseg2coords_spines']
+    k = sp['k'] if k is None else k
+    ds_vertices = sp['ds_vertices'] if ds_vertices is None else ds_vertices
+    ignore_labels = sp['ignore_labels'] if ignore_labels is None else ignore_labels
+    if pred_key_ax is None:
+        comp = cfg['compartments']
+        pred_key_ax = '{}_avg{}'.format(comp['view_properties_semsegax']['semseg_key'], comp['dist_axoness_averaging'])
+    m = int(cfg['tcmn']['ndim_embedding'] if n_embedding is None else n_embedding)
+    sym_thresh = cfg['cell_objects']['sym_thresh'] if sym_thresh is None else sym_thresh
+    if not isinstance(cells, CellTable):
+        raise TypeError('cells must be a CellTable')
+    for name, v in (('k', k), ('ds_vertices', ds_vertices)):
+        if isinstance(v, bool) or int(v) != v or int(v) < 1:
+            raise ValueError(f'{name} must be an integer >= 1, got {v!r}')
+    if int(k) > L.SD_SYN_PROPS_MAX_K:
+        raise ValueError(f'k = {k}: at most {L.SD_SYN_PROPS_MAX_K} neighbours per query')
+    scale = np.asarray(scaling, np.float32).reshape(-1).astype(np.float64)   # SuperSegmentationObject.scaling is float32, numpy widens it
+    if scale.shape != (3,) or not np.all(scale > 0):
+        raise ValueError(f'scaling must be three positive voxel sizes, got {scaling}')
+    if 'latent_morph' in cells.node_attrs and cells.node_attrs['latent_morph'].shape[1] != m:
+        raise ValueError(f"latent_morph holds {cells.node_attrs['latent_morph'].shape[1]} values per node, ndim_embedding is {m}")
+    n = len(syn_ssv)
+    partners = np.ascontiguousarray(syn_ssv.neuron_partners, dtype=np.uint64).reshape(n, 2)
+    rep = np.ascontiguousarray(syn_ssv.rep_coords, dtype=np.int32).reshape(n, 3)
+    ratio = np.asarray(syn_ssv.syn_type_sym_ratio, np.float64).reshape(-1)
+    syn_ids = np.arange(n, dtype=np.uint64) if syn_ids is None else np.ascontiguousarray(syn_ids, dtype=np.uint64).reshape(-1)
+    if len(ratio) != n or len(syn_ids) != n:
+        raise ValueError(f'{n} synapses, {len(ratio)} syn_type_sym_ratio, {len(syn_ids)} syn_ids')
+    order = np.argsort(cells.ids, kind='stable')
+    side_cell_id = partners.reshape(-1)
+    if 2 * n and not len(cells):
+        raise ValueError(f'Could not find the partner cell {int(side_cell_id[0])} of synssv with ID {int(syn_ids[0])} in the cell table.')
+    at = np.minimum(np.searchsorted(cells.ids[order], side_cell_id), max(len(cells) - 1, 0))
+    row = order[at] if len(cells) else np.zeros(0, np.int64)
+    miss = np.flatnonzero(cells.ids[row] != side_cell_id) if 2 * n else np.zeros(0, np.int64)
+    if len(miss):
+        s = int(miss[0])
+        raise ValueError(f'Could not find the partner cell {int(side_cell_id[s])} of synssv with ID {int(syn_ids[s // 2])} in the cell table.')
+    props = dict(partner_axoness=np.zeros(2 * n, np.int32), partner_spiness=np.zeros(2 * n, np.int32), partner_celltypes=np.zeros(2 * n, np.int32),
+                 partner_spineheadvol=np.zeros(2 * n, np.float32), latent_morph=np.zeros((2 * n, m), np.float32))
+    sign = np.where(ratio > sym_thresh, -1, 1).astype(np.int64)
+    if n:
+        used = np.zeros(len(cells), bool)
+        used[row] = True
+        has_mesh = np.diff(cells.vert_begin) > 0
+        has_skel = np.diff(cells.node_begin) > 0
+        sides = np.flatnonzero(has_mesh[row])                    # the others keep their zeros (:144-152)
+        q_xyz = np.repeat(rep.astype(np.float64) * scale, 2, 0)  # np.array(coords) * self.scaling
+        if len(sides):
+            verts, lab, begin = spine_vertices(cells, used & has_mesh, 'spiness', ds_vertices, ignore_labels)
+            empty = np.flatnonzero(used & has_mesh & (np.diff(begin) == 0))
+            if len(empty):
+                raise ValueError(f'every mesh vertex of cell {int(cells.ids[empty[0]])} carries an ignored label: no vertex to vote')
+            props['partner_spiness'][sides] = segmented_knn(verts, begin, lab, row[sides], q_xyz[sides], int(k), device)
+            props['partner_celltypes'][sides] = cells.celltypes[row[sides]]
+            vol = np.full(len(sides), -1, np.float32)
+            if cells.spinehead_vol is not None:
+                sb, sid, sv = cells.spinehead_vol
+                ids_all = np.unique(np.concatenate([sid, syn_ids]))                         # (cell row, syn_ssv id) as one integer
+                if len(cells) * len(ids_all) >= 2 ** 62:
+                    raise ValueError('spinehead_vol: cells x synapse ids do not fit 62 bits')
+                have = np.repeat(np.arange(len(cells)), np.diff(sb)) * len(ids_all) + np.searchsorted(ids_all, sid)
+                o = np.argsort(have, kind='stable')
+                want = row[sides] * len(ids_all) + np.searchsorted(ids_all, syn_ids[sides // 2])
+                if len(have):
+                    j = np.minimum(np.searchsorted(have[o], want), len(have) - 1)
+                    hit = have[o][j] == want
+                    vol[hit] = sv[o][j[hit]]
+            props['partner_spineheadvol'][sides] = vol
+            props['partner_axoness'][sides] = -1
+            props['latent_morph'][sides] = np.inf
+            sk = sides[has_skel[row[sides]]]
+            if len(sk):
+                nb = np.concatenate(([0], np.cumsum(np.where(used & has_mesh, np.diff(cells.node_begin), 0)))).astype(np.int64)
+                node_keep = np.repeat(used & has_mesh, np.diff(cells.node_begin))
+                kept_rows = np.flatnonzero(node_keep)             # kept node j is node kept_rows[j] of the table
+                nearest = segmented_knn(cells.nodes[node_keep] * scale, nb, None, row[sk], q_xyz[sk], 1, device)
+                dev = _cs_device(device)
+                near_d = torch.from_numpy(kept_rows[nearest]).to(dev)
+                if pred_key_ax in cells.node_attrs:
+                    ax = torch.from_numpy(cells.node_attrs[pred_key_ax]).to(dev)[near_d].cpu().numpy()
+                    ok = cells.node_attr_present[pred_key_ax][row[sk]]
+                    props['partner_axoness'][sk[ok]] = ax[ok]
+                if 'latent_morph' in cells.node_attrs:
+                    lm = torch.from_numpy(cells.node_attrs['latent_morph']).to(dev)[near_d].cpu().numpy()
+                    ok = cells.node_attr_present['latent_morph'][row[sk]]
+                    props['latent_morph'][sk[ok]] = lm[ok]
+    return SynSsvProperties(partner_axoness=props['partner_axoness'].reshape(n, 2), partner_spiness=props['partner_spiness'].reshape(n, 2),
+                            partner_celltypes=props['partner_celltypes'].reshape(n, 2),
+                            partner_spineheadvol=props['partner_spineheadvol'].reshape(n, 2), latent_morph=props['latent_morph'].reshape(n, 2, m),
+                            syn_sign=sign)
+
+
+def conn_mat_header(n_embedding: int) -> str:
+    """:1492-1498."""
+    return ("x\ty\tz\tssv1\tssv2\tsize\tcomp1\tcomp2\tcelltype1\tcelltype2\tspiness1\tspiness2\tsynprob\tspinehead_vol1\tspinehead_vol2" +
+            "".join(["\tlatentmorph1_{}".format(ix) for ix in range(n_embedding)]) +
+            "".join(["\tlatentmorph2_{}".format(ix) for ix in range(n_embedding)]))
+
+
+def export_matrix(syn_ssv, props: SynSsvProperties, syn_prob, mesh_area, dest_folder=None, threshold_syn=0, export_kzip: bool = False,
+                  n_embedding=None) -> str:
+    """``export_matrix`` (:1434-1499): ``dest_folder + '/conn_mat.csv'``, one row per synapse with ``syn_prob > threshold_syn``
+    (None: ``config['cell_objects']['thresh_synssv_proba']``): x, y, z (``rep_coords``), the two cell ids, ``size = mesh_area / 2 *
+    syn_sign``, compartments, cell types, spine labels, the probability, the spine-head volumes and the two embeddings, written by
+    ``np.savetxt`` with tabs in its default format.  An existing file is renamed with a time stamp first.  -> the path.
+    ``export_kzip=True`` raises NotImplementedError (the skeleton classes are not built).  Host only."""
+    import datetime
+    import os
+    import time
+    from .. import global_params
+    cfg = global_params.config
+    if export_kzip:
+        raise NotImplementedError('export_matrix: the kzip export needs the skeleton classes, which are not built')
+    if threshold_syn is None:
+        threshold_syn = cfg['cell_objects']['thresh_synssv_proba']
+    if dest_folder is None:
+        dest_folder = cfg.working_dir + '/connectivity_matrix/'
+    n = len(syn_ssv)
+    syn_prob = np.asarray(syn_prob, np.float64).reshape(-1)
+    area = np.asarray(mesh_area, np.float64).reshape(-1)
+    if len(props) != n or len(syn_prob) != n or len(area) != n:
+        raise ValueError(f'{n} synapses, {len(props)} property rows, {len(syn_prob)} probabilities, {len(area)} mesh areas')
+    m_emb = props.latent_morph.shape[2] if n_embedding is None else int(n_embedding)
+    if props.latent_morph.shape[2] != m_emb:
+        raise ValueError(f'latent_morph holds {props.latent_morph.shape[2]} values, the header {m_emb}')
+    os.makedirs(dest_folder, exist_ok=True)                      # the reference makes the parent only: its default ends with '/'
+    dest_name = dest_folder + '/conn_mat'
+    m = syn_prob > threshold_syn
+    m_sizes = area[m] / 2
+    m_sizes = np.multiply(m_sizes, np.asarray(props.syn_sign)[m]).reshape(-1)[:, None]
+    table = np.concatenate([np.asarray(syn_ssv.rep_coords).reshape(n, 3)[m], np.asarray(syn_ssv.neuron_partners).reshape(n, 2)[m], m_sizes,
+                            props.partner_axoness[m], props.partner_celltypes[m], props.partner_spiness[m], syn_prob[m][:, None],
+                            props.partner_spineheadvol[m], props.latent_morph[m].reshape(int(m.sum()), -1)], axis=1)
+    if os.path.isfile(dest_name + '.csv'):                       # do not overwrite previous files
+        st = datetime.datetime.fromtimestamp(time.time()).strftime('%Y-%m-%d %H:%M:%S')
+        os.rename(dest_name + '.csv', '{}_{}.csv'.format(dest_name, st))
+    np.savetxt(dest_name + '.csv', table, delimiter='\t', header=conn_mat_header(m_emb))
+    return dest_name + '.csv'

@@ -75,7 +75,14 @@ DEFAULTS = {
         # voxel counts as close; organelles whose representative coordinate is farther than max_rep_coord_dist_nm are not looked at
         'max_vert_dist_nm': {'mi': 1000, 'vc': 500},
         'max_rep_coord_dist_nm': 4000,
+        # export_matrix(threshold_syn=None) keeps the synapses with a probability above this (config.yml:161)
+        'thresh_synssv_proba': 0.5,
     },
+    # partner properties of the cell-level synapses (config.yml:271-274, :278, :288, :303): the vote over the k nearest mesh vertices
+    # (every ds_vertices-th one, without the ignored labels), the skeleton key of the compartment, the length of the embedding
+    'spines': {'semseg2coords_spines': {'k': 50, 'ds_vertices': 1, 'ignore_labels': [4, 5]}},
+    'compartments': {'dist_axoness_averaging': 10000, 'view_properties_semsegax': {'semseg_key': 'axoness'}},
+    'tcmn': {'ndim_embedding': 10},
 }
 
 
