@@ -582,6 +582,80 @@ int sd_syn_props_forest(const double* rows_dev, size_t n_rows, int n_features, c
                         const int32_t* left_dev, const int32_t* right_dev, const double* proba_dev, const int32_t* tree_begin_dev, int n_trees,
                         int n_nodes, int n_classes, double* out_dev, uint64_t* counts_dev, void* stream);
 
+/* ---- spine head volumes (csrc/sd_spinehead.hip) ------------------------------------------------------------------------
+ * The per-window steps of extract_spinehead_volume_mesh (/root/reference/syconn/reps/super_segmentation_helper.py:2068-2198) that the
+ * entries above do not cover.  All volumes (X,Y,Z) with z fastest, < 2^31 voxels; everything is asynchronous on the stream.  One grid
+ * stride of the kernels is SD_SPINEHEAD_VOX_GRID blocks of 256 voxels (or peaks, or queries), SD_SPINEHEAD_VERT_GRID blocks of 256
+ * (window, vertex) pairs, SD_SPINEHEAD_ID_GRID blocks of 256 table rows.  Scratch of every entry that takes `workspace_dev`:
+ * sd_spinehead_workspace_bytes(X, Y, Z), which also covers sd_edt_squared and sd_marker_flood on the same extents.
+ *   sd_edt_squared (csrc/sd_objseg.hip)  ndimage.distance_transform_edt(seg) (:2161) as exact SQUARED distances: d2_dev int32 = squared
+ *                        Euclidean distance (pitch 1, 1, 1) of every mask voxel to the nearest voxel that is 0 INSIDE the array, 0 in the
+ *                        background; the kernels of sd_object_segmentation_watershed on the whole volume.  A mask without any background
+ *                        voxel gives 0x3f000000 everywhere (scipy's result is undefined there).  Extents <= 18000.  Scratch:
+ *                        sd_objseg_workspace_bytes(X, Y, Z, 0).
+ *   sd_spinehead_window_mask  kd.load_seg(offset, size) + ndimage.zoom(seg, 1 / ds, order=0) + relabel_vol_nonexist2zero / (seg ==
+ *                        sv_ids[0]) (:2135-2141; both branches give the same 0/1 mask).  seg_dev: a resident (VX,VY,VZ) uint64 volume
+ *                        whose voxel 0 is vol_origin_xyz (HOST int64[3]); voxels outside it read 0.  win_offset_xyz HOST int64[3].
+ *                        tab_*_dev int32[X] / [Y] / [Z]: the source index of every output sample along the axis, -1 = scipy's constant
+ *                        0 (the order-0 zoom is separable; the host builds the tables by scipy's rule: n_out = round(n_in / ds),
+ *                        coordinate c = i (n_in - 1) / (n_out - 1) in double, c > n_in - 1 -> -1, else floor(c + 0.5)).
+ *                        cell_sv_dev: the cell's supervoxel ids, sorted ascending, n_sv >= 1 (binary search per voxel).
+ *   sd_spinehead_fill_holes  ndimage.binary_fill_holes (:2143): a background voxel becomes foreground unless its 6-connected background
+ *                        component owns a voxel of the window border (the inverted mask labelled by sd_object_segmentation's
+ *                        components).  *n_filled_dev = foreground voxels of filled_dev (0: the reference raises ValueError, :2144).
+ *   sd_spinehead_peaks   peak_local_max(distance, footprint=np.ones((3, 3, 3)), labels=seg) (:2162) restated from skimage 0.18 / 0.19;
+ *                        skimage is absent from the reference tree and this image: parity-UNPINNED.  roi = bounding box of the mask
+ *                        voxels that are not on the outermost voxel layer of the window (exclude_border with min_distance 1; none: no
+ *                        peaks).  A mask voxel inside roi is a peak iff its d2 equals the largest d2 over the mask voxels of its 3x3x3
+ *                        neighbourhood clipped to roi and d2 > 0; mask voxels outside roi are neither peaks nor seen.  If EVERY mask voxel
+ *                        in roi equals its neighbourhood maximum (skimage's "trivial image", e.g. a sheet one voxel thick) there are no
+ *                        peaks.  ensure_spacing with spacing 1 culls nothing: every voxel of a plateau is a peak.  peaks_dev int32
+ *                        [max_peaks][3] in raster order (flag + scan); *n_peaks_dev = their number, which may exceed max_peaks (the
+ *                        list is cut: the caller must treat that as an error).
+ *   sd_spinehead_box_vertices  in_bounding_box(verts, [offset + size / 2, size]) (:2150-2153, extraction/in_bounding_boxC.pyx) for n_win
+ *                        windows at once: vertex v (verts_dev [n_verts][3] in voxels, float64 or float32 widened exactly, labels_dev int32)
+ *                        is in window w iff -e < v - (win_offset_dev[w] + size / 2) < e on every axis in float64, e = the half edge
+ *                        rounded to C float.  stages bit 0: flags, scan, begin_dev uint64[n_win + 2] (begin[w] = vertices in windows < w;
+ *                        entries n_win and n_win + 1 = the total: segment n_win is empty); bit 1: points_dev double[total][3] = v -
+ *                        window offset (:2165) and point_labels_dev with label 0 rewritten to 9 (:2160), window by window in vertex
+ *                        order -- the segmented point set sd_syn_props_knn takes.  Scratch sd_spinehead_box_vertices_temp_bytes (kept
+ *                        between the two stages); n_verts, n_win >= 1, n_verts * n_win < 2^31.
+ *   sd_spinehead_queries the queries of colorcode_vertices (:2165): q_slots <= max_peaks slots per window (the caller sizes them by the
+ *                        largest peak count of its batch); for window w and slot p < min(n_peaks_dev[w], q_slots): q_cell = w, q_xyz =
+ *                        peak * ds_xyz (HOST double[3]); other slots: q_cell = n_win (the empty segment: vote -1).  peaks_dev
+ *                        [n_win][max_peaks][3], q_*_dev [n_win * q_slots].
+ *   sd_spinehead_markers local_maxi (:2167-2168): markers_dev int32 = 0, then votes_dev[p] at peak p of one window (negative votes: 0).
+ *   sd_spinehead_select  :2171-2196.  head = (flood_dev == 1); its 6-connected components numbered like ndimage.label (objects_dev,
+ *                        optional int32 output); nb_obj <= 1: id 1; else the id with the most voxels in labels[c - 10 : c + 11] per axis
+ *                        with numpy's slice rules (a negative start wraps, so c < 10 on an axis empties the slice; the stop clips),
+ *                        the smallest id on equal counts; if the slice holds no labelled voxel the object owning the voxel nearest to c
+ *                        (distance ((v - c) * scaling_xyz)^2 summed in double: exact for integral scalings; ties: lowest id, then raster
+ *                        index).  c_xyz HOST int64[3] = rep_coord - offset (mag-1 voxels indexing the zoomed volume, as the reference
+ *                        does), scaling_xyz HOST double[3].  result_dev int32[3] = voxels of the chosen object (0 if nb_obj == 0), the
+ *                        chosen id, nb_obj. */
+#define SD_SPINEHEAD_VOX_GRID 8192
+#define SD_SPINEHEAD_VERT_GRID 1024
+#define SD_SPINEHEAD_ID_GRID 1024
+size_t sd_spinehead_workspace_bytes(int X, int Y, int Z);
+int sd_edt_squared(const uint8_t* mask_dev, int X, int Y, int Z, int32_t* d2_dev, void* workspace_dev, size_t ws_bytes, void* stream);
+int sd_spinehead_window_mask(const uint64_t* seg_dev, int VX, int VY, int VZ, const int64_t* vol_origin_xyz, const int64_t* win_offset_xyz,
+                             const int32_t* tab_x_dev, const int32_t* tab_y_dev, const int32_t* tab_z_dev, int X, int Y, int Z,
+                             const uint64_t* cell_sv_dev, size_t n_sv, uint8_t* mask_dev, void* stream);
+int sd_spinehead_fill_holes(const uint8_t* mask_dev, int X, int Y, int Z, uint8_t* filled_dev, int32_t* n_filled_dev, void* workspace_dev,
+                            size_t ws_bytes, void* stream);
+int sd_spinehead_peaks(const uint8_t* mask_dev, const int32_t* d2_dev, int X, int Y, int Z, int32_t* peaks_dev, size_t max_peaks,
+                       int32_t* n_peaks_dev, void* workspace_dev, size_t ws_bytes, void* stream);
+size_t sd_spinehead_box_vertices_temp_bytes(size_t n_verts, size_t n_win);
+int sd_spinehead_box_vertices(const void* verts_dev, int verts_f32, const int32_t* labels_dev, size_t n_verts, const int64_t* win_offset_dev,
+                              size_t n_win, const int32_t* win_size_xyz, int stages, uint64_t* begin_dev, double* points_dev,
+                              int32_t* point_labels_dev, size_t max_points, void* temp_dev, size_t temp_bytes, void* stream);
+int sd_spinehead_queries(const int32_t* peaks_dev, const int32_t* n_peaks_dev, size_t n_win, size_t max_peaks, size_t q_slots,
+                         const double* ds_xyz, uint32_t* q_cell_dev, double* q_xyz_dev, void* stream);
+int sd_spinehead_markers(const int32_t* peaks_dev, const int32_t* n_peaks_dev, const int32_t* votes_dev, size_t max_peaks, int X, int Y, int Z,
+                         int32_t* markers_dev, void* stream);
+int sd_spinehead_select(const int32_t* flood_dev, int X, int Y, int Z, const int64_t* c_xyz, const double* scaling_xyz, int32_t* objects_dev,
+                        int32_t* result_dev, void* workspace_dev, size_t ws_bytes, void* stream);
+
 /* ---- host-side helpers of the chunk pipeline (no GPU) -----------------------------------------------------------------
  * Multi-threaded strided copy of an (nz, ny, nx)-byte box between two uint8 host arrays whose x-rows are contiguous
  * (strides in bytes), and a multi-threaded memset: what numpy slicing does on one core when the reference cuts a chunk

@@ -14,6 +14,7 @@ SD_MOP_OPENING, SD_MOP_CLOSING, SD_MOP_DILATION, SD_MOP_EROSION = 1, 2, 3, 4
 SD_CS_FIRST, SD_CS_LAST = 1, 2
 SD_CST_COLS = 24
 SD_SYNSSV_MAP_ITEM = 1024
+SD_SPINEHEAD_VOX_GRID, SD_SPINEHEAD_VERT_GRID, SD_SPINEHEAD_ID_GRID = 8192, 1024, 1024
 SD_SYN_PROPS_MAX_K, SD_SYN_PROPS_CELL_GRID, SD_SYN_PROPS_POINT_GRID, SD_SYN_PROPS_QUERY_GRID, SD_SYN_PROPS_FOREST_GRID = 64, 4096, 1024, 8192, 1024
 
 LIB_NAME = 'libsyconn_dense_hip.so'
@@ -34,7 +35,9 @@ EXPORTS = ['sd_init', 'sd_device_count', 'sd_model_create', 'sd_model_destroy', 
            'sd_cs_syntype_voxels', 'sd_syntype_masks', 'sd_cs_merge_append', 'sd_cs_merge_temp_bytes', 'sd_cs_merge_objects',
            'sd_cs_merge_synapses', 'sd_syn_ssv_temp_bytes', 'sd_syn_ssv_components', 'sd_syn_ssv_stats',
            'sd_synssv_map_pairs_temp_bytes', 'sd_synssv_map_pairs', 'sd_synssv_map_query_temp_bytes', 'sd_synssv_map_query',
-           'sd_syn_props_knn_temp_bytes', 'sd_syn_props_knn', 'sd_syn_props_forest']
+           'sd_syn_props_knn_temp_bytes', 'sd_syn_props_knn', 'sd_syn_props_forest', 'sd_spinehead_workspace_bytes', 'sd_edt_squared',
+           'sd_spinehead_window_mask', 'sd_spinehead_fill_holes', 'sd_spinehead_peaks', 'sd_spinehead_box_vertices_temp_bytes',
+           'sd_spinehead_box_vertices', 'sd_spinehead_queries', 'sd_spinehead_markers', 'sd_spinehead_select']
 
 
 class OpDesc(C.Structure):
@@ -179,6 +182,20 @@ def load():
     lib.sd_syn_props_knn.restype = i32
     lib.sd_syn_props_forest.argtypes = [vp, sz, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
     lib.sd_syn_props_forest.restype = i32
+    # reps/super_segmentation_helper.py:2068-2198 (extract_spinehead_volume_mesh, the per-window steps)
+    i64p, i32p, f64p = C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_double)
+    lib.sd_spinehead_workspace_bytes.argtypes = [i32, i32, i32]; lib.sd_spinehead_workspace_bytes.restype = sz
+    lib.sd_edt_squared.argtypes = [vp, i32, i32, i32, vp, vp, sz, vp]; lib.sd_edt_squared.restype = i32
+    lib.sd_spinehead_window_mask.argtypes = [vp, i32, i32, i32, i64p, i64p, vp, vp, vp, i32, i32, i32, vp, sz, vp, vp]
+    lib.sd_spinehead_window_mask.restype = i32
+    lib.sd_spinehead_fill_holes.argtypes = [vp, i32, i32, i32, vp, vp, vp, sz, vp]; lib.sd_spinehead_fill_holes.restype = i32
+    lib.sd_spinehead_peaks.argtypes = [vp, vp, i32, i32, i32, vp, sz, vp, vp, sz, vp]; lib.sd_spinehead_peaks.restype = i32
+    lib.sd_spinehead_box_vertices_temp_bytes.argtypes = [sz, sz]; lib.sd_spinehead_box_vertices_temp_bytes.restype = sz
+    lib.sd_spinehead_box_vertices.argtypes = [vp, i32, vp, sz, vp, sz, i32p, i32, vp, vp, vp, sz, vp, sz, vp]
+    lib.sd_spinehead_box_vertices.restype = i32
+    lib.sd_spinehead_queries.argtypes = [vp, vp, sz, sz, sz, f64p, vp, vp, vp]; lib.sd_spinehead_queries.restype = i32
+    lib.sd_spinehead_markers.argtypes = [vp, vp, vp, sz, i32, i32, i32, vp, vp]; lib.sd_spinehead_markers.restype = i32
+    lib.sd_spinehead_select.argtypes = [vp, i32, i32, i32, i64p, f64p, vp, vp, vp, sz, vp]; lib.sd_spinehead_select.restype = i32
     _lib = lib
     return lib
 

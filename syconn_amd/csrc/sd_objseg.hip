@@ -1613,6 +1613,29 @@ int sd_marker_flood(const int32_t* d2_dev, const int32_t* markers_dev, const uin
     return launch_status("sd_marker_flood: launch failed");
 }
 
+// The whole-volume form of the distance transform above on its own (k_edt_z / k_edt_axis without the component filter): squared exact
+// Euclidean distances with pitch (1, 1, 1) of a uint8 mask, 0 in the background.  Scratch: the plain layout (mask bits + one int32 volume).
+int sd_edt_squared(const uint8_t* mask_dev, int X, int Y, int Z, int32_t* d2_dev, void* ws, size_t ws_bytes, void* stream) {
+    if (!mask_dev || !d2_dev || !ws || X <= 0 || Y <= 0 || Z <= 0) return sd_fail_msg(SD_ERR_INVALID, "sd_edt_squared: bad argument");
+    if ((size_t)X * Y * Z >= (1ull << 31)) return sd_fail_msg(SD_ERR_INVALID, "sd_edt_squared: volume must have < 2^31 voxels");
+    if (X > 18000 || Y > 18000 || Z > 18000) return sd_fail_msg(SD_ERR_INVALID, "sd_edt_squared: extent out of range");
+    const WsLayout w = ws_layout(X, Y, Z, 0);
+    if (ws_bytes < w.total) return sd_fail_msg(SD_ERR_NOMEM, "sd_edt_squared: workspace too small");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    char* const wb = reinterpret_cast<char*>(ws);
+    uint32_t* M = reinterpret_cast<uint32_t*>(wb + w.a);
+    int* tmp = reinterpret_cast<int*>(wb + w.rank);
+    const Dom d = make_dom(X, Y, Z, 0);
+    const size_t pwords = (size_t)d.PX * d.PY * d.PZW, nvox = (size_t)X * Y * Z;
+    hipLaunchKernelGGL(k_threshold_bits, dim3(grid_for(pwords, 8192)), dim3(256), 0, s, mask_dev, 1, d, M);
+    (void)hipMemsetAsync(d2_dev, 0, nvox * sizeof(int), s);      // the passes write foreground voxels only
+    (void)hipMemsetAsync(tmp, 0, nvox * sizeof(int), s);
+    hipLaunchKernelGGL(k_edt_z, dim3(grid_for(pwords, 8192)), dim3(256), 0, s, M, d, 1, d2_dev, (const int*)nullptr, (const int*)nullptr, (const int*)nullptr);
+    hipLaunchKernelGGL(k_edt_axis, dim3(grid_for(nvox, 8192)), dim3(256), 0, s, M, d2_dev, tmp, d, 1, 1, (const int*)nullptr, (const int*)nullptr, (const int*)nullptr);
+    hipLaunchKernelGGL(k_edt_axis, dim3(grid_for(nvox, 8192)), dim3(256), 0, s, M, tmp, d2_dev, d, 2, 1, (const int*)nullptr, (const int*)nullptr, (const int*)nullptr);
+    return launch_status("sd_edt_squared: launch failed");
+}
+
 // ---- Gaussian pre-smoothing of a probability map + threshold (object_extraction_steps.py:296-297, 316-317) -------------------
 // vigra.gaussianSmoothing restated from its published algorithm (vigra is absent from the reference tree and this image: parity
 // UNPINNED): separable, axes in memory order (x, then y, then z), per axis a window of radius int(3 sigma + 0.5) (at least 1)

@@ -1183,3 +1183,116 @@ def export_matrix(syn_ssv, props: SynSsvProperties, syn_prob, mesh_area, dest_fo
         os.rename(dest_name + '.csv', '{}_{}.csv'.format(dest_name, st))
     np.savetxt(dest_name + '.csv', table, delimiter='\t', header=conn_mat_header(m_emb))
     return dest_name + '.csv'
+
+
+def calculate_spinehead_volume(cells: CellTable, sv_begin, sv_ids, syn_ids, syn_rep_coords, syn_cells, seg, scaling=None, ctx_vol=(200, 200, 100),
+                               k=None, ignore_labels=None, semseg_key: str = 'spiness', ax_key=None, ds_vertices=None, device=None,
+                               batch: int = 8, max_peaks=None):
+    """``extract_spinehead_volume_mesh`` (reps/super_segmentation_helper.py:2068-2198, run per cell by ``exec_syns.run_spinehead_volume_calc``)
+    for every cell of a ``CellTable`` at once, tables in memory.  Cell c owns the supervoxels ``sv_ids[sv_begin[c]:sv_begin[c + 1]]``;
+    synapse i (`syn_ids` uint64, `syn_rep_coords` (n, 3) voxels) touches the cells ``syn_cells[i]`` (n, 2): it is one of the ``syn_ssv`` of
+    each of them that is in the table (ids that are not are skipped: the reference runs per cell).  `seg`: the cell segmentation, a
+    ``KnossosDataset`` (windows are read in spatial buckets kept on the device) or ``(volume (x, y, z) of 64-bit ids, origin)`` as an array
+    or device tensor, zeros outside.
+
+    Per cell: the synapses whose spine label (vote of the `k` nearest mesh vertices, ``semseg_for_coords``) is 1 and whose nearest skeleton
+    node carries `ax_key` == 0 are spine-head synapses (:2114-2122); each gets a ``2 * ctx_vol`` window (``extraction/spinehead.py``).
+    A cell without skeleton nodes or without `ax_key` has no spine-head synapse (its compartment reads -1, as for the partner properties;
+    the reference fails inside ``attr_for_coords`` there).  Negative `semseg_key` labels raise: they cannot seed the flood (the reference
+    would write them into its float marker volume).
+    -> ``(sh_begin (cells + 1) int64, ids uint64, volumes float64 um^3)``: the triple ``CellTable(spinehead_vol=...)`` takes, per cell in
+    the order of the synapses.  A window without a mesh vertex in its box gives no entry, one whose flood leaves no head voxel 0.0.
+
+    ValueError (before any launch): bad shapes, a cell with synapses but without `semseg_key` labels (the reference's message); after the
+    batch: a window without any voxel of the cell (the reference's message).  Defaults from ``config['scaling']``,
+    ``config['spines']['semseg2coords_spines']`` and ``config['compartments']``.  k <= 64.  No CPU fallback."""
+    from .. import global_params
+    from . import spinehead as SH
+    cfg = global_params.config
+    if not isinstance(cells, CellTable):
+        raise TypeError('cells must be a CellTable')
+    sp = cfg['spines']['semseg2coords_spines']
+    k = sp['k'] if k is None else k
+    ds_vertices = sp['ds_vertices'] if ds_vertices is None else ds_vertices
+    ignore_labels = list(sp['ignore_labels'] if ignore_labels is None else ignore_labels)
+    if ax_key is None:
+        comp = cfg['compartments']
+        ax_key = '{}_avg{}'.format(comp['view_properties_semsegax']['semseg_key'], comp['dist_axoness_averaging'])
+    for name, v in (('k', k), ('ds_vertices', ds_vertices), ('batch', batch)):
+        if isinstance(v, bool) or int(v) != v or int(v) < 1:
+            raise ValueError(f'{name} must be an integer >= 1, got {v!r}')
+    if int(k) > L.SD_SYN_PROPS_MAX_K:
+        raise ValueError(f'k = {k}: at most {L.SD_SYN_PROPS_MAX_K} neighbours per query')
+    sc, ds = SH.check_scaling(cfg['scaling'] if scaling is None else scaling)
+    ctx = np.array(ctx_vol)
+    if ctx.shape != (3,) or ctx.dtype.kind not in 'iu' or np.any(ctx < 1):
+        raise ValueError(f'ctx_vol must be three positive integers, got {ctx_vol}')
+    n_cells = len(cells)
+    sv_begin = np.ascontiguousarray(sv_begin, dtype=np.int64).reshape(-1)
+    sv_ids = np.ascontiguousarray(sv_ids, dtype=np.uint64).reshape(-1)
+    _check_offsets('calculate_spinehead_volume: sv_begin', sv_begin, n_cells, len(sv_ids))
+    syn_ids = np.ascontiguousarray(syn_ids, dtype=np.uint64).reshape(-1)
+    n = len(syn_ids)
+    rep = np.ascontiguousarray(syn_rep_coords, dtype=np.int64).reshape(-1, 3)
+    syn_cells = np.ascontiguousarray(syn_cells, dtype=np.uint64).reshape(-1, 2)
+    if len(rep) != n or len(syn_cells) != n:
+        raise ValueError(f'{n} syn_ids, {len(rep)} syn_rep_coords, {len(syn_cells)} syn_cells')
+    if n and rep.min() < 0:
+        raise ValueError('calculate_spinehead_volume: a representative coordinate is negative')
+    if not hasattr(seg, 'load_seg') and not (isinstance(seg, (tuple, list)) and len(seg) == 2 and len(np.asarray(seg[1]).reshape(-1)) == 3):
+        raise ValueError('seg must be a KnossosDataset or (volume, origin)')
+    # (cell row, synapse) pairs: a synapse is a syn_ssv of each of its cells, once
+    order = np.argsort(cells.ids, kind='stable')
+    side = syn_cells.reshape(-1)
+    at = np.minimum(np.searchsorted(cells.ids[order], side), max(n_cells - 1, 0))
+    row = order[at] if n_cells else np.zeros(len(side), np.int64)
+    known = (cells.ids[row] == side) if n_cells else np.zeros(len(side), bool)
+    known[1::2] &= ~(known[0::2] & (syn_cells[:, 0] == syn_cells[:, 1]))
+    pair_syn, pair_row = np.flatnonzero(known) // 2, row[known]
+    used = np.zeros(n_cells, bool)
+    used[pair_row] = True
+    n_vert = np.diff(cells.vert_begin)
+    for c in np.flatnonzero(used):
+        if semseg_key not in cells.vertex_labels or n_vert[c] == 0:
+            raise ValueError(f'"{semseg_key}" not available in skeleton of SSO {int(cells.ids[c])}.')
+        if sv_begin[c + 1] == sv_begin[c]:
+            raise ValueError(f'cell {int(cells.ids[c])} has no supervoxel')
+    if n and len(cells.vertex_labels.get(semseg_key, ())) and cells.vertex_labels[semseg_key].min() < 0:
+        raise ValueError(f'negative "{semseg_key}" vertex labels cannot seed the flood')
+    sh_ids, sh_vol, sh_count = [], [], np.zeros(n_cells, np.int64)
+    if len(pair_syn):
+        # the spine-head filter (:2114-2122) through the two segmented_knn paths of collect_properties_from_ssv_partners
+        scale = np.asarray(sc, np.float32).astype(np.float64)
+        q_xyz = rep[pair_syn].astype(np.float64) * scale
+        verts, lab, begin = spine_vertices(cells, used, semseg_key, ds_vertices, ignore_labels)
+        empty = np.flatnonzero(used & (np.diff(begin) == 0))
+        if len(empty):
+            raise ValueError(f'every mesh vertex of cell {int(cells.ids[empty[0]])} carries an ignored label: no vertex to vote')
+        curr_sp = segmented_knn(verts, begin, lab, pair_row, q_xyz, int(k), device)
+        curr_ax = np.full(len(pair_syn), -1, np.int64)
+        has_ax = ax_key in cells.node_attrs
+        sk = np.flatnonzero((np.diff(cells.node_begin) > 0)[pair_row] & (cells.node_attr_present[ax_key][pair_row] if has_ax else False))
+        if len(sk):
+            nb = np.concatenate(([0], np.cumsum(np.where(used, np.diff(cells.node_begin), 0)))).astype(np.int64)
+            node_keep = np.repeat(used, np.diff(cells.node_begin))
+            nearest = segmented_knn(cells.nodes[node_keep] * scale, nb, None, pair_row[sk], q_xyz[sk], 1, device)
+            curr_ax[sk] = cells.node_attrs[ax_key][np.flatnonzero(node_keep)[nearest]]
+        head = (curr_sp == 1) & (curr_ax == 0)
+        runner = None                                                # every cell has the same window shape: one set of device buffers
+        for c in np.flatnonzero(used):
+            sel = np.flatnonzero(head & (pair_row == c))
+            if not len(sel):
+                continue
+            v = cells.vertices[cells.vert_begin[c]:cells.vert_begin[c + 1]] / sc          # sso.mesh[1].reshape(-1, 3) / scaling (:2106)
+            sem = cells.vertex_labels[semseg_key][cells.vert_begin[c]:cells.vert_begin[c + 1]]
+            keep = ~np.isin(sem, np.asarray(ignore_labels, np.int64))
+            if runner is None:
+                runner = SH.WindowRunner([len(SH.zoom_source_table(2 * int(ctx[a]), ds[a])) for a in range(3)], int(batch), max_peaks, device)
+            res = SH.spinehead_windows(seg, sv_ids[sv_begin[c]:sv_begin[c + 1]], rep[pair_syn[sel]], v[keep], sem[keep], sc, ctx, int(k), runner.dev,
+                                       int(batch), max_peaks, syn_ids[pair_syn[sel]], runner=runner)
+            entry = res[:, 5] > 0
+            sh_ids.append(syn_ids[pair_syn[sel]][entry])
+            sh_vol.append(np.asarray(SH.head_volume(res[entry, 2], sc, ds), np.float64))
+            sh_count[c] = int(entry.sum())
+    return (np.concatenate(([0], np.cumsum(sh_count))).astype(np.int64), np.concatenate(sh_ids) if sh_ids else np.zeros(0, np.uint64),
+            np.concatenate(sh_vol) if sh_vol else np.zeros(0, np.float64))

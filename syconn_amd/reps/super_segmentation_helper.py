@@ -66,3 +66,40 @@ def map_myelin2coords(coords: np.ndarray, cube_edge_avg: np.ndarray = np.array([
         res = box_majority_device(vol_dev, org, edge[::-1], thresh_proba, thresh_majority)
         preds[ix] = res.cpu().numpy()
     return preds
+
+
+def extract_spinehead_volume_mesh(sso, ctx_vol=(200, 200, 100)):
+    """Drop-in for ``extract_spinehead_volume_mesh`` (/root/reference/syconn/reps/super_segmentation_helper.py:2068-2198): fills
+    ``sso.attr_dict['spinehead_vol']`` = {syn_ssv id: spine head volume in um^3} for one cell.  Reads what the reference reads of a
+    (duck-typed) ``sso``: ``attr_dict`` / ``load_attr_dict``, ``scaling``, ``id``, ``label_dict('vertex')['spiness']``, ``sv_ids``,
+    ``syn_ssv`` (``rep_coord``, ``id``), ``mesh[1]``, ``skeleton`` (``nodes`` and the averaged axoness key, what ``attr_for_coords``
+    looks up), ``config`` (``['spines']['semseg2coords_spines']``, ``['compartments']``, ``kd_seg_path``).  The windows run on the
+    device (``cs_processing_steps.calculate_spinehead_volume``); no CPU fallback."""
+    from ..extraction.cs_processing_steps import CellTable, calculate_spinehead_volume
+    if len(sso.attr_dict) == 0:
+        sso.load_attr_dict()
+    sso.attr_dict['spinehead_vol'] = {}
+    labels = sso.label_dict('vertex')
+    if 'spiness' not in labels:
+        raise ValueError(f'"spiness" not available in skeleton of SSO {sso.id}.')
+    syns = list(sso.syn_ssv)
+    if len(syns) == 0:
+        return
+    cfg = sso.config
+    sp = cfg['spines']['semseg2coords_spines']
+    ax_key = "{}_avg{}".format(cfg['compartments']['view_properties_semsegax']['semseg_key'], cfg['compartments']['dist_axoness_averaging'])
+    skel = getattr(sso, 'skeleton', None) or {}
+    nodes = np.asarray(skel.get('nodes', np.zeros((0, 3)))).reshape(-1, 3)
+    attrs = {ax_key: np.asarray(skel[ax_key]).reshape(-1)} if ax_key in skel and len(nodes) else {}
+    verts = np.asarray(sso.mesh[1]).reshape(-1, 3)
+    cells = CellTable([sso.id], verts, [0, len(verts)], {'spiness': labels['spiness']}, nodes, [0, len(nodes)], attrs)
+    sv = np.asarray(sso.sv_ids, dtype=np.uint64).reshape(-1)
+    kd_path = cfg.kd_seg_path
+    kd = kd_factory(kd_path) if isinstance(kd_path, (str, os.PathLike)) else kd_path
+    syn_ids = np.array([syn.id for syn in syns], np.uint64)
+    rep = np.array([syn.rep_coord for syn in syns]).reshape(-1, 3)
+    partners = np.stack([np.full(len(syns), sso.id, np.uint64), np.full(len(syns), sso.id, np.uint64)], 1)
+    _, ids, vols = calculate_spinehead_volume(cells, [0, len(sv)], sv, syn_ids, rep, partners, kd, scaling=sso.scaling, ctx_vol=ctx_vol, k=sp['k'],
+                                              ignore_labels=sp['ignore_labels'], ds_vertices=sp['ds_vertices'], ax_key=ax_key)
+    for i, v in zip(ids.tolist(), vols.tolist()):
+        sso.attr_dict['spinehead_vol'][i] = v
