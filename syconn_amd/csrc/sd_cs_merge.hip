@@ -1,5 +1,5 @@
 // Dataset-wide merge of contact sites and synapses on the device: the record form of what
-// /root/reference/syconn/extraction/cs_extraction_steps.py does with Python dictionaries -- the running merges of
+// extraction/cs_extraction_steps.py does with Python dictionaries -- the running merges of
 // _contact_site_extraction_thread (:484-492, merge_prop_dicts / merge_type_dicts / merge_voxel_dicts per chunk), the pickles its
 // workers write, _write_props_collect_helper (:631-673, which loads them again per storage bucket and worker) and the merging,
 // joining and filtering half of _write_props_to_syn_thread (:544-623).  As in sd_propmerge.hip nothing per object exists on the host
@@ -19,6 +19,7 @@
 // inside every segment whatever order the records of one chunk were appended in.
 #include "../../include/syconn_dense.h"
 #include "sd_sortseg.h"
+#include "sd_pointtiles.h"
 
 namespace {
 
@@ -65,16 +66,6 @@ __global__ __launch_bounds__(256) void k_csm_vox_append(const int64_t* __restric
 }
 __global__ void k_csm_vox_advance(u64* cursors, u64 n_rows) { cursors[2] += n_rows; }
 
-// first index in the ascending ids[0 .. n) that holds `key`, or -1
-__device__ __forceinline__ long find_id(const u64* ids, u64 n, u64 key) {
-    u64 lo = 0, hi = n;
-    while (lo < hi) {
-        const u64 mid = lo + (hi - lo) / 2;
-        if (ids[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return (lo < n && ids[lo] == key) ? (long)lo : -1;
-}
-
 // one thread per segment: does the id stay?  Its merged size must reach min_vx; with a join table (the kept cs objects) the id must
 // be in it, and its size there is kept for the output.
 __global__ __launch_bounds__(256) void k_csm_keep(const u64* skey, const u32* perm, const u32* head, const u32* seg, const u64* sizes, u64 n,
@@ -89,7 +80,7 @@ __global__ __launch_bounds__(256) void k_csm_keep(const u64* skey, const u32* pe
         bool keep = sum >= min_vx;
         u64 jsz = 0;
         if (join) {
-            const long at = find_id(join_ids, n_join, k);
+            const long at = find_exact(join_ids, n_join, k);
             if (at < 0) keep = false; else jsz = join_sizes[at];
         }
         keepseg[s] = keep ? 1u : 0u; joined[s] = jsz;

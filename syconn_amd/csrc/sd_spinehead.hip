@@ -1,5 +1,5 @@
 // Spine head volumes on the device: the per-window glue of extract_spinehead_volume_mesh
-// (/root/reference/syconn/reps/super_segmentation_helper.py:2068-2198) around the entries that exist already.  Per synapse window:
+// (reps/super_segmentation_helper.py:2068-2198) around the entries that exist already.  Per synapse window:
 //     :2135-2141  kd.load_seg + ndimage.zoom(order=0) + relabel_vol_nonexist2zero / (seg == sv)   -> sd_spinehead_window_mask
 //     :2143       ndimage.binary_fill_holes                                                       -> sd_spinehead_fill_holes
 //     :2161       ndimage.distance_transform_edt                                                  -> sd_edt_squared (sd_objseg.hip)
@@ -281,24 +281,23 @@ __global__ __launch_bounds__(64) void k_shs_final(const int* __restrict__ cnt, c
 
 // scratch of this file's entries: the labelling scratch of sd_objseg.hip, one uint8 and two int32 volumes, three id tables (a volume of
 // n voxels has at most n / 2 + 1 six-connected components), scalars and the rocPRIM scan
-struct ShLayout { size_t cc, cc_bytes, u8, va, vb, tab[3], scal, prim, prim_bytes, total, T; };
-ShLayout sh_layout(int X, int Y, int Z) {
-    ShLayout l{};
+struct ShScalars { int i[16]; unsigned long long sel[24]; };      // the 256-byte scalar block: nb_obj / the peaks' scal, then sel
+static_assert(sizeof(ShScalars) == 256, "the scalar block keeps its size");
+// flag, pos: the two int32 volumes as the peaks' scan sees them; lab: the first of them as labels (fill_holes, select)
+struct ShLayout { char* cc; size_t cc_bytes, T; uint8_t* u8; uint32_t *flag, *pos; int *lab, *tab[3]; ShScalars* scal; PrimScratch prim; };
+size_t layout(ShLayout& l, void* base, int X, int Y, int Z) {
+    ScratchAlloc a(base);
     const size_t nvox = (size_t)X * Y * Z;
     l.T = nvox / 2 + 1026;
     l.cc_bytes = sd_objseg_workspace_bytes(X, Y, Z, 0);
-    size_t cur = 0;
-    l.cc = cur; cur += up256(l.cc_bytes);
-    l.u8 = cur; cur += up256(nvox);
-    l.va = cur; cur += up256(nvox * 4);
-    l.vb = cur; cur += up256(nvox * 4);
-    for (int i = 0; i < 3; ++i) { l.tab[i] = cur; cur += up256(l.T * 4); }
-    l.scal = cur; cur += 256;
-    ScratchAlloc a(nullptr);
-    const PrimScratch p = take_prim(a, nvox);
-    l.prim = cur; l.prim_bytes = p.bytes; cur += p.bytes;
-    l.total = cur;
-    return l;
+    l.cc = a.take<char>(l.cc_bytes);
+    l.u8 = a.take<uint8_t>(nvox);
+    a.take_into(nvox, l.flag, l.pos);
+    l.lab = reinterpret_cast<int*>(l.flag);
+    a.take_into(l.T, l.tab[0], l.tab[1], l.tab[2]);
+    l.scal = a.take<ShScalars>(1);
+    l.prim = take_prim(a, nvox);
+    return a.used;
 }
 bool bad_dims(int X, int Y, int Z) { return X <= 0 || Y <= 0 || Z <= 0 || (size_t)X * Y * Z >= (1ull << 31); }
 
@@ -319,7 +318,8 @@ extern "C" {
 
 size_t sd_spinehead_workspace_bytes(int X, int Y, int Z) {
     if (bad_dims(X, Y, Z)) return 0;
-    return std::max(sh_layout(X, Y, Z).total, sd_objseg_watershed_workspace_bytes(X, Y, Z, 0));
+    ShLayout l;
+    return std::max(layout(l, nullptr, X, Y, Z), sd_objseg_watershed_workspace_bytes(X, Y, Z, 0));
 }
 
 int sd_spinehead_window_mask(const uint64_t* seg_dev, int VX, int VY, int VZ, const int64_t* vol_origin_xyz, const int64_t* win_offset_xyz,
@@ -338,17 +338,14 @@ int sd_spinehead_window_mask(const uint64_t* seg_dev, int VX, int VY, int VZ, co
 int sd_spinehead_fill_holes(const uint8_t* mask_dev, int X, int Y, int Z, uint8_t* filled_dev, int32_t* n_filled_dev, void* ws, size_t ws_bytes,
                             void* stream) {
     if (!mask_dev || !filled_dev || !n_filled_dev || !ws || bad_dims(X, Y, Z)) return sd_fail_msg(SD_ERR_INVALID, "sd_spinehead_fill_holes: bad argument");
-    const ShLayout l = sh_layout(X, Y, Z);
-    if (ws_bytes < l.total) return sd_fail_msg(SD_ERR_NOMEM, "sd_spinehead_fill_holes: workspace too small");
+    ShLayout l;
+    if (ws_bytes < layout(l, ws, X, Y, Z)) return sd_fail_msg(SD_ERR_NOMEM, "sd_spinehead_fill_holes: workspace too small");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    char* const wb = reinterpret_cast<char*>(ws);
-    uint8_t* inv = reinterpret_cast<uint8_t*>(wb + l.u8);
-    int* L = reinterpret_cast<int*>(wb + l.va);
-    int* open = reinterpret_cast<int*>(wb + l.tab[0]);
-    int* scal = reinterpret_cast<int*>(wb + l.scal);
+    uint8_t* inv = l.u8;
+    int *L = l.lab, *open = l.tab[0], *scal = l.scal->i;
     const size_t nvox = (size_t)X * Y * Z;
     hipLaunchKernelGGL(k_sh_invert, dim3(grid_for(nvox, VG)), dim3(256), 0, s, mask_dev, nvox, inv);
-    const int rc = sd_object_segmentation(inv, X, Y, Z, 0.0, nullptr, nullptr, 0, nullptr, 0, 0, 0, L, scal, nullptr, wb + l.cc, l.cc_bytes, stream);
+    const int rc = sd_object_segmentation(inv, X, Y, Z, 0.0, nullptr, nullptr, 0, nullptr, 0, 0, 0, L, scal, nullptr, l.cc, l.cc_bytes, stream);
     if (rc != SD_OK) return rc;
     hipLaunchKernelGGL(k_sh_zero, dim3(grid_for(l.T, TG)), dim3(256), 0, s, open, l.T);
     hipLaunchKernelGGL(k_sh_zero, dim3(1), dim3(256), 0, s, n_filled_dev, (size_t)1);
@@ -361,20 +358,17 @@ int sd_spinehead_peaks(const uint8_t* mask_dev, const int32_t* d2_dev, int X, in
                        void* ws, size_t ws_bytes, void* stream) {
     if (!mask_dev || !d2_dev || !peaks_dev || !n_peaks_dev || !ws || max_peaks < 1 || max_peaks >= (1ull << 31) || bad_dims(X, Y, Z))
         return sd_fail_msg(SD_ERR_INVALID, "sd_spinehead_peaks: bad argument");
-    const ShLayout l = sh_layout(X, Y, Z);
-    if (ws_bytes < l.total) return sd_fail_msg(SD_ERR_NOMEM, "sd_spinehead_peaks: workspace too small");
+    ShLayout l;
+    if (ws_bytes < layout(l, ws, X, Y, Z)) return sd_fail_msg(SD_ERR_NOMEM, "sd_spinehead_peaks: workspace too small");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    char* const wb = reinterpret_cast<char*>(ws);
-    uint32_t* flag = reinterpret_cast<uint32_t*>(wb + l.va);
-    uint32_t* pos = reinterpret_cast<uint32_t*>(wb + l.vb);
-    int* scal = reinterpret_cast<int*>(wb + l.scal);
+    uint32_t *flag = l.flag, *pos = l.pos;
+    int* scal = l.scal->i;
     const size_t nvox = (size_t)X * Y * Z;
     const int g = grid_for(nvox, VG);
     hipLaunchKernelGGL(k_shp_init, dim3(1), dim3(64), 0, s, scal);
     hipLaunchKernelGGL(k_shp_bbox, dim3(g), dim3(256), 0, s, mask_dev, X, Y, Z, scal);
     hipLaunchKernelGGL(k_shp_flags, dim3(g), dim3(256), 0, s, mask_dev, d2_dev, X, Y, Z, scal, flag);
-    const PrimScratch prim{wb + l.prim, l.prim_bytes};
-    const int rc = scan_u32("sd_spinehead_peaks", prim, flag, pos, nvox, s);
+    const int rc = scan_u32("sd_spinehead_peaks", l.prim, flag, pos, nvox, s);
     if (rc != SD_OK) return rc;
     hipLaunchKernelGGL(k_shp_compact, dim3(g), dim3(256), 0, s, flag, pos, X, Y, Z, scal, peaks_dev, (long long)max_peaks, n_peaks_dev);
     return launch_status("sd_spinehead_peaks: launch failed");
@@ -441,15 +435,13 @@ int sd_spinehead_markers(const int32_t* peaks_dev, const int32_t* n_peaks_dev, c
 int sd_spinehead_select(const int32_t* flood_dev, int X, int Y, int Z, const int64_t* c_xyz, const double* scaling_xyz, int32_t* objects_dev,
                         int32_t* result_dev, void* ws, size_t ws_bytes, void* stream) {
     if (!flood_dev || !c_xyz || !scaling_xyz || !result_dev || !ws || bad_dims(X, Y, Z)) return sd_fail_msg(SD_ERR_INVALID, "sd_spinehead_select: bad argument");
-    const ShLayout l = sh_layout(X, Y, Z);
-    if (ws_bytes < l.total) return sd_fail_msg(SD_ERR_NOMEM, "sd_spinehead_select: workspace too small");
+    ShLayout l;
+    if (ws_bytes < layout(l, ws, X, Y, Z)) return sd_fail_msg(SD_ERR_NOMEM, "sd_spinehead_select: workspace too small");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    char* const wb = reinterpret_cast<char*>(ws);
-    uint8_t* head = reinterpret_cast<uint8_t*>(wb + l.u8);
-    int* L = objects_dev ? objects_dev : reinterpret_cast<int*>(wb + l.va);
-    int *cnt = reinterpret_cast<int*>(wb + l.tab[0]), *cbox = reinterpret_cast<int*>(wb + l.tab[1]);
-    int* nb = reinterpret_cast<int*>(wb + l.scal);
-    unsigned long long* sel = reinterpret_cast<unsigned long long*>(wb + l.scal + 64);
+    uint8_t* head = l.u8;
+    int* L = objects_dev ? objects_dev : l.lab;
+    int *cnt = l.tab[0], *cbox = l.tab[1], *nb = l.scal->i;
+    unsigned long long* sel = l.scal->sel;
     const size_t nvox = (size_t)X * Y * Z;
     const int g = grid_for(nvox, VG);
     const int ext[3] = {X, Y, Z};
@@ -468,7 +460,7 @@ int sd_spinehead_select(const int32_t* flood_dev, int X, int Y, int Z, const int
         sc.v[a] = scaling_xyz[a];
     }
     hipLaunchKernelGGL(k_shs_head, dim3(g), dim3(256), 0, s, flood_dev, nvox, head);
-    const int rc = sd_object_segmentation(head, X, Y, Z, 0.0, nullptr, nullptr, 0, nullptr, 0, 0, 0, L, nb, nullptr, wb + l.cc, l.cc_bytes, stream);
+    const int rc = sd_object_segmentation(head, X, Y, Z, 0.0, nullptr, nullptr, 0, nullptr, 0, 0, 0, L, nb, nullptr, l.cc, l.cc_bytes, stream);
     if (rc != SD_OK) return rc;
     hipLaunchKernelGGL(k_sh_zero, dim3(grid_for(l.T, TG)), dim3(256), 0, s, cnt, l.T);
     hipLaunchKernelGGL(k_sh_zero, dim3(grid_for(l.T, TG)), dim3(256), 0, s, cbox, l.T);

@@ -8,14 +8,13 @@
 //            coordinate).  The neighbours of a query are the min(k, points of the cell) points of ITS cell with the smallest
 //            (d^2, original index), d^2 = ((dx dx) + dy dy) + dz dz in float64 with nothing fused; the vote is the label with the
 //            highest count among them, on equal counts the one whose first occurrence is nearest (Counter.most_common(1)).
-//     build  one wave per cell: the cell's box.  Per point a key (cell, 30-bit Morton code of the position inside the cell's box),
-//            a stable radix sort (sd_sortseg.h), the points as float64 in sorted order, tiles of 64 with one box each (tile t of
-//            cell c is slot begin[c] / 64 + c + t).
+//     build  one wave per cell: the cell's box.  The tile index of sd_pointtiles.h with the cells as segments and, per point, the
+//            30-bit Morton code of its position inside the cell's box as the spatial key.
 //     query  one wave per query.  Lane i holds entry i of the candidate list, ascending by (d^2, index); the k-th best is lane k - 1.
 //            The list is seeded from the tile whose box is nearest; then the lanes test 64 tile boxes at a time, and a tile is
-//            skipped when its box distance^2 is strictly above the k-th best (a tie on d^2 is still decided by the index).  The box
-//            distance is summed like d^2 itself, so rounding cannot lift it above the d^2 of a point inside the box.  (d^2, index) is
-//            a total order: the result depends neither on the tiling nor on the visit order.
+//            skipped when its box distance^2 (box_dist2: never above the d^2 of a point inside) is strictly above the k-th best (a
+//            tie on d^2 is still decided by the index).  (d^2, index) is a total order: the result depends neither on the tiling nor
+//            on the visit order.
 //   forest   one thread per row: the row cast to float32, in every tree left iff x[feature] <= threshold (the float32 widened to
 //            float64), the leaf's class fractions added in tree order in float64, divided by the number of trees: sklearn's
 //            predict_proba with n_jobs = 1.
@@ -24,38 +23,16 @@
 // writes, no inline assembly.
 #include "../../include/syconn_dense.h"
 #include "sd_sortseg.h"
-#include <cmath>
+#include "sd_pointtiles.h"
 
 namespace {
 
-constexpr int KNN_TILE = 64;                                 // points per tile = lanes of a wave
 constexpr int KNN_BITS = 10;                                 // key bits per axis
 constexpr u32 NO_IX = 0xffffffffu;
-static_assert(SD_SYN_PROPS_MAX_K == 64, "one list entry per lane");
+static_assert(SD_SYN_PROPS_MAX_K == 64 && TILE == 64, "one list entry and one point of a tile per lane");
 
-// first index in [0, n) whose element is > key (n if none); a[] ascending
-__device__ __forceinline__ u64 upper_bound(const u64* a, u64 n, u64 key) {
-    u64 lo = 0, hi = n;
-    while (lo < hi) {
-        const u64 mid = lo + (hi - lo) / 2;
-        if (a[mid] <= key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
 __device__ __forceinline__ double ld_coord(const void* pts, int f32, u64 i) {
     return f32 ? (double)reinterpret_cast<const float*>(pts)[i] : reinterpret_cast<const double*>(pts)[i];
-}
-__device__ __forceinline__ double sq_dist(const double* p, const double* q) {
-#pragma clang fp contract(off)                              // ((dx dx) + dy dy) + dz dz, no fused multiply-add: cKDTree's own sum
-    const double dx = p[0] - q[0], dy = p[1] - q[1], dz = p[2] - q[2];
-    return ((dx * dx) + dy * dy) + dz * dz;
-}
-// the same sum over the per-axis gaps to the box (bx = min | max): never above sq_dist of a point inside the box, rounding included
-__device__ __forceinline__ double box_dist2(const double* p, const double* bx) {
-#pragma clang fp contract(off)
-    const double dx = fmax(0.0, fmax(bx[0] - p[0], p[0] - bx[3])), dy = fmax(0.0, fmax(bx[1] - p[1], p[1] - bx[4])),
-                 dz = fmax(0.0, fmax(bx[2] - p[2], p[2] - bx[5]));
-    return ((dx * dx) + dy * dy) + dz * dz;
 }
 __device__ __forceinline__ u64 spread3(u32 v) {              // bit i of v -> bit 3 i
     u64 r = 0;
@@ -78,9 +55,7 @@ __global__ __launch_bounds__(256) void k_knn_cell_box(const void* __restrict__ p
             for (u64 i = b0 + lane; i < b1; i += 64)
 #pragma unroll
                 for (int a = 0; a < 3; ++a) { const double v = ld_coord(pts, f32, 3 * i + a); lo[a] = fmin(lo[a], v); hi[a] = fmax(hi[a], v); }
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-            for (int msk = 32; msk; msk >>= 1) { lo[a] = fmin(lo[a], __shfl_xor(lo[a], msk)); hi[a] = fmax(hi[a], __shfl_xor(hi[a], msk)); }
+        wave_minmax3(lo, hi);
         if (lane == 0) {
             if (bad) counts[7] = 1;
             const double ext = fmax(hi[0] - lo[0], fmax(hi[1] - lo[1], hi[2] - lo[2]));
@@ -93,9 +68,7 @@ __global__ __launch_bounds__(256) void k_knn_cell_box(const void* __restrict__ p
 __global__ __launch_bounds__(256) void k_knn_keys(const void* __restrict__ pts, int f32, const u64* __restrict__ begin, const double* __restrict__ cbox,
                                                   u64 n_cells, u64 n_pts, u64* key) {
     for (u64 j = (u64)blockIdx.x * 256 + threadIdx.x; j < n_pts; j += (u64)gridDim.x * 256) {
-        u64 c = upper_bound(begin, n_cells + 1, j);
-        c = c ? c - 1 : 0;
-        if (c >= n_cells) c = n_cells - 1;
+        const u64 c = segment_of(begin, n_cells, j);
         const double g = cbox[4 * c + 3];
         u64 k = 0;
 #pragma unroll
@@ -113,29 +86,6 @@ __global__ __launch_bounds__(256) void k_knn_place(const void* __restrict__ pts,
         if (j >= n_pts) j = n_pts - 1;
 #pragma unroll
         for (int a = 0; a < 3; ++a) spts[3 * i + a] = ld_coord(pts, f32, 3 * j + a);                    // float32 widens exactly
-    }
-}
-// one wave per cell: the box of every tile of 64 sorted points
-__global__ __launch_bounds__(256) void k_knn_tiles(const double* __restrict__ spts, const u64* __restrict__ begin, u64 n_cells, u64 n_pts, u64 n_slots,
-                                                   double* tbox) {
-    const int lane = threadIdx.x & 63;
-    const u64 wave = ((u64)blockIdx.x * 256 + threadIdx.x) >> 6, n_waves = ((u64)gridDim.x * 256) >> 6;
-    for (u64 c = wave; c < n_cells; c += n_waves) {
-        const u64 i1 = begin[c + 1] < n_pts ? begin[c + 1] : n_pts, i0 = begin[c] < i1 ? begin[c] : i1;
-        u64 slot = i0 / KNN_TILE + c;
-        for (u64 t0 = i0; t0 < i1; t0 += KNN_TILE, ++slot) {
-            const u64 i = t0 + lane;
-            double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-            if (i < i1)
-#pragma unroll
-                for (int a = 0; a < 3; ++a) lo[a] = hi[a] = spts[3 * i + a];
-#pragma unroll
-            for (int a = 0; a < 3; ++a)
-                for (int msk = 32; msk; msk >>= 1) { lo[a] = fmin(lo[a], __shfl_xor(lo[a], msk)); hi[a] = fmax(hi[a], __shfl_xor(hi[a], msk)); }
-            if (lane == 0 && slot < n_slots)
-#pragma unroll
-                for (int a = 0; a < 3; ++a) { tbox[6 * slot + a] = lo[a]; tbox[6 * slot + 3 + a] = hi[a]; }
-        }
     }
 }
 
@@ -187,15 +137,14 @@ __global__ __launch_bounds__(256) void k_knn_query(const double* __restrict__ sp
         int keff = 0;
         if (c < n_cells) {
             const u64 i1 = begin[c + 1] < n_pts ? begin[c + 1] : n_pts, i0 = begin[c] < i1 ? begin[c] : i1;
-            const u64 n = i1 - i0, n_tiles = (n + KNN_TILE - 1) / KNN_TILE, slot0 = i0 / KNN_TILE + c;
+            const u64 n = i1 - i0, n_tiles = (n + TILE - 1) / TILE, slot0 = tile_slot0(i0, c);
             keff = n < (u64)k ? (int)n : k;
             const double qp[3] = {q_xyz[3 * q], q_xyz[3 * q + 1], q_xyz[3 * q + 2]};
             // the tile with the nearest box seeds the list
             double bd = INFINITY;
             u64 bt = 0;
             for (u64 t = lane; t < n_tiles; t += 64) {
-                const u64 slot = slot0 + t < n_slots ? slot0 + t : n_slots - 1;
-                const double d = box_dist2(qp, tbox + 6 * slot);
+                const double d = box_dist2(qp, tile_box(tbox, n_slots, slot0, t));
                 if (d < bd) { bd = d; bt = t; }
             }
             for (int msk = 32; msk; msk >>= 1) {
@@ -203,15 +152,12 @@ __global__ __launch_bounds__(256) void k_knn_query(const double* __restrict__ sp
                 const u64 ot = __shfl_xor(bt, msk);
                 if (od < bd || (od == bd && ot < bt)) { bd = od; bt = ot; }
             }
-            if (n_tiles) { knn_visit(spts, perm, i0 + bt * KNN_TILE, i1, qp, k, lane, e_d2, e_ix); ++n_visit; }
+            if (n_tiles) { knn_visit(spts, perm, i0 + bt * TILE, i1, qp, k, lane, e_d2, e_ix); ++n_visit; }
             for (u64 t0 = 0; t0 < n_tiles; t0 += 64) {
                 const u64 t = t0 + lane;
                 const bool live = t < n_tiles && t != bt;
                 double d = INFINITY;
-                if (live) {
-                    const u64 slot = slot0 + t < n_slots ? slot0 + t : n_slots - 1;
-                    d = box_dist2(qp, tbox + 6 * slot);
-                }
+                if (live) d = box_dist2(qp, tile_box(tbox, n_slots, slot0, t));
                 const double kth0 = __shfl(e_d2, k - 1);
                 u64 m = __ballot(live && !(d > kth0));
                 n_skip += (u64)__popcll(__ballot(live)) - (u64)__popcll(m);
@@ -220,7 +166,7 @@ __global__ __launch_bounds__(256) void k_knn_query(const double* __restrict__ sp
                     m &= m - 1;
                     const double db = __shfl(d, b), kth = __shfl(e_d2, k - 1);
                     if (db > kth) { ++n_skip; continue; }                          // strictly above the k-th best
-                    knn_visit(spts, perm, i0 + (t0 + b) * KNN_TILE, i1, qp, k, lane, e_d2, e_ix);
+                    knn_visit(spts, perm, i0 + (t0 + b) * TILE, i1, qp, k, lane, e_d2, e_ix);
                     ++n_visit;
                 }
             }
@@ -287,7 +233,7 @@ __global__ __launch_bounds__(256) void k_forest(const double* __restrict__ rows,
 struct KnnScratch { double *spts, *tbox, *cbox; u64 *key, *skey; u32 *i0, *perm; size_t n_slots; PrimScratch prim; };
 size_t layout(KnnScratch& w, void* base, size_t n_pts, size_t n_cells) {
     ScratchAlloc a(base);
-    w.n_slots = n_pts / KNN_TILE + n_cells + 1;
+    w.n_slots = tile_slots(n_pts, n_cells);
     a.take_into(3 * n_pts, w.spts);
     a.take_into(6 * w.n_slots, w.tbox);
     a.take_into(4 * n_cells, w.cbox);
@@ -296,8 +242,6 @@ size_t layout(KnnScratch& w, void* base, size_t n_pts, size_t n_cells) {
     w.prim = take_prim(a, n_pts);
     return a.used;
 }
-
-const size_t LIM31 = (size_t)1 << 31;
 
 }  // namespace
 
@@ -333,8 +277,7 @@ int sd_syn_props_knn(const void* points_dev, int points_f32, const uint64_t* beg
     const u64* begin = reinterpret_cast<const u64*>(begin_dev);
     const int f32 = points_f32 ? 1 : 0;
     if (stages & 1) {
-        int cbits = 0;
-        while (cbits < 31 && ((Cn - 1) >> cbits)) ++cbits;
+        const int cbits = bits_for(Cn);
         const int gc = grid_for(64 * Cn, SD_SYN_PROPS_CELL_GRID);
         hipLaunchKernelGGL(k_knn_cell_box, dim3(gc), dim3(256), 0, s, points_dev, f32, begin, Cn, N, w.cbox, counts);
         if (N) {
@@ -342,7 +285,7 @@ int sd_syn_props_knn(const void* points_dev, int points_f32, const uint64_t* beg
             hipLaunchKernelGGL(k_knn_keys, dim3(gp), dim3(256), 0, s, points_dev, f32, begin, w.cbox, Cn, N, w.key);
             if (int rc = sort_by_key(who, w.prim, w.key, w.skey, w.i0, w.perm, n_points, cbits + 3 * KNN_BITS, s); rc != SD_OK) return rc;
             hipLaunchKernelGGL(k_knn_place, dim3(gp), dim3(256), 0, s, points_dev, f32, w.perm, N, w.spts);
-            hipLaunchKernelGGL(k_knn_tiles, dim3(gc), dim3(256), 0, s, w.spts, begin, Cn, N, (u64)w.n_slots, w.tbox);
+            hipLaunchKernelGGL(k_tile_boxes<false>, dim3(gc), dim3(256), 0, s, w.spts, begin, Cn, N, (u64)w.n_slots, w.tbox, (double*)nullptr);
         }
     }
     if ((stages & 2) && Q) {

@@ -1,4 +1,4 @@
-// Synapse agglomeration on the device: the array form of what /root/reference/syconn/extraction/cs_processing_steps.py does per cell
+// Synapse agglomeration on the device: the array form of what extraction/cs_processing_steps.py does per cell
 // pair in Python -- connected_cluster_kdtree (:552-602, a networkx graph with one node per voxel and one cKDTree per fragment and per
 // pair of first-stage components) and the per-component half of _combine_and_split_syn_thread (:453-474: voxel share of every
 // fragment, size, bounding box, the voxel nearest the scaled centre of mass, the size filter).  All cell pairs ("groups") of a dataset
@@ -27,7 +27,7 @@
 // assembly.
 #include "../../include/syconn_dense.h"
 #include "sd_sortseg.h"
-#include <cmath>
+#include "sd_pointtiles.h"
 
 namespace {
 
@@ -123,15 +123,6 @@ __global__ __launch_bounds__(256) void k_ssv_cell_boxes(const int* __restrict__ 
 }
 
 // ---- link -------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ long find_cell(const u64* keys, u64 n, u64 key) {
-    u64 lo = 0, hi = n;
-    while (lo < hi) {
-        const u64 mid = lo + (hi - lo) / 2;
-        if (keys[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return (lo < n && keys[lo] == key) ? (long)lo : -1;
-}
-
 // squared scaled distance between a point and a box / the smallest and largest between two boxes (inclusive voxel boxes)
 __device__ __forceinline__ double point_box_d2(const int* v, const int* bx, const SsvGeom& g) {
     double d2 = 0.0;
@@ -206,7 +197,7 @@ __global__ __launch_bounds__(256) void k_ssv_link(const int* __restrict__ svox, 
                     ok = ok && q >= 0 && q < (1ll << g.b[a]);
                     nk = (nk << g.b[a]) | (u64)(ok ? q : 0);
                 }
-                if (ok) nb = find_cell(cell_key, n_cells, nk);
+                if (ok) nb = find_exact(cell_key, n_cells, nk);
                 if (nb >= 0) {
                     double dmin = 0.0, dmax = 0.0;
 #pragma unroll

@@ -8,9 +8,9 @@
 //   pairs    one wave per side.  The organelles arrive sorted by cell; the wave finds its cell's run by binary search, its lanes test
 //            the representative coordinates (d^2 <= D^2, inclusive as query_ball_tree is), and a ballot with a prefix popcount keeps
 //            the run's order.  The first call counts and scans (side_begin, the total); the second fills the caller's pair list.
-//   voxels   the sampled voxels of all synapses (rows 0, f, 2 f, ... of every run) as float64 nm, synapse-major; inside a synapse
-//            sorted by a coarse spatial key (boxes of 4 voxels, relative to the synapse's corner) and cut into tiles of 64 with one
-//            box per tile; one box per synapse.  Nothing of this depends on the organelle type.
+//   voxels   the sampled voxels of all synapses (rows 0, f, 2 f, ... of every run) as float64 nm, synapse-major: the tile index of
+//            sd_pointtiles.h with the synapses as segments, a coarse spatial key (boxes of 4 voxels, relative to the synapse's
+//            corner) and one box per synapse next to the tile boxes.  Nothing of this depends on the organelle type.
 //   query    every pair is split into work items of at most MAP_T sampled vertices (one scan over ceil(len / MAP_T)); one block of
 //            256 threads per item.  A thread holds MAP_T / 256 vertices; vertices outside the synapse's box by R or more are dropped;
 //            the block walks the synapse's tiles, skips a tile that no vertex of the block can profit from (__syncthreads_or),
@@ -22,51 +22,18 @@
 // (every product and sum rounded on its own) decides the rest.  No scalar memory writes, no inline assembly.
 #include "../../include/syconn_dense.h"
 #include "sd_sortseg.h"
-#include <cmath>
+#include "sd_pointtiles.h"
 
 namespace {
 
 constexpr int MAP_T = SD_SYNSSV_MAP_ITEM;                    // sampled vertices per work item
 constexpr int MAP_VPT = MAP_T / 256;                         // per thread
-constexpr int MAP_TILE = 64;                                 // sampled voxels per tile
 constexpr int MAP_QUERY_GRID = 8192;                         // blocks of the query kernel (items beyond are reached by the stride)
 constexpr u64 INF_BITS = 0x7ff0000000000000ull;
 static_assert(MAP_T % 256 == 0 && MAP_VPT <= 32, "one flag bit per vertex of a thread");
+static_assert(3 * TILE <= 256, "the block stages a tile through LDS with one coordinate per thread");
 
 struct MapGeom { double s[3], r2, r2_hi; };                  // voxel size in nm, squared radius, r2 (1 + 1e-9)
-
-// first index in [0, n) whose element is > key (n if none); a[] ascending
-template <class T> __device__ __forceinline__ u64 upper_bound(const T* a, u64 n, u64 key) {
-    u64 lo = 0, hi = n;
-    while (lo < hi) {
-        const u64 mid = lo + (hi - lo) / 2;
-        if ((u64)a[mid] <= key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-__device__ __forceinline__ u64 lower_bound(const u64* a, u64 n, u64 key) {
-    u64 lo = 0, hi = n;
-    while (lo < hi) {
-        const u64 mid = lo + (hi - lo) / 2;
-        if (a[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-__device__ __forceinline__ double sq_dist(const double* p, const double* q) {
-#pragma clang fp contract(off)                              // ((dx dx) + dy dy) + dz dz, no fused multiply-add: cKDTree's own sum
-    const double dx = p[0] - q[0], dy = p[1] - q[1], dz = p[2] - q[2];
-    return ((dx * dx) + dy * dy) + dz * dz;
-}
-__device__ __forceinline__ double box_dist2(const double* p, const double* bx) {   // bx = min | max
-    double d2 = 0.0;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const double d = fmax(0.0, fmax(bx[a] - p[a], p[a] - bx[3 + a]));
-        d2 += d * d;
-    }
-    return d2;
-}
 
 // ---- pairs ------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_map_pairs(const u64* __restrict__ side_cell, const int* __restrict__ syn_rep, u64 n_sides,
@@ -144,9 +111,7 @@ __global__ __launch_bounds__(256) void k_map_syn_corner(const u32* __restrict__ 
 __global__ __launch_bounds__(256) void k_map_vox_keys(const u32* __restrict__ vox, const u64* __restrict__ vb, const u64* __restrict__ svb,
                                                       const u32* __restrict__ corner, u64 n_syn, u64 n_vox, u64 n_sv, u32 f, int b, u64* key) {
     for (u64 j = (u64)blockIdx.x * 256 + threadIdx.x; j < n_sv; j += (u64)gridDim.x * 256) {
-        u64 s = upper_bound(svb, n_syn + 1, j);
-        s = s ? s - 1 : 0;
-        if (s >= n_syn) s = n_syn - 1;
+        const u64 s = segment_of(svb, n_syn, j);
         const u64 row = vox_row(vb, svb, s, j, f, n_vox);
         u64 k = s;
 #pragma unroll
@@ -168,35 +133,6 @@ __global__ __launch_bounds__(256) void k_map_vox_place(const u32* __restrict__ v
         const u64 row = vox_row(vb, svb, s, j, f, n_vox);
 #pragma unroll
         for (int a = 0; a < 3; ++a) pts[3 * i + a] = (double)vox[3 * row + a] * g.s[a];     // float64(voxel) * s, as numpy does it
-    }
-}
-// one wave per synapse: the box of every tile of 64 sorted points and of the synapse (tile t of synapse s is slot svb[s] / 64 + s + t)
-__global__ __launch_bounds__(256) void k_map_tiles(const double* __restrict__ pts, const u64* __restrict__ svb, u64 n_syn, u64 n_sv,
-                                                   u64 n_slots, double* tbox, double* sbox) {
-    const int lane = threadIdx.x & 63;
-    const u64 wave = ((u64)blockIdx.x * 256 + threadIdx.x) >> 6, n_waves = ((u64)gridDim.x * 256) >> 6;
-    for (u64 s = wave; s < n_syn; s += n_waves) {
-        const u64 i0 = svb[s], i1 = svb[s + 1] < n_sv ? svb[s + 1] : n_sv;
-        double slo[3] = {INFINITY, INFINITY, INFINITY}, shi[3] = {-INFINITY, -INFINITY, -INFINITY};
-        u64 slot = i0 / MAP_TILE + s;
-        for (u64 t0 = i0; t0 < i1; t0 += MAP_TILE, ++slot) {
-            const u64 i = t0 + lane;
-            double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-            if (i < i1)
-#pragma unroll
-                for (int a = 0; a < 3; ++a) lo[a] = hi[a] = pts[3 * i + a];
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                for (int msk = 32; msk; msk >>= 1) { lo[a] = fmin(lo[a], __shfl_xor(lo[a], msk)); hi[a] = fmax(hi[a], __shfl_xor(hi[a], msk)); }
-                slo[a] = fmin(slo[a], lo[a]); shi[a] = fmax(shi[a], hi[a]);
-            }
-            if (lane == 0 && slot < n_slots)
-#pragma unroll
-                for (int a = 0; a < 3; ++a) { tbox[6 * slot + a] = lo[a]; tbox[6 * slot + 3 + a] = hi[a]; }
-        }
-        if (lane == 0)
-#pragma unroll
-            for (int a = 0; a < 3; ++a) { sbox[6 * s + a] = slo[a]; sbox[6 * s + 3 + a] = shi[a]; }
     }
 }
 
@@ -234,7 +170,7 @@ __global__ __launch_bounds__(256) void k_map_query(const float* __restrict__ ver
                                                    const u32* __restrict__ pair_obj, const u32* __restrict__ pair_len, const u32* __restrict__ icnt,
                                                    const u32* __restrict__ iscan, u64 P, u32 f, MapGeom g, u32* pair_close, u64* pair_min,
                                                    u64* counts) {
-    __shared__ double tile[3 * MAP_TILE];
+    __shared__ double tile[3 * TILE];
     __shared__ u32 w_close[4];
     __shared__ u64 w_min[4];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -245,12 +181,9 @@ __global__ __launch_bounds__(256) void k_map_query(const float* __restrict__ ver
         const u64 p = upper_bound(iscan, P, item);                               // pairs without vertices have no item
         if (p >= P) break;
         const u64 chunk = item - (u64)(iscan[p] - icnt[p]);
-        u64 side = upper_bound(side_begin, n_sides + 1, p);
-        side = side ? side - 1 : 0;
-        if (side >= n_sides) side = n_sides - 1;
-        const u64 syn = side >> 1;
+        const u64 syn = segment_of(side_begin, n_sides, p) >> 1;
         const u64 i0 = svb[syn], i1 = svb[syn + 1] < n_sv ? svb[syn + 1] : n_sv;
-        const u64 n_tiles = i1 > i0 ? (i1 - i0 + MAP_TILE - 1) / MAP_TILE : 0, slot0 = i0 / MAP_TILE + syn;
+        const u64 n_tiles = i1 > i0 ? (i1 - i0 + TILE - 1) / TILE : 0, slot0 = tile_slot0(i0, syn);
         double sb[6];
 #pragma unroll
         for (int a = 0; a < 6; ++a) sb[a] = sbox[6 * syn + a];
@@ -271,10 +204,10 @@ __global__ __launch_bounds__(256) void k_map_query(const float* __restrict__ ver
             }
         }
         for (u64 t = 0; t < n_tiles; ++t) {
-            const u64 slot = slot0 + t < n_slots ? slot0 + t : n_slots - 1;
+            const double* tb = tile_box(tbox, n_slots, slot0, t);
             double bx[6];
 #pragma unroll
-            for (int a = 0; a < 6; ++a) bx[a] = tbox[6 * slot + a];
+            for (int a = 0; a < 6; ++a) bx[a] = tb[a];
             u32 want = 0;
 #pragma unroll
             for (int v = 0; v < MAP_VPT; ++v)
@@ -284,8 +217,8 @@ __global__ __launch_bounds__(256) void k_map_query(const float* __restrict__ ver
                 }
             if (!__syncthreads_or((int)want)) { ++n_skip; continue; }
             ++n_stage;
-            const u64 t0 = i0 + t * MAP_TILE;
-            const int cnt = (int)(i1 - t0 < (u64)MAP_TILE ? i1 - t0 : (u64)MAP_TILE);
+            const u64 t0 = i0 + t * TILE;
+            const int cnt = (int)(i1 - t0 < (u64)TILE ? i1 - t0 : (u64)TILE);
             if (tid < 3 * cnt) tile[tid] = pts[3 * t0 + tid];
             __syncthreads();
 #pragma unroll
@@ -346,7 +279,7 @@ size_t layout(MapPairScratch& w, void* base, size_t n_sides) {
 struct MapQueryScratch { double *pts, *tbox, *sbox; u32 *corner, *icnt, *iscan, *i0, *perm; u64 *key, *skey; size_t n_slots; PrimScratch prim; };
 size_t layout(MapQueryScratch& w, void* base, size_t n_syn, size_t n_sv, size_t n_pairs) {
     ScratchAlloc a(base);
-    w.n_slots = n_sv / MAP_TILE + n_syn + 1;
+    w.n_slots = tile_slots(n_sv, n_syn);
     a.take_into(3 * n_sv, w.pts);
     a.take_into(6 * w.n_slots, w.tbox);
     a.take_into(6 * n_syn, w.sbox);
@@ -368,8 +301,6 @@ bool map_geom(const double* scale, double radius, MapGeom& g) {
     g.r2_hi = g.r2 * (1.0 + 1e-9);
     return true;
 }
-
-const size_t LIM31 = (size_t)1 << 31;
 
 }  // namespace
 
@@ -447,9 +378,7 @@ int sd_synssv_map_query(const uint32_t* vox_dev, const uint64_t* vox_begin_dev, 
     const u64* vb = reinterpret_cast<const u64*>(vox_begin_dev);
     const u64* svb = reinterpret_cast<const u64*>(sampled_begin_dev);
     if (stages & 1) {
-        int sbits = 0;
-        while (sbits < 31 && ((S - 1) >> sbits)) ++sbits;
-        const int b = std::min(10, (64 - sbits) / 3);
+        const int sbits = bits_for(S), b = std::min(10, (64 - sbits) / 3);
         hipLaunchKernelGGL(k_map_syn_corner, dim3(grid_for(64 * S, 4096)), dim3(256), 0, s, vox_dev, vb, svb, S, (u64)n_vox, V, f, w.corner,
                            counts);
         if (V) {
@@ -458,7 +387,7 @@ int sd_synssv_map_query(const uint32_t* vox_dev, const uint64_t* vox_begin_dev, 
             if (int rc = sort_by_key(who, w.prim, w.key, w.skey, w.i0, w.perm, n_sampled_vox, sbits + 3 * b, s); rc != SD_OK) return rc;
             hipLaunchKernelGGL(k_map_vox_place, dim3(gv), dim3(256), 0, s, vox_dev, vb, svb, w.skey, w.perm, S, (u64)n_vox, V, f, b, g, w.pts);
         }
-        hipLaunchKernelGGL(k_map_tiles, dim3(grid_for(64 * S, 4096)), dim3(256), 0, s, w.pts, svb, S, V, (u64)w.n_slots, w.tbox, w.sbox);
+        hipLaunchKernelGGL(k_tile_boxes<true>, dim3(grid_for(64 * S, 4096)), dim3(256), 0, s, w.pts, svb, S, V, (u64)w.n_slots, w.tbox, w.sbox);
     }
     if ((stages & 2) && P) {
         if (!vert_begin_dev || !side_begin_dev || !pair_obj_dev || !pair_close_dev || !pair_len_dev || !pair_min_d2_dev || !n_org ||

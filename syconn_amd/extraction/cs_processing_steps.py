@@ -40,6 +40,22 @@ def _check_gap(cs_gap_nm, scaling):
     return gap, s
 
 
+def _check_scaling32(scaling):
+    """Three positive voxel sizes as the float32 that ``SegmentationDataset.scaling`` / ``SuperSegmentationObject.scaling`` hold
+    (segmentation.py:1747), widened to float64 as numpy widens them in a product.  (``_check_gap`` is a different rule on purpose:
+    it evaluates ``min_gap_nm`` and the binning cell on the float64 values the caller gives.)"""
+    scale = np.asarray(scaling, np.float32).reshape(-1).astype(np.float64)
+    if scale.shape != (3,) or not np.all(scale > 0):
+        raise ValueError(f'scaling must be three positive voxel sizes, got {scaling}')
+    return scale
+
+
+def _check_positive_int(**named):
+    for name, v in named.items():
+        if isinstance(v, bool) or int(v) != v or int(v) < 1:
+            raise ValueError(f'{name} must be an integer >= 1, got {v!r}')
+
+
 def choose_cell(scaling, cs_gap_nm):
     """The binning cell (voxels per axis) of the component search: per axis the largest extent whose share of the scaled diagonal is
     gap / sqrt(3), shrunk until ``||(c - 1) * scaling||`` (float64) is strictly below the gap -- all voxels of a group inside one cell
@@ -658,11 +674,8 @@ def map_objects_from_synssv_partners(syn_ssv, organelles: dict, scaling=None, ma
     cobj = cfg['cell_objects']
     max_vert_dist_nm = cobj['max_vert_dist_nm'] if max_vert_dist_nm is None else max_vert_dist_nm
     D = float(cobj['max_rep_coord_dist_nm'] if max_rep_coord_dist_nm is None else max_rep_coord_dist_nm)
-    if isinstance(sample_fact, bool) or int(sample_fact) != sample_fact or int(sample_fact) < 1:
-        raise ValueError(f'sample_fact must be an integer >= 1, got {sample_fact!r}')
-    scale = np.asarray(scaling, np.float32).reshape(-1).astype(np.float64)   # SegmentationDataset.scaling is float32, numpy widens it
-    if scale.shape != (3,) or not np.all(scale > 0):
-        raise ValueError(f'scaling must be three positive voxel sizes, got {scaling}')
+    _check_positive_int(sample_fact=sample_fact)
+    scale = _check_scaling32(scaling)
     radius = {}
     for t, table in organelles.items():
         if not isinstance(table, OrganelleTable):
@@ -1005,6 +1018,25 @@ def segmented_knn(points, begin, labels, q_cell, q_xyz, k: int, device=None, ret
     return out[0] if len(out) == 1 else tuple(out)
 
 
+def _cell_rows(cells: CellTable, ids):
+    """-> (row of every id in the table, found mask); a missing id gets some row of the table (none if the table is empty)."""
+    if not len(cells):
+        return np.zeros(len(ids), np.int64), np.zeros(len(ids), bool)
+    order = np.argsort(cells.ids, kind='stable')
+    row = order[np.minimum(np.searchsorted(cells.ids[order], ids), len(cells) - 1)]
+    return row, cells.ids[row] == ids
+
+
+def _nearest_nodes(cells: CellTable, used, rows, q_xyz, scale, device):
+    """The skeleton node nearest to every query (`rows`: its cell, flagged in `used`; ``attr_for_coords``'s k = 1 tree over
+    ``nodes * scaling``) as a row of ``cells.nodes``.  Only the nodes of the used cells go to the device."""
+    n_nodes = np.diff(cells.node_begin)
+    begin = np.concatenate(([0], np.cumsum(np.where(used, n_nodes, 0)))).astype(np.int64)
+    node_keep = np.repeat(used, n_nodes)
+    nearest = segmented_knn(cells.nodes[node_keep] * scale, begin, None, rows, q_xyz, 1, device)
+    return np.flatnonzero(node_keep)[nearest]               # kept node j is node flatnonzero(node_keep)[j] of the table
+
+
 def spine_vertices(cells: CellTable, used, semseg_key: str, ds_vertices: int, ignore_labels):
     """The vertices ``semseg_for_coords`` (super_segmentation_object.py:2219-2237) hands to the tree, for the cells flagged in `used`:
     every ``ds``-th vertex of a cell (``ds = max(1, ds_vertices // 10)`` below 5e6 vertices), without the ignored labels.
@@ -1055,14 +1087,10 @@ def collect_properties_from_ssv_partners(syn_ssv, cells: CellTable, scaling=None
     sym_thresh = cfg['cell_objects']['sym_thresh'] if sym_thresh is None else sym_thresh
     if not isinstance(cells, CellTable):
         raise TypeError('cells must be a CellTable')
-    for name, v in (('k', k), ('ds_vertices', ds_vertices)):
-        if isinstance(v, bool) or int(v) != v or int(v) < 1:
-            raise ValueError(f'{name} must be an integer >= 1, got {v!r}')
+    _check_positive_int(k=k, ds_vertices=ds_vertices)
     if int(k) > L.SD_SYN_PROPS_MAX_K:
         raise ValueError(f'k = {k}: at most {L.SD_SYN_PROPS_MAX_K} neighbours per query')
-    scale = np.asarray(scaling, np.float32).reshape(-1).astype(np.float64)   # SuperSegmentationObject.scaling is float32, numpy widens it
-    if scale.shape != (3,) or not np.all(scale > 0):
-        raise ValueError(f'scaling must be three positive voxel sizes, got {scaling}')
+    scale = _check_scaling32(scaling)
     if 'latent_morph' in cells.node_attrs and cells.node_attrs['latent_morph'].shape[1] != m:
         raise ValueError(f"latent_morph holds {cells.node_attrs['latent_morph'].shape[1]} values per node, ndim_embedding is {m}")
     n = len(syn_ssv)
@@ -1072,15 +1100,10 @@ def collect_properties_from_ssv_partners(syn_ssv, cells: CellTable, scaling=None
     syn_ids = np.arange(n, dtype=np.uint64) if syn_ids is None else np.ascontiguousarray(syn_ids, dtype=np.uint64).reshape(-1)
     if len(ratio) != n or len(syn_ids) != n:
         raise ValueError(f'{n} synapses, {len(ratio)} syn_type_sym_ratio, {len(syn_ids)} syn_ids')
-    order = np.argsort(cells.ids, kind='stable')
     side_cell_id = partners.reshape(-1)
-    if 2 * n and not len(cells):
-        raise ValueError(f'Could not find the partner cell {int(side_cell_id[0])} of synssv with ID {int(syn_ids[0])} in the cell table.')
-    at = np.minimum(np.searchsorted(cells.ids[order], side_cell_id), max(len(cells) - 1, 0))
-    row = order[at] if len(cells) else np.zeros(0, np.int64)
-    miss = np.flatnonzero(cells.ids[row] != side_cell_id) if 2 * n else np.zeros(0, np.int64)
-    if len(miss):
-        s = int(miss[0])
+    row, known = _cell_rows(cells, side_cell_id)
+    if not known.all():
+        s = int(np.flatnonzero(~known)[0])
         raise ValueError(f'Could not find the partner cell {int(side_cell_id[s])} of synssv with ID {int(syn_ids[s // 2])} in the cell table.')
     props = dict(partner_axoness=np.zeros(2 * n, np.int32), partner_spiness=np.zeros(2 * n, np.int32), partner_celltypes=np.zeros(2 * n, np.int32),
                  partner_spineheadvol=np.zeros(2 * n, np.float32), latent_morph=np.zeros((2 * n, m), np.float32))
@@ -1117,12 +1140,8 @@ def collect_properties_from_ssv_partners(syn_ssv, cells: CellTable, scaling=None
             props['latent_morph'][sides] = np.inf
             sk = sides[has_skel[row[sides]]]
             if len(sk):
-                nb = np.concatenate(([0], np.cumsum(np.where(used & has_mesh, np.diff(cells.node_begin), 0)))).astype(np.int64)
-                node_keep = np.repeat(used & has_mesh, np.diff(cells.node_begin))
-                kept_rows = np.flatnonzero(node_keep)             # kept node j is node kept_rows[j] of the table
-                nearest = segmented_knn(cells.nodes[node_keep] * scale, nb, None, row[sk], q_xyz[sk], 1, device)
                 dev = _cs_device(device)
-                near_d = torch.from_numpy(kept_rows[nearest]).to(dev)
+                near_d = torch.from_numpy(_nearest_nodes(cells, used & has_mesh, row[sk], q_xyz[sk], scale, device)).to(dev)
                 if pred_key_ax in cells.node_attrs:
                     ax = torch.from_numpy(cells.node_attrs[pred_key_ax]).to(dev)[near_d].cpu().numpy()
                     ok = cells.node_attr_present[pred_key_ax][row[sk]]
@@ -1218,9 +1237,7 @@ def calculate_spinehead_volume(cells: CellTable, sv_begin, sv_ids, syn_ids, syn_
     if ax_key is None:
         comp = cfg['compartments']
         ax_key = '{}_avg{}'.format(comp['view_properties_semsegax']['semseg_key'], comp['dist_axoness_averaging'])
-    for name, v in (('k', k), ('ds_vertices', ds_vertices), ('batch', batch)):
-        if isinstance(v, bool) or int(v) != v or int(v) < 1:
-            raise ValueError(f'{name} must be an integer >= 1, got {v!r}')
+    _check_positive_int(k=k, ds_vertices=ds_vertices, batch=batch)
     if int(k) > L.SD_SYN_PROPS_MAX_K:
         raise ValueError(f'k = {k}: at most {L.SD_SYN_PROPS_MAX_K} neighbours per query')
     sc, ds = SH.check_scaling(cfg['scaling'] if scaling is None else scaling)
@@ -1242,11 +1259,7 @@ def calculate_spinehead_volume(cells: CellTable, sv_begin, sv_ids, syn_ids, syn_
     if not hasattr(seg, 'load_seg') and not (isinstance(seg, (tuple, list)) and len(seg) == 2 and len(np.asarray(seg[1]).reshape(-1)) == 3):
         raise ValueError('seg must be a KnossosDataset or (volume, origin)')
     # (cell row, synapse) pairs: a synapse is a syn_ssv of each of its cells, once
-    order = np.argsort(cells.ids, kind='stable')
-    side = syn_cells.reshape(-1)
-    at = np.minimum(np.searchsorted(cells.ids[order], side), max(n_cells - 1, 0))
-    row = order[at] if n_cells else np.zeros(len(side), np.int64)
-    known = (cells.ids[row] == side) if n_cells else np.zeros(len(side), bool)
+    row, known = _cell_rows(cells, syn_cells.reshape(-1))
     known[1::2] &= ~(known[0::2] & (syn_cells[:, 0] == syn_cells[:, 1]))
     pair_syn, pair_row = np.flatnonzero(known) // 2, row[known]
     used = np.zeros(n_cells, bool)
@@ -1273,10 +1286,7 @@ def calculate_spinehead_volume(cells: CellTable, sv_begin, sv_ids, syn_ids, syn_
         has_ax = ax_key in cells.node_attrs
         sk = np.flatnonzero((np.diff(cells.node_begin) > 0)[pair_row] & (cells.node_attr_present[ax_key][pair_row] if has_ax else False))
         if len(sk):
-            nb = np.concatenate(([0], np.cumsum(np.where(used, np.diff(cells.node_begin), 0)))).astype(np.int64)
-            node_keep = np.repeat(used, np.diff(cells.node_begin))
-            nearest = segmented_knn(cells.nodes[node_keep] * scale, nb, None, pair_row[sk], q_xyz[sk], 1, device)
-            curr_ax[sk] = cells.node_attrs[ax_key][np.flatnonzero(node_keep)[nearest]]
+            curr_ax[sk] = cells.node_attrs[ax_key][_nearest_nodes(cells, used, pair_row[sk], q_xyz[sk], scale, device)]
         head = (curr_sp == 1) & (curr_ax == 0)
         runner = None                                                # every cell has the same window shape: one set of device buffers
         for c in np.flatnonzero(used):
