@@ -656,6 +656,58 @@ int sd_spinehead_markers(const int32_t* peaks_dev, const int32_t* n_peaks_dev, c
 int sd_spinehead_select(const int32_t* flood_dev, int X, int Y, int Z, const int64_t* c_xyz, const double* scaling_xyz, int32_t* objects_dev,
                         int32_t* result_dev, void* workspace_dev, size_t ws_bytes, void* stream);
 
+/* ---- majority votes along skeletons (csrc/sd_skeleton.hip) -------------------------------------------------------------
+ * The array form of majorityvote_skeleton_property (/root/reference/syconn/reps/super_segmentation_helper.py:1270-1302, one
+ * nx.single_source_dijkstra_path and one np.unique per skeleton node, over SuperSegmentationObject.weighted_graph, reps/
+ * super_segmentation_object.py:1440-1451) and of majority_vote_compartments (:1233-1266), for all cells in one call.  Cell c owns the
+ * table rows node_begin_dev[c] .. node_begin_dev[c + 1] and the edges edge_begin_dev[c] .. edge_begin_dev[c + 1] (uint64[n_cells + 1],
+ * ascending from 0 to the total); edges_dev int64[n_edges][2] names nodes by their index INSIDE the cell.  classes_dev uint8[n_nodes]:
+ * dense classes below n_classes <= SD_SKEL_MAX_CLASSES (the caller maps its labels with np.unique, so the smaller class is the smaller
+ * label).  Limits (SD_ERR_INVALID beyond): n_cells < 2^31, n_nodes < 2^31 - 1, n_edges < 2^30.  Asynchronous on the stream.
+ *   sd_skel_csr          the adjacency: adj_begin_dev uint64[n_nodes + 1], adj_nbr_dev uint32[2 n_edges] (the neighbour's index inside the
+ *                        cell), adj_w_dev double[2 n_edges]; weight_dev double[n_edges] is computed by the caller (np.linalg.norm of
+ *                        the scaled end points: the reference's own expression, its dtype promotion included).  Parallel edges and self
+ *                        loops stay in the rows.  counts_dev uint64[8]; [7] != 0: an offset table is not ascending from 0 to the total,
+ *                        an edge names a node outside its cell (it is left out of every row, nothing is read through it) or a weight
+ *                        is negative or NaN (stored as +inf).  Scratch: sd_skel_csr_temp_bytes(n_edges).
+ *   sd_skel_vote         vote_dev[g] uint8 = the most frequent class, on equal counts the smallest, among the nodes v of g's cell with
+ *                        dist(g, v) <= max_dist, dist = the minimum over all paths of the left-to-right float64 sum of the weights (what
+ *                        Dijkstra yields; g itself is always in).  Optional n_reached_dev uint32[n_nodes] = the size of that window.
+ *                        One wave per source; a window of up to SD_SKEL_LDS_NODES nodes is held in LDS, a larger one is redone over
+ *                        arrays in the scratch that are sized by max_cell_nodes (>= the nodes of every cell; [7] otherwise).
+ *                        counts_dev uint64[8] = sources redone that way, relaxation steps of the first pass, of the second, ...; [7] !=
+ *                        0: an offset or a cell size was out of range.  Scratch: sd_skel_vote_temp_bytes(n_nodes, max_cell_nodes): one
+ *                        byte per node and 20 bytes per node of the largest cell for each wave of the second pass, which runs
+ *                        SD_SKEL_REDO_GRID blocks, fewer where those arrays would pass SD_SKEL_REDO_BYTES.
+ *   sd_skel_components   out_dev[g] uint8: nodes of class soma_class keep it; the others form connected components over the edges whose
+ *                        two nodes are not soma (a node without such an edge is a component), and every node gets its component's
+ *                        most frequent class, the smallest on equal counts; where that is one_class with a count c1 and 50 c1 < 33
+ *                        total (the reference's float32 test `c1 / total < 0.66`, equal to it for total < 2^24) it gets zero_class.
+ *                        soma_class / one_class may be -1 (no such class).  counts_dev uint64[8]; [6] != 0: such a component had 2^24
+ *                        nodes or more; [7] != 0: an offset or an edge was out of range (the edge is ignored).
+ *                        Scratch: sd_skel_components_temp_bytes(n_nodes).
+ * One grid stride of the kernels is SD_SKEL_VOTE_GRID blocks of four sources, SD_SKEL_NODE_GRID blocks of 256 nodes (or cells),
+ * SD_SKEL_EDGE_GRID blocks of 256 half edges (or edges). */
+#define SD_SKEL_MAX_CLASSES 64
+#define SD_SKEL_LDS_NODES 512
+#define SD_SKEL_VOTE_GRID 2048
+#define SD_SKEL_NODE_GRID 1024
+#define SD_SKEL_EDGE_GRID 1024
+#define SD_SKEL_REDO_GRID 1024
+#define SD_SKEL_REDO_BYTES 268435456
+size_t sd_skel_csr_temp_bytes(size_t n_edges);
+int sd_skel_csr(const int64_t* edges_dev, const uint64_t* edge_begin_dev, const uint64_t* node_begin_dev, size_t n_cells, size_t n_nodes,
+                size_t n_edges, const double* weight_dev, uint64_t* adj_begin_dev, uint32_t* adj_nbr_dev, double* adj_w_dev, uint64_t* counts_dev,
+                void* temp_dev, size_t temp_bytes, void* stream);
+size_t sd_skel_vote_temp_bytes(size_t n_nodes, size_t max_cell_nodes);
+int sd_skel_vote(const uint64_t* adj_begin_dev, const uint32_t* adj_nbr_dev, const double* adj_w_dev, size_t n_adj, const uint64_t* node_begin_dev,
+                 size_t n_cells, size_t n_nodes, size_t max_cell_nodes, const uint8_t* classes_dev, int n_classes, double max_dist,
+                 uint8_t* vote_dev, uint32_t* n_reached_dev, uint64_t* counts_dev, void* temp_dev, size_t temp_bytes, void* stream);
+size_t sd_skel_components_temp_bytes(size_t n_nodes);
+int sd_skel_components(const int64_t* edges_dev, const uint64_t* edge_begin_dev, const uint64_t* node_begin_dev, size_t n_cells, size_t n_nodes,
+                       size_t n_edges, const uint8_t* classes_dev, int soma_class, int one_class, int zero_class, uint8_t* out_dev,
+                       uint64_t* counts_dev, void* temp_dev, size_t temp_bytes, void* stream);
+
 /* ---- host-side helpers of the chunk pipeline (no GPU) -----------------------------------------------------------------
  * Multi-threaded strided copy of an (nz, ny, nx)-byte box between two uint8 host arrays whose x-rows are contiguous
  * (strides in bytes), and a multi-threaded memset: what numpy slicing does on one core when the reference cuts a chunk

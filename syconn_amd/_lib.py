@@ -16,6 +16,7 @@ SD_CST_COLS = 24
 SD_SYNSSV_MAP_ITEM = 1024
 SD_SPINEHEAD_VOX_GRID, SD_SPINEHEAD_VERT_GRID, SD_SPINEHEAD_ID_GRID = 8192, 1024, 1024
 SD_SYN_PROPS_MAX_K, SD_SYN_PROPS_CELL_GRID, SD_SYN_PROPS_POINT_GRID, SD_SYN_PROPS_QUERY_GRID, SD_SYN_PROPS_FOREST_GRID = 64, 4096, 1024, 8192, 1024
+SD_SKEL_MAX_CLASSES, SD_SKEL_LDS_NODES, SD_SKEL_VOTE_GRID, SD_SKEL_NODE_GRID, SD_SKEL_EDGE_GRID, SD_SKEL_REDO_GRID, SD_SKEL_REDO_BYTES = 64, 512, 2048, 1024, 1024, 1024, 1 << 28
 
 LIB_NAME = 'libsyconn_dense_hip.so'
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), os.environ.get('SD_LIB_NAME', LIB_NAME))
@@ -37,7 +38,8 @@ EXPORTS = ['sd_init', 'sd_device_count', 'sd_model_create', 'sd_model_destroy', 
            'sd_synssv_map_pairs_temp_bytes', 'sd_synssv_map_pairs', 'sd_synssv_map_query_temp_bytes', 'sd_synssv_map_query',
            'sd_syn_props_knn_temp_bytes', 'sd_syn_props_knn', 'sd_syn_props_forest', 'sd_spinehead_workspace_bytes', 'sd_edt_squared',
            'sd_spinehead_window_mask', 'sd_spinehead_fill_holes', 'sd_spinehead_peaks', 'sd_spinehead_box_vertices_temp_bytes',
-           'sd_spinehead_box_vertices', 'sd_spinehead_queries', 'sd_spinehead_markers', 'sd_spinehead_select']
+           'sd_spinehead_box_vertices', 'sd_spinehead_queries', 'sd_spinehead_markers', 'sd_spinehead_select', 'sd_skel_csr_temp_bytes', 'sd_skel_csr',
+           'sd_skel_vote_temp_bytes', 'sd_skel_vote', 'sd_skel_components_temp_bytes', 'sd_skel_components']
 
 
 class OpDesc(C.Structure):
@@ -196,6 +198,13 @@ def load():
     lib.sd_spinehead_queries.argtypes = [vp, vp, sz, sz, sz, f64p, vp, vp, vp]; lib.sd_spinehead_queries.restype = i32
     lib.sd_spinehead_markers.argtypes = [vp, vp, vp, sz, i32, i32, i32, vp, vp]; lib.sd_spinehead_markers.restype = i32
     lib.sd_spinehead_select.argtypes = [vp, i32, i32, i32, i64p, f64p, vp, vp, vp, sz, vp]; lib.sd_spinehead_select.restype = i32
+    # reps/super_segmentation_helper.py:1270-1302 (majorityvote_skeleton_property) and :1233-1266 (majority_vote_compartments)
+    lib.sd_skel_csr_temp_bytes.argtypes = [sz]; lib.sd_skel_csr_temp_bytes.restype = sz
+    lib.sd_skel_csr.argtypes = [vp, vp, vp, sz, sz, sz, vp, vp, vp, vp, vp, vp, sz, vp]; lib.sd_skel_csr.restype = i32
+    lib.sd_skel_vote_temp_bytes.argtypes = [sz, sz]; lib.sd_skel_vote_temp_bytes.restype = sz
+    lib.sd_skel_vote.argtypes = [vp, vp, vp, sz, vp, sz, sz, sz, vp, i32, C.c_double, vp, vp, vp, vp, sz, vp]; lib.sd_skel_vote.restype = i32
+    lib.sd_skel_components_temp_bytes.argtypes = [sz]; lib.sd_skel_components_temp_bytes.restype = sz
+    lib.sd_skel_components.argtypes = [vp, vp, vp, sz, sz, sz, vp, i32, i32, i32, vp, vp, vp, sz, vp]; lib.sd_skel_components.restype = i32
     _lib = lib
     return lib
 

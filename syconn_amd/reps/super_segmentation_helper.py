@@ -1,8 +1,10 @@
-"""Drop-in for the one function of ``syconn.reps.super_segmentation_helper`` that consumes the dense path's output
-directly: ``map_myelin2coords`` (/root/reference/syconn/reps/super_segmentation_helper.py:550-615; SURVEY.md
-section 8f row 3).  Same name, arguments, return value and error behaviour; the per-node ``kd.load_raw`` + numpy
+"""Drop-ins for the functions of ``syconn.reps.super_segmentation_helper`` that consume the dense path's output or smooth it along
+the skeletons.  ``map_myelin2coords`` (/root/reference/syconn/reps/super_segmentation_helper.py:550-615; SURVEY.md
+section 8f row 3): same name, arguments, return value and error behaviour; the per-node ``kd.load_raw`` + numpy
 reduction of the reference (one 11x11x5 box read per skeleton node) becomes: read the region the nodes cover once,
-keep it on the GPU, one wave per node (``sd_box_majority``).  No CPU fallback.
+keep it on the GPU, one wave per node (``sd_box_majority``).  ``majorityvote_skeleton_property`` (:1270-1302) and
+``majority_vote_compartments`` (:1233-1266): one Dijkstra per node and one ``np.unique`` per node or component become
+``skeleton_majority_vote`` / ``skeleton_compartment_majority`` over all cells of a call (``sd_skel_*``).  No CPU fallback.
 """
 import os
 
@@ -103,3 +105,183 @@ def extract_spinehead_volume_mesh(sso, ctx_vol=(200, 200, 100)):
                                               ignore_labels=sp['ignore_labels'], ds_vertices=sp['ds_vertices'], ax_key=ax_key)
     for i, v in zip(ids.tolist(), vols.tolist()):
         sso.attr_dict['spinehead_vol'][i] = v
+
+
+# -- majority votes along skeletons ------------------------------------------------------------------------------------------
+def _skel_graph(what, n_nodes, node_begin, edges, edge_begin):
+    """Checked offsets and edges -> (node_begin int64, edges int64 (e, 2), edge_begin int64, row of the cell of every edge)."""
+    from ..extraction.cs_processing_steps import _check_offsets
+    node_begin = np.ascontiguousarray(node_begin, dtype=np.int64).reshape(-1)
+    edge_begin = np.ascontiguousarray(edge_begin, dtype=np.int64).reshape(-1)
+    n_cells = len(node_begin) - 1
+    if n_cells < 0:
+        raise ValueError(f'{what}: node_begin must hold cells + 1 offsets')
+    e = np.asarray(edges)
+    if e.size and not np.issubdtype(e.dtype, np.integer):
+        raise ValueError(f'{what}: edges must be integers, got {e.dtype}')
+    if e.size % 2 or (e.ndim == 2 and e.shape[1] != 2 and e.size):
+        raise ValueError(f'{what}: edges must have the shape (e, 2)')
+    if e.size and e.dtype == np.uint64 and e.max() >= 2 ** 63:
+        raise ValueError(f'{what}: an edge names a node outside its cell')
+    e = np.ascontiguousarray(e.reshape(-1, 2), dtype=np.int64)
+    _check_offsets(f'{what}: node_begin', node_begin, n_cells, n_nodes)
+    _check_offsets(f'{what}: edge_begin', edge_begin, n_cells, len(e))
+    cell_of = np.repeat(np.arange(n_cells), np.diff(edge_begin))
+    size = np.diff(node_begin)[cell_of]
+    if len(e) and ((e < 0) | (e >= size[:, None])).any():
+        raise ValueError(f'{what}: an edge names a node outside its cell')
+    return node_begin, e, edge_begin, cell_of
+
+
+def _dense_classes(what, labels, n_nodes, extra=()):
+    """Integer labels -> (their sorted distinct values, with `extra`; the uint8 class of every node)."""
+    lab = np.asarray(labels)
+    if lab.size and not np.issubdtype(lab.dtype, np.integer):
+        raise ValueError(f'{what}: labels must be integers, got {lab.dtype} (float-valued properties are not supported)')
+    if lab.size != n_nodes or (lab.ndim > 1 and lab.shape[0] != n_nodes):
+        raise ValueError(f'{what}: {n_nodes} nodes, labels of shape {lab.shape}')
+    lab = lab.reshape(-1)
+    values = np.unique(lab)
+    for x in extra:
+        if x not in values:
+            values = np.unique(np.concatenate([values, np.array([x], values.dtype)]))
+    if len(values) > L.SD_SKEL_MAX_CLASSES:
+        raise ValueError(f'{what}: {len(values)} distinct labels, at most {L.SD_SKEL_MAX_CLASSES} classes are supported')
+    return values, np.searchsorted(values, lab).astype(np.uint8), lab
+
+
+def skeleton_edge_weights(nodes, node_begin, edges, edge_begin, scaling) -> np.ndarray:
+    """The edge weights of ``weighted_graph`` (super_segmentation_object.py:1440-1444) for all cells: ``np.linalg.norm`` of the
+    difference of the end points of ``nodes * scaling``, in the dtypes the caller passes; `edges` index the nodes of their cell."""
+    nodes = np.asarray(nodes)
+    node_begin, e, edge_begin, cell_of = _skel_graph('skeleton_edge_weights', len(nodes), node_begin, edges, edge_begin)
+    node_scaled = nodes * scaling
+    edge_coords = node_scaled[e + node_begin[cell_of][:, None]]
+    return np.linalg.norm(edge_coords[:, 0] - edge_coords[:, 1], axis=1)
+
+
+def _skel_counts(name, counts_d):
+    counts = counts_d.cpu().numpy()
+    if int(counts[7]):
+        raise RuntimeError(f'{name}: an offset, an edge or a weight was out of range')
+    return counts
+
+
+def skeleton_majority_vote(nodes, node_begin, edges, edge_begin, labels, scaling, max_dist=10000, device=None, return_reached=False,
+                           return_counts=False):
+    """``majorityvote_skeleton_property`` (:1270-1302) for all cells at once.  Cell c owns ``nodes[node_begin[c]:node_begin[c + 1]]``
+    ((n, 3), voxels) and ``edges[edge_begin[c]:edge_begin[c + 1]]`` ((e, 2) integers: node indices INSIDE the cell).  An edge weighs
+    ``np.linalg.norm`` of its end points in ``nodes * scaling`` (computed here on the host with the caller's dtypes, widened to
+    float64); the window of a node holds the nodes whose shortest-path distance (float64 sums from the source on) is ``<= max_dist``;
+    the result is the most frequent of the integer `labels` in the window, the smallest on equal counts, in the dtype of `labels`.
+    At most 64 distinct labels.  With `return_reached` also the window sizes (uint32), with `return_counts` the device's counters."""
+    what = 'skeleton_majority_vote'
+    nodes = np.asarray(nodes)
+    if nodes.ndim != 2 or nodes.shape[1] != 3:
+        if nodes.size:
+            raise ValueError(f'{what}: nodes must have the shape (n, 3), got {nodes.shape}')
+        nodes = nodes.reshape(0, 3)
+    scaling = np.asarray(scaling)
+    if scaling.shape != (3,) or not np.isfinite(scaling.astype(np.float64)).all():
+        raise ValueError(f'{what}: scaling must hold three finite numbers')
+    if not np.isfinite(nodes.astype(np.float64)).all():
+        raise ValueError(f'{what}: a node coordinate is not finite')
+    if isinstance(max_dist, bool) or not np.isscalar(max_dist) or not float(max_dist) >= 0:
+        raise ValueError(f'{what}: max_dist must be a number >= 0, got {max_dist!r}')
+    n = len(nodes)
+    node_begin, e, edge_begin, cell_of = _skel_graph(what, n, node_begin, edges, edge_begin)
+    values, classes, lab = _dense_classes(what, labels, n)
+    node_scaled = nodes * scaling
+    edge_coords = node_scaled[e + node_begin[cell_of][:, None]]
+    weights = np.ascontiguousarray(np.linalg.norm(edge_coords[:, 0] - edge_coords[:, 1], axis=1), dtype=np.float64).reshape(-1)
+    if not np.isfinite(weights).all():
+        raise ValueError(f'{what}: an edge length is not finite')
+    if n == 0:
+        out = [lab.copy(), np.zeros(0, np.uint32), dict(sources_redone=0, steps_lds=0, steps_redo=0)]
+        return out[0] if not (return_reached or return_counts) else tuple(o for o, f in zip(out, (True, return_reached, return_counts)) if f)
+    from ..extraction.find_object_properties import _cs_device
+    lib, dev = L.load(), _cs_device(device)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    n_cells, n_e = len(node_begin) - 1, len(e)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    nb_d, eb_d, e_d, w_d, cls_d = up(node_begin), up(edge_begin), up(e), up(weights), up(classes)
+    adj_begin = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    adj_nbr = torch.empty(max(2 * n_e, 1), dtype=torch.int32, device=dev)
+    adj_w = torch.empty(max(2 * n_e, 1), dtype=torch.float64, device=dev)
+    counts_d = torch.zeros(8, dtype=torch.int64, device=dev)
+    tmp = torch.empty(lib.sd_skel_csr_temp_bytes(n_e), dtype=torch.uint8, device=dev)
+    L.check(lib.sd_skel_csr(e_d.data_ptr(), eb_d.data_ptr(), nb_d.data_ptr(), n_cells, n, n_e, w_d.data_ptr(), adj_begin.data_ptr(), adj_nbr.data_ptr(),
+                            adj_w.data_ptr(), counts_d.data_ptr(), tmp.data_ptr(), tmp.numel(), stream), 'sd_skel_csr')
+    _skel_counts('sd_skel_csr', counts_d)
+    max_cell = int(np.diff(node_begin).max())
+    vote_d = torch.empty(n, dtype=torch.uint8, device=dev)
+    reached_d = torch.empty(n, dtype=torch.int32, device=dev) if return_reached else None
+    tmp = torch.empty(lib.sd_skel_vote_temp_bytes(n, max_cell), dtype=torch.uint8, device=dev)
+    L.check(lib.sd_skel_vote(adj_begin.data_ptr(), adj_nbr.data_ptr(), adj_w.data_ptr(), 2 * n_e, nb_d.data_ptr(), n_cells, n, max_cell, cls_d.data_ptr(),
+                             len(values), float(max_dist), vote_d.data_ptr(), None if reached_d is None else reached_d.data_ptr(), counts_d.data_ptr(),
+                             tmp.data_ptr(), tmp.numel(), stream), 'sd_skel_vote')
+    counts = _skel_counts('sd_skel_vote', counts_d)
+    out = [values[vote_d.cpu().numpy()].astype(lab.dtype, copy=False)]
+    if return_reached:
+        out.append(reached_d.cpu().numpy().view(np.uint32))
+    if return_counts:
+        out.append(dict(sources_redone=int(counts[0]), steps_lds=int(counts[1]), steps_redo=int(counts[2])))
+    return out[0] if len(out) == 1 else tuple(out)
+
+
+def skeleton_compartment_majority(node_begin, edges, edge_begin, labels, soma_label=2, device=None):
+    """``majority_vote_compartments`` (:1233-1266) for all cells at once (`node_begin`, `edges`, `edge_begin` as in
+    ``skeleton_majority_vote``): the nodes labelled `soma_label` keep it; the connected components of the others get their most
+    frequent label, the smallest on equal counts; where that is 1 with a share below 0.66 (``50 * c1 < 33 * total``, the reference's
+    float32 test for every component below 2^24 nodes) they get 0.  -> labels in the dtype of `labels`."""
+    what = 'skeleton_compartment_majority'
+    lab0 = np.asarray(labels)
+    n = int(lab0.shape[0]) if lab0.ndim else 0
+    node_begin, e, edge_begin, _ = _skel_graph(what, n, node_begin, edges, edge_begin)
+    values, classes, lab = _dense_classes(what, lab0, n, extra=(0,) if n and (lab0 == 1).any() else ())
+    if n == 0:
+        return lab.copy()
+    find = lambda x: int(np.searchsorted(values, x)) if x in values else -1
+    from ..extraction.find_object_properties import _cs_device
+    lib, dev = L.load(), _cs_device(device)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    nb_d, eb_d, e_d, cls_d = up(node_begin), up(edge_begin), up(e), up(classes)
+    out_d = torch.empty(n, dtype=torch.uint8, device=dev)
+    counts_d = torch.zeros(8, dtype=torch.int64, device=dev)
+    tmp = torch.empty(lib.sd_skel_components_temp_bytes(n), dtype=torch.uint8, device=dev)
+    L.check(lib.sd_skel_components(e_d.data_ptr(), eb_d.data_ptr(), nb_d.data_ptr(), len(node_begin) - 1, n, len(e), cls_d.data_ptr(), find(soma_label),
+                                   find(1), max(find(0), 0), out_d.data_ptr(), counts_d.data_ptr(), tmp.data_ptr(), tmp.numel(),
+                                   torch.cuda.current_stream(dev).cuda_stream), 'sd_skel_components')
+    counts = _skel_counts('sd_skel_components', counts_d)
+    if int(counts[6]):
+        raise ValueError(f'{what}: a component of 2^24 nodes or more: the share of label 1 is not pinned there')
+    return values[out_d.cpu().numpy()].astype(lab.dtype, copy=False)
+
+
+def majorityvote_skeleton_property(sso, prop_key: str, max_dist: int = 10000, return_res: bool = False):
+    """Drop-in for ``majorityvote_skeleton_property`` (:1270-1302): the sliding-window majority vote of the integer property
+    ``sso.skeleton[prop_key]`` along the skeleton, stored as ``"%s_avg%d" % (prop_key, max_dist)`` or returned.  Reads ``skeleton``
+    (``nodes``, ``edges``, the property), ``scaling`` and ``id`` of a (duck-typed) ``sso``.  Does not call ``sso.save_skeleton()``."""
+    if prop_key not in sso.skeleton:
+        raise ValueError(f'Given property "{prop_key}" does not exist in '
+                         f'skeleton of SSV {sso.id}.')
+    nodes = np.asarray(sso.skeleton['nodes']).reshape(-1, 3)
+    edges = np.array(sso.skeleton['edges'], dtype=np.int64).reshape(-1, 2)
+    prop = np.asarray(sso.skeleton[prop_key])
+    avg_prop = skeleton_majority_vote(nodes, [0, len(nodes)], edges, [0, len(edges)], prop, sso.scaling, max_dist)
+    if return_res:
+        return avg_prop
+    sso.skeleton["%s_avg%d" % (prop_key, max_dist)] = avg_prop
+
+
+def majority_vote_compartments(sso, ax_pred_key: str = 'axoness'):
+    """Drop-in for ``majority_vote_compartments`` (:1233-1266): stores ``ax_pred_key + "_comp_maj"`` (float64, as the reference
+    does) and calls ``sso.save_skeleton()``."""
+    nodes = np.asarray(sso.skeleton['nodes']).reshape(-1, 3)
+    edges = np.array(sso.skeleton['edges'], dtype=np.int64).reshape(-1, 2)
+    pred = np.asarray(sso.skeleton[ax_pred_key])
+    res = skeleton_compartment_majority([0, len(nodes)], edges, [0, len(edges)], pred)
+    new_axoness_arr = np.zeros((len(nodes)))
+    new_axoness_arr[:] = res
+    sso.skeleton[ax_pred_key + "_comp_maj"] = new_axoness_arr
+    sso.save_skeleton()

@@ -1,0 +1,88 @@
+"""Drop-in for ``semsegaxoness2skel`` of ``syconn.reps.super_segmentation_object`` (/root/reference/syconn/reps/
+super_segmentation_object.py:3497-3557) and its table form over a ``CellTable``.  The three steps -- the vertex predictions at the
+skeleton nodes (``semseg_for_coords``, :2190-2240), the sliding-window vote (``majorityvote_skeleton_property``) and the compartment
+vote (``majority_vote_compartments``) -- run on the device for all cells of a call: one ``segmented_knn`` call, one
+``skeleton_majority_vote`` call, one ``skeleton_compartment_majority`` call.  No CPU fallback.
+"""
+import logging
+
+import numpy as np
+
+from .. import _lib as L
+from .super_segmentation_helper import skeleton_compartment_majority, skeleton_majority_vote
+
+log_reps = logging.getLogger('syconn_amd.reps')
+
+
+def _recover_boutons(node_preds, smoothed):
+    """Bouton predictions (3: en-passant, 4: terminal) come back where the smoothed label is axon (:3545-3546, :3554-3555)."""
+    smoothed[(node_preds == 3) & (smoothed == 1)] = 3
+    smoothed[(node_preds == 4) & (smoothed == 1)] = 4
+    return smoothed
+
+
+def _smooth(node_preds, nodes, node_begin, edges, edge_begin, scaling, max_dist, device):
+    """Node predictions -> (merged int32 labels, their sliding-window vote, the compartment vote as float64), :3531-3556."""
+    nodes_ax_den_so = np.array(node_preds, dtype=np.int32)
+    nodes_ax_den_so[nodes_ax_den_so == 3] = 1
+    nodes_ax_den_so[nodes_ax_den_so == 4] = 1
+    avg = _recover_boutons(node_preds, skeleton_majority_vote(nodes, node_begin, edges, edge_begin, nodes_ax_den_so, scaling, max_dist, device))
+    comp = np.zeros(len(avg))
+    comp[:] = skeleton_compartment_majority(node_begin, edges, edge_begin, avg, device=device)
+    return nodes_ax_den_so, avg, _recover_boutons(node_preds, comp)
+
+
+def semsegaxoness2skel_table(cells, edges, edge_begin, map_properties: dict, pred_key: str, max_dist, scaling, device=None) -> dict:
+    """``semsegaxoness2skel`` for all cells of a ``CellTable`` (``cs_processing_steps.CellTable``: vertices, ``vertex_labels[pred_key]``
+    and the skeleton nodes) plus their skeleton edges (`edges` (e, 2): node indices inside the cell, `edge_begin` (cells + 1)).
+    `map_properties`: ``k`` (<= 64), ``ds_vertices``, optionally ``ignore_labels``.  -> the node attributes ``pred_key`` (int32),
+    ``"{pred_key}_avg{max_dist}"`` (int32) and ``"{pred_key}_avg{max_dist}_comp_maj"`` (float64) for all nodes of the table.  The
+    nodes of a cell without mesh vertices get zeros in all three (the reference's branch for such a cell, :3520-3525)."""
+    from ..extraction.cs_processing_steps import CellTable, _check_positive_int, segmented_knn, spine_vertices
+    if not isinstance(cells, CellTable):
+        raise TypeError('cells must be a CellTable')
+    k, ds_vertices = map_properties['k'], map_properties['ds_vertices']
+    _check_positive_int(k=k, ds_vertices=ds_vertices)
+    if int(k) > L.SD_SYN_PROPS_MAX_K:
+        raise ValueError(f'k = {k}: at most {L.SD_SYN_PROPS_MAX_K} neighbours per query')
+    scaling = np.asarray(scaling)
+    n_nodes, n_vert = np.diff(cells.node_begin), np.diff(cells.vert_begin)
+    used = (n_nodes > 0) & (n_vert > 0)
+    node_preds = np.zeros(len(cells.nodes), np.int32)
+    if used.any():
+        verts, lab, begin = spine_vertices(cells, used, pred_key, int(ds_vertices), map_properties.get('ignore_labels'))
+        empty = np.flatnonzero(used & (np.diff(begin) == 0))
+        if len(empty):
+            raise ValueError(f'every mesh vertex of cell {int(cells.ids[empty[0]])} carries an ignored label: no vertex to vote')
+        cell_of = np.repeat(np.arange(len(cells)), n_nodes)
+        q = np.flatnonzero(used[cell_of])
+        q_xyz = np.asarray(cells.nodes[q] * scaling, np.float64)                # np.array(coords) * self.scaling (:2219)
+        node_preds[q] = segmented_knn(verts, begin, lab, cell_of[q], q_xyz, int(k), device)
+    merged, avg, comp = _smooth(node_preds, cells.nodes, cells.node_begin, edges, edge_begin, scaling, max_dist, device)
+    return {pred_key: merged, "{}_avg{}".format(pred_key, max_dist): avg, "{}_avg{}_comp_maj".format(pred_key, max_dist): comp}
+
+
+def semsegaxoness2skel(sso, map_properties: dict, pred_key: str, max_dist: int):
+    """Drop-in for ``semsegaxoness2skel`` (:3497-3557): populates ``sso.skeleton[pred_key]``, ``"{}_avg{}".format(pred_key, max_dist)``
+    and ``"{}_avg{}_comp_maj".format(pred_key, max_dist)`` and calls ``sso.save_skeleton()``.  Reads of a (duck-typed) ``sso``:
+    ``skeleton`` / ``load_skeleton``, ``mesh[1]``, ``label_dict('vertex')[pred_key]``, ``scaling``, ``id``."""
+    from ..extraction.cs_processing_steps import CellTable
+    if sso.skeleton is None:
+        sso.load_skeleton()
+    if sso.skeleton is None:
+        log_reps.warning(f"Skeleton of {sso} hdoes not exist.")
+        return
+    if len(sso.skeleton["nodes"]) == 0 or len(sso.mesh[1]) == 0:
+        log_reps.warning(f"Skeleton of {sso} has zero nodes or no mesh vertices.")
+        sso.skeleton["{}_avg{}".format(pred_key, max_dist)] = np.zeros((len(sso.skeleton['nodes']), 1))
+        sso.skeleton["{}_avg{}_comp_maj".format(pred_key, max_dist)] = np.zeros((len(sso.skeleton['nodes']), 1))
+        sso.save_skeleton()
+        return
+    nodes = np.asarray(sso.skeleton['nodes']).reshape(-1, 3)
+    edges = np.array(sso.skeleton['edges'], dtype=np.int64).reshape(-1, 2)
+    verts = np.asarray(sso.mesh[1]).reshape(-1, 3)
+    cells = CellTable([sso.id], verts, [0, len(verts)], {pred_key: sso.label_dict('vertex')[pred_key]}, nodes, [0, len(nodes)], {})
+    res = semsegaxoness2skel_table(cells, edges, [0, len(edges)], map_properties, pred_key, max_dist, sso.scaling)
+    for key, val in res.items():
+        sso.skeleton[key] = val
+    sso.save_skeleton()
