@@ -629,10 +629,14 @@ int sd_syn_props_forest(const double* rows_dev, size_t n_rows, int n_features, c
  *                        optional int32 output); nb_obj <= 1: id 1; else the id with the most voxels in labels[c - 10 : c + 11] per axis
  *                        with numpy's slice rules (a negative start wraps, so c < 10 on an axis empties the slice; the stop clips),
  *                        the smallest id on equal counts; if the slice holds no labelled voxel the object owning the voxel nearest to c
- *                        (distance ((v - c) * scaling_xyz)^2 summed in double: exact for integral scalings; ties: lowest id, then raster
- *                        index).  c_xyz HOST int64[3] = rep_coord - offset (mag-1 voxels indexing the zoomed volume, as the reference
- *                        does), scaling_xyz HOST double[3].  result_dev int32[3] = voxels of the chosen object (0 if nb_obj == 0), the
- *                        chosen id, nb_obj. */
+ *                        in the reference's own float64 arithmetic (:2189-2191, cKDTree): per axis d = (v + offset) * scaling -
+ *                        (c + offset) * scaling, both points scaled and then subtracted, d2 = ((dx dx) + dy dy) + dz dz with every
+ *                        product and sum rounded, never fused; ties in d2: lowest id, then raster index (the project's rule: cKDTree's
+ *                        pick among equal distances follows its tree order).  c_xyz HOST int64[3] = rep_coord - offset (mag-1 voxels
+ *                        indexing the zoomed volume, as the reference does), win_offset_xyz HOST int64[3] = the window offset (it moves
+ *                        the rounding of the scaled points, so it decides near-ties for non-integral voxel sizes; |v + offset| < 2^53),
+ *                        scaling_xyz HOST double[3].  result_dev int32[3] = voxels of the chosen object (0 if nb_obj == 0), the chosen
+ *                        id, nb_obj. */
 #define SD_SPINEHEAD_VOX_GRID 8192
 #define SD_SPINEHEAD_VERT_GRID 1024
 #define SD_SPINEHEAD_ID_GRID 1024
@@ -653,8 +657,8 @@ int sd_spinehead_queries(const int32_t* peaks_dev, const int32_t* n_peaks_dev, s
                          const double* ds_xyz, uint32_t* q_cell_dev, double* q_xyz_dev, void* stream);
 int sd_spinehead_markers(const int32_t* peaks_dev, const int32_t* n_peaks_dev, const int32_t* votes_dev, size_t max_peaks, int X, int Y, int Z,
                          int32_t* markers_dev, void* stream);
-int sd_spinehead_select(const int32_t* flood_dev, int X, int Y, int Z, const int64_t* c_xyz, const double* scaling_xyz, int32_t* objects_dev,
-                        int32_t* result_dev, void* workspace_dev, size_t ws_bytes, void* stream);
+int sd_spinehead_select(const int32_t* flood_dev, int X, int Y, int Z, const int64_t* c_xyz, const int64_t* win_offset_xyz, const double* scaling_xyz,
+                        int32_t* objects_dev, int32_t* result_dev, void* workspace_dev, size_t ws_bytes, void* stream);
 
 /* ---- majority votes along skeletons (csrc/sd_skeleton.hip) -------------------------------------------------------------
  * The array form of majorityvote_skeleton_property (/root/reference/syconn/reps/super_segmentation_helper.py:1270-1302, one

@@ -197,7 +197,7 @@ def load():
     lib.sd_spinehead_box_vertices.restype = i32
     lib.sd_spinehead_queries.argtypes = [vp, vp, sz, sz, sz, f64p, vp, vp, vp]; lib.sd_spinehead_queries.restype = i32
     lib.sd_spinehead_markers.argtypes = [vp, vp, vp, sz, i32, i32, i32, vp, vp]; lib.sd_spinehead_markers.restype = i32
-    lib.sd_spinehead_select.argtypes = [vp, i32, i32, i32, i64p, f64p, vp, vp, vp, sz, vp]; lib.sd_spinehead_select.restype = i32
+    lib.sd_spinehead_select.argtypes = [vp, i32, i32, i32, i64p, i64p, f64p, vp, vp, vp, sz, vp]; lib.sd_spinehead_select.restype = i32
     # reps/super_segmentation_helper.py:1270-1302 (majorityvote_skeleton_property) and :1233-1266 (majority_vote_compartments)
     lib.sd_skel_csr_temp_bytes.argtypes = [sz]; lib.sd_skel_csr_temp_bytes.restype = sz
     lib.sd_skel_csr.argtypes = [vp, vp, vp, sz, sz, sz, vp, vp, vp, vp, vp, vp, sz, vp]; lib.sd_skel_csr.restype = i32

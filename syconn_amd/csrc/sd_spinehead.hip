@@ -212,13 +212,19 @@ __global__ __launch_bounds__(256) void k_shs_head(const int* __restrict__ flood,
 __global__ __launch_bounds__(64) void k_shs_init(unsigned long long* sel) {
     if (threadIdx.x == 0) { sel[0] = ~0ull; sel[1] = 0ull; sel[2] = ~0ull; }
 }
-__device__ __forceinline__ double sh_dist2(int x, int y, int z, const I3& c, const D3& sc) {
-    const double dx = (double)((long long)x - c.v[0]) * sc.v[0], dy = (double)((long long)y - c.v[1]) * sc.v[1], dz = (double)((long long)z - c.v[2]) * sc.v[2];
-    return dx * dx + dy * dy + dz * dz;
+// squared distance of voxel (x, y, z) to c in the bits of cKDTree((coords + offset) * scaling).query([(c + offset) * scaling]) (:2189-2191): both
+// points scaled, then subtracted (the window offset moves the rounding of the products), ((dx dx) + dy dy) + dz dz.  The one definition for
+// k_shs_count and k_shs_nearest, which looks the minimum of the former up by equality: contraction is off HERE, so both get the same bits.
+__device__ __forceinline__ double sh_dist2(int x, int y, int z, const I3& off, const I3& c, const D3& sc) {
+#pragma clang fp contract(off)                              // every product and sum rounded on its own, as numpy / cKDTree do
+    const double dx = (double)((long long)x + off.v[0]) * sc.v[0] - (double)(c.v[0] + off.v[0]) * sc.v[0];
+    const double dy = (double)((long long)y + off.v[1]) * sc.v[1] - (double)(c.v[1] + off.v[1]) * sc.v[1];
+    const double dz = (double)((long long)z + off.v[2]) * sc.v[2] - (double)(c.v[2] + off.v[2]) * sc.v[2];
+    return ((dx * dx) + dy * dy) + dz * dz;
 }
 // voxels per object and per object inside the slice.  The voxels of an object are neighbours, so the lanes of a wave mostly hold one label:
 // per distinct label of the wave one lane adds the wave's count (a ballot per label) instead of 64 atomics on one address.
-__global__ __launch_bounds__(256) void k_shs_count(const int* __restrict__ L, int X, int Y, int Z, B6 box, I3 c, D3 sc, int* __restrict__ cnt, int* __restrict__ cbox,
+__global__ __launch_bounds__(256) void k_shs_count(const int* __restrict__ L, int X, int Y, int Z, B6 box, I3 off, I3 c, D3 sc, int* __restrict__ cnt, int* __restrict__ cbox,
                                                    unsigned long long* sel) {
     const size_t total = (size_t)X * Y * Z;
     const int lane = threadIdx.x & 63;
@@ -231,7 +237,7 @@ __global__ __launch_bounds__(256) void k_shs_count(const int* __restrict__ L, in
             int z, y, x;
             dec3(i, Z, Y, z, y, x);
             inb = x >= box.lo[0] && x < box.hi[0] && y >= box.lo[1] && y < box.hi[1] && z >= box.lo[2] && z < box.hi[2];
-            const unsigned long long b = (unsigned long long)__double_as_longlong(sh_dist2(x, y, z, c, sc));
+            const unsigned long long b = (unsigned long long)__double_as_longlong(sh_dist2(x, y, z, off, c, sc));
             best = b < best ? b : best;
         } else {
             l = 0;
@@ -257,7 +263,7 @@ __global__ __launch_bounds__(256) void k_shs_best(const int* __restrict__ cbox, 
         if (k > 0) atomicMax(sel + 1, ((unsigned long long)(unsigned)k << 32) | (unsigned long long)(0xffffffffu - (unsigned)id));
     }
 }
-__global__ __launch_bounds__(256) void k_shs_nearest(const int* __restrict__ L, int X, int Y, int Z, I3 c, D3 sc, unsigned long long* sel) {
+__global__ __launch_bounds__(256) void k_shs_nearest(const int* __restrict__ L, int X, int Y, int Z, I3 off, I3 c, D3 sc, unsigned long long* sel) {
     const size_t total = (size_t)X * Y * Z;
     const unsigned long long want = sel[0];
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
@@ -265,7 +271,7 @@ __global__ __launch_bounds__(256) void k_shs_nearest(const int* __restrict__ L, 
         if (l <= 0) continue;
         int z, y, x;
         dec3(i, Z, Y, z, y, x);
-        if ((unsigned long long)__double_as_longlong(sh_dist2(x, y, z, c, sc)) == want) atomicMin(sel + 2, ((unsigned long long)(unsigned)l << 32) | (unsigned long long)i);
+        if ((unsigned long long)__double_as_longlong(sh_dist2(x, y, z, off, c, sc)) == want) atomicMin(sel + 2, ((unsigned long long)(unsigned)l << 32) | (unsigned long long)i);
     }
 }
 // result: [0] voxels of the chosen object, [1] the chosen id, [2] nb_obj
@@ -432,9 +438,9 @@ int sd_spinehead_markers(const int32_t* peaks_dev, const int32_t* n_peaks_dev, c
     return launch_status("sd_spinehead_markers: launch failed");
 }
 
-int sd_spinehead_select(const int32_t* flood_dev, int X, int Y, int Z, const int64_t* c_xyz, const double* scaling_xyz, int32_t* objects_dev,
-                        int32_t* result_dev, void* ws, size_t ws_bytes, void* stream) {
-    if (!flood_dev || !c_xyz || !scaling_xyz || !result_dev || !ws || bad_dims(X, Y, Z)) return sd_fail_msg(SD_ERR_INVALID, "sd_spinehead_select: bad argument");
+int sd_spinehead_select(const int32_t* flood_dev, int X, int Y, int Z, const int64_t* c_xyz, const int64_t* win_offset_xyz, const double* scaling_xyz,
+                        int32_t* objects_dev, int32_t* result_dev, void* ws, size_t ws_bytes, void* stream) {
+    if (!flood_dev || !c_xyz || !win_offset_xyz || !scaling_xyz || !result_dev || !ws || bad_dims(X, Y, Z)) return sd_fail_msg(SD_ERR_INVALID, "sd_spinehead_select: bad argument");
     ShLayout l;
     if (ws_bytes < layout(l, ws, X, Y, Z)) return sd_fail_msg(SD_ERR_NOMEM, "sd_spinehead_select: workspace too small");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -446,7 +452,7 @@ int sd_spinehead_select(const int32_t* flood_dev, int X, int Y, int Z, const int
     const int g = grid_for(nvox, VG);
     const int ext[3] = {X, Y, Z};
     B6 box;
-    I3 c;
+    I3 off, c;
     D3 sc;
     for (int a = 0; a < 3; ++a) {      // labels[c - 10 : c + 11] with numpy's slice rules: a negative bound wraps once, then both clip to the extent
         long long lo = (long long)c_xyz[a] - 10, hi = (long long)c_xyz[a] + 11;
@@ -457,6 +463,7 @@ int sd_spinehead_select(const int32_t* flood_dev, int X, int Y, int Z, const int
         hi = hi < 0 ? 0 : (hi > n ? n : hi);
         box.lo[a] = (int)lo; box.hi[a] = (int)hi;
         c.v[a] = (long long)c_xyz[a];
+        off.v[a] = (long long)win_offset_xyz[a];
         sc.v[a] = scaling_xyz[a];
     }
     hipLaunchKernelGGL(k_shs_head, dim3(g), dim3(256), 0, s, flood_dev, nvox, head);
@@ -465,9 +472,9 @@ int sd_spinehead_select(const int32_t* flood_dev, int X, int Y, int Z, const int
     hipLaunchKernelGGL(k_sh_zero, dim3(grid_for(l.T, TG)), dim3(256), 0, s, cnt, l.T);
     hipLaunchKernelGGL(k_sh_zero, dim3(grid_for(l.T, TG)), dim3(256), 0, s, cbox, l.T);
     hipLaunchKernelGGL(k_shs_init, dim3(1), dim3(64), 0, s, sel);
-    hipLaunchKernelGGL(k_shs_count, dim3(g), dim3(256), 0, s, L, X, Y, Z, box, c, sc, cnt, cbox, sel);
+    hipLaunchKernelGGL(k_shs_count, dim3(g), dim3(256), 0, s, L, X, Y, Z, box, off, c, sc, cnt, cbox, sel);
     hipLaunchKernelGGL(k_shs_best, dim3(grid_for(l.T, TG)), dim3(256), 0, s, cbox, nb, sel);
-    hipLaunchKernelGGL(k_shs_nearest, dim3(g), dim3(256), 0, s, L, X, Y, Z, c, sc, sel);
+    hipLaunchKernelGGL(k_shs_nearest, dim3(g), dim3(256), 0, s, L, X, Y, Z, off, c, sc, sel);
     hipLaunchKernelGGL(k_shs_final, dim3(1), dim3(64), 0, s, cnt, nb, sel, result_dev);
     return launch_status("sd_spinehead_select: launch failed");
 }

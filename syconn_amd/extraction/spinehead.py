@@ -186,13 +186,13 @@ class WindowRunner:
                                           tmp.data_ptr(), tmp.numel(), self.stream), 'sd_syn_props_knn')
         self._knn_tmp = tmp
 
-    def flood_select(self, w, c_rel, scaling, objects=None):
+    def flood_select(self, w, c_rel, offset, scaling, objects=None):
         v = self.votes[w * self.q_slots:]                          # (a window with more peaks than max_peaks raises after the batch)
         L.check(self.lib.sd_spinehead_markers(self.peaks[w].data_ptr(), self._res_ptr(w, 1), v.data_ptr(), self.q_slots, self.X, self.Y, self.Z,
                                               self.markers.data_ptr(), self.stream), 'sd_spinehead_markers')
         L.check(self.lib.sd_marker_flood(self.d2[w].data_ptr(), self.markers.data_ptr(), self.filled[w].data_ptr(), self.X, self.Y, self.Z,
                                          self.flood.data_ptr(), self.max_label.data_ptr(), self.ws.data_ptr(), self.ws_bytes, self.stream), 'sd_marker_flood')
-        L.check(self.lib.sd_spinehead_select(self.flood.data_ptr(), self.X, self.Y, self.Z, _i64x3(c_rel), _f64x3(scaling),
+        L.check(self.lib.sd_spinehead_select(self.flood.data_ptr(), self.X, self.Y, self.Z, _i64x3(c_rel), _i64x3(offset), _f64x3(scaling),
                                              None if objects is None else objects.data_ptr(), self._res_ptr(w, 2), self.ws.data_ptr(),
                                              self.ws_bytes, self.stream), 'sd_spinehead_select')
 
@@ -220,7 +220,7 @@ class WindowRunner:
                 continue
             import torch
             objects = torch.empty_like(self.flood) if keep is not None else None
-            self.flood_select(w, c_rel[w], scaling, objects)
+            self.flood_select(w, c_rel[w], offsets[w], scaling, objects)
             if keep is not None:
                 keep[len(keep) - n + w].update(markers=self.markers.clone(), flood=self.flood.clone(), objects=objects)
         buf = self.buf.cpu().numpy()                              # the one copy back of the batch

@@ -70,24 +70,60 @@ def vote(queries, points, labels, k):
     return np.array([Counter(np.asarray(labels)[i].tolist()).most_common(1)[0][0] for i in ixs], np.int32).reshape(-1)
 
 
-def select_head(flood, c, offset, scaling):
-    """:2171-2196 -> (objects, nb_obj, chosen id, its voxel count)."""
+def nearest_d2(coords, c, offset, scaling):
+    """The array form of what ``cKDTree((coords + offset) * scaling).query([(c + offset) * scaling])`` measures (:2189-2191): per axis
+    ``(x + off) * s - (c + off) * s`` -- both points scaled in the dtype numpy gives the product, held as float64 (cKDTree's own copy),
+    then subtracted -- squared and summed in axis order, float64 with every operation rounded.  -> (n) float64."""
+    sc, off = np.asarray(scaling), np.asarray(offset)
+    p = np.asarray((np.asarray(coords) + off) * sc, np.float64).reshape(-1, 3)
+    q = np.asarray((np.asarray(c) + off) * sc, np.float64).reshape(3)
+    d = p - q
+    return ((d[:, 0] * d[:, 0]) + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+
+
+def nearest_object(objects, nb_obj, c, offset, scaling):
+    """The branch :2182-2192 in the reference's own words, `scaling` in the dtype it is given -> dict: ``ref_id`` the reference's pick
+    (cKDTree), ``dist`` its returned distance, ``d2`` / ``ids`` the array form per object voxel (objects in id order, raster order
+    inside one), ``decided``: the smallest d2 of the nearest object is strictly below that of every other object in this arithmetic,
+    ``chosen``: ``ref_id`` if decided; else -- an exact float64 tie between objects, where cKDTree's pick is an artefact of its tree
+    order -- THE PROJECT'S RULE, not the reference's: the lowest id among the tied objects."""
+    coords, ids = [], []
+    for ii in range(1, nb_obj + 1):
+        curr_coords = np.transpose(np.nonzero(objects == ii))
+        coords.append(curr_coords)
+        ids.extend(len(curr_coords) * [ii])
+    coords = np.concatenate(coords) + offset
+    nn_kdt = spatial.cKDTree(coords * scaling)
+    dist, nn_id = nn_kdt.query([(np.asarray(c) + offset) * scaling])
+    ids = np.array(ids, np.int64)
+    d2 = nearest_d2(coords - offset, c, offset, scaling)
+    per_obj = np.array([d2[ids == ii].min() for ii in range(1, nb_obj + 1)])
+    tied = 1 + np.flatnonzero(per_obj == per_obj.min())
+    decided = len(tied) == 1
+    ref_id = int(ids[nn_id[0]])
+    return dict(ref_id=ref_id, dist=float(dist[0]), d2=d2, ids=ids, decided=decided, chosen=ref_id if decided else int(tied.min()))
+
+
+def select_head(flood, c, offset, scaling, info=None):
+    """:2171-2196 -> (objects, nb_obj, chosen id, its voxel count).  `info`: an optional dict that receives ``branch`` ('single',
+    'slice' or 'nearest') and, for 'nearest', the entries of ``nearest_object``."""
     objects, nb_obj = ndimage.label(flood == 1)
     max_id = 1
+    branch = 'single'
     if nb_obj > 1:
         c = [int(v) for v in c]
         ls = objects[(c[0] - 10):(c[0] + 11), (c[1] - 10):(c[1] + 11), (c[2] - 10):(c[2] + 11)]      # a negative start wraps: empty for c < 10
         ids, cnts = np.unique(ls, return_counts=True)
         cnts, ids = cnts[ids != 0], ids[ids != 0]
         if len(ids) == 0:
-            coords = np.transpose(np.nonzero(objects)).astype(np.int64)
-            owner = objects[tuple(coords.T)]
-            d = ((coords + np.asarray(offset, np.int64)) - (np.asarray(c, np.int64) + np.asarray(offset, np.int64))) * np.asarray(scaling).astype(np.float64)
-            d2 = (d * d).sum(1)
-            best = np.flatnonzero(d2 == d2.min())
-            max_id = int(owner[best].min())                                                          # (ties: the lowest id; g22 has none)
+            near = nearest_object(objects, nb_obj, np.asarray(c, np.int64), np.asarray(offset, np.int64), scaling)
+            max_id, branch = near['chosen'], 'nearest'
+            if info is not None:
+                info.update(near)
         else:
-            max_id = int(ids[np.argmax(cnts)])
+            max_id, branch = int(ids[np.argmax(cnts)]), 'slice'
+    if info is not None:
+        info['branch'] = branch
     return objects.astype(np.int32), int(nb_obj), max_id, int(np.sum(objects == max_id))
 
 

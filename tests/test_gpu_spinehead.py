@@ -83,14 +83,25 @@ def test_golden_windows_stage_by_stage(gpu, g22, p):
 RANDOM = [((17, 33, 9), 3), ((16, 16, 16), 4), ((40, 23, 31), 5), ((33, 40, 17), 6), ((21, 19, 38), 7)]
 
 
-@pytest.mark.parametrize('shape,seed', RANDOM)
-def test_random_windows_stage_by_stage(gpu, shape, seed):
-    """Blobs and sticks, rows that are no multiple of a mask word; one window = the whole volume (identity zoom), two supervoxel ids of
-    which the cell owns one or both; random vertices labelled by the side of a plane they are on, so that several head objects form."""
+VOXEL_SIZES = [('', np.array([10, 10, 10])), ('-9.1-float64', np.array([9.1, 9.1, 22.5], np.float64)), ('-9.1-float32', np.array([9.1, 9.1, 22.5], np.float32))]
+
+
+@pytest.mark.parametrize('shape,seed,scaling', [(sh, seed, sc) for _, sc in VOXEL_SIZES for sh, seed in RANDOM],
+                         ids=[f'shape{i}-{seed}{tag}' for tag, _ in VOXEL_SIZES for i, (_, seed) in enumerate(RANDOM)])
+def test_random_windows_stage_by_stage(gpu, shape, seed, scaling):
+    """Blobs and sticks, rows that are no multiple of a mask word; one window = the whole volume, two supervoxel ids of which the cell
+    owns one or both; random vertices labelled by the side of a plane they are on, so that several head objects form.  Voxel size
+    (10, 10, 10): the identity zoom; (9.1, 9.1, 22.5): ds = (2, 2, 1), so the zoom tables and ``maxima * ds`` count, and the distances of
+    the head selection are no longer exact; the window then has ``shape * ds`` voxels, every blob voxel repeated ds times,
+    so that the zoomed volume has `shape` and blobs as thick."""
     import torch
     from syconn_amd.extraction import spinehead as SH
     rng = np.random.default_rng(seed)
-    m = R.blob_volume(shape, seed)
+    ds = scaling[2] // scaling
+    zoomed, shape = shape, tuple(int(n * d) for n, d in zip(shape, ds))
+    m = R.blob_volume(zoomed, seed)
+    for a in range(3):
+        m = np.repeat(m, int(ds[a]), a)                                        # (the zoom samples it back with scipy's drifting step)
     ids = np.where(np.indices(shape)[1] < shape[1] // 2, 7, 9).astype(np.uint64)
     vol = np.where(m > 0, ids, np.uint64(3))                                   # a foreign id in the background
     sv = np.array([7, 9] if seed % 2 else [9, 7, 7], np.uint64)
@@ -99,19 +110,20 @@ def test_random_windows_stage_by_stage(gpu, shape, seed):
     surf = np.transpose(np.nonzero(m))
     verts = surf[rng.permutation(len(surf))[:300]] + rng.uniform(0.05, 0.95, (min(300, len(surf)), 3))
     labels = np.where(verts[:, 0] + verts[:, 2] * 0.5 < (shape[0] + shape[2] * 0.5) * 0.5, 1, np.where(rng.random(len(verts)) < 0.5, 0, 2)).astype(np.int32)
-    scaling = np.array([10, 10, 10])
     k = 7
-    runner = SH.WindowRunner(shape, batch=2, device=gpu)
-    tabs = [torch.arange(n, dtype=torch.int32, device=runner.dev) for n in shape]
+    tabs_h = [SH.zoom_source_table(n, d) for n, d in zip(shape, ds)]
+    assert [len(t) for t in tabs_h] == list(zoomed)
+    runner = SH.WindowRunner([len(t) for t in tabs_h], batch=2, device=gpu)
+    tabs = [torch.from_numpy(t).to(runner.dev) for t in tabs_h]
     seg_d = torch.from_numpy(vol.view(np.int64)).to(runner.dev)
     sv_d = torch.from_numpy(np.unique(sv).view(np.int64)).to(runner.dev)
     verts_d, lab_d = torch.from_numpy(verts).to(runner.dev), torch.from_numpy(labels).to(runner.dev)
-    cs = np.array([[s // 2 for s in shape], [3, 2, 4]], np.int64)              # the slice around the first holds voxels, the second wraps
+    cs = np.array([[s // 2 for s in zoomed], [3, 2, 4]], np.int64)              # the slice around the first holds voxels, the second wraps
     keep = []
-    res = runner.run_batch(seg_d, (0, 0, 0), np.zeros((2, 3), np.int64), tabs, sv_d, verts_d, lab_d, np.array(shape, np.int32), np.ones(3), k, cs,
+    res = runner.run_batch(seg_d, (0, 0, 0), np.zeros((2, 3), np.int64), tabs, sv_d, verts_d, lab_d, np.array(shape, np.int32), ds.astype(np.float64), k, cs,
                            scaling.astype(np.float64), keep)
     for w in range(2):
-        want = R.window_stages(vol, sv, (1, 1, 1), verts, labels, np.zeros(3, np.int64), np.array(shape), cs[w], scaling, k)
+        want = R.window_stages(vol, sv, ds, verts, labels, np.zeros(3, np.int64), np.array(shape), cs[w], scaling, k)
         assert want['entry'] and len(want['peaks']) > 0
         assert_stages(keep[w], want, (shape, w))
         assert res[w].tolist() == [want['filled'].sum(), len(want['peaks']), want['n_voxels'], want['chosen'], want['nb_obj'], len(want['points'])]

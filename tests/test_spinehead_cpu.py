@@ -1,7 +1,8 @@
 """CPU: the restatement of the spine head volumes (tests/_spinehead_ref.py) against golden g22 (the reference's own
 ``extract_spinehead_volume_mesh`` on stand-ins, tests/golden/make_golden_spinehead.py) bit for bit, the zoom table builder of
 ``syconn_amd.extraction.spinehead`` against scipy, the region plan of the dataset reads, and the argument checks of the public functions, which
-raise before any launch."""
+raise before any launch.  The head selection (``select_head``): its array form of the nearest-object distances against cKDTree's own bit for bit
+on the hand-built volumes of tests/_spinehead_select_cases.py, which of those cases the reference's arithmetic decides, and the slice rule."""
 import os
 import sys
 
@@ -12,6 +13,7 @@ from scipy import ndimage
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import _spinehead_ref as R  # noqa: E402
+import _spinehead_select_cases as K  # noqa: E402
 
 from syconn_amd.extraction import spinehead as SH  # noqa: E402
 from syconn_amd.extraction.cs_processing_steps import CellTable, calculate_spinehead_volume  # noqa: E402
@@ -41,6 +43,65 @@ def test_restatement_matches_the_reference(g22, p):
             assert isinstance(got[s], np.float64) and got[s] == want[s], (cell['id'], s, got[s], want[s])
         n_entries += len(want)
     assert n_entries > 0
+
+
+def _select(case):
+    info = {}
+    objects, nb_obj, chosen, n_vox = R.select_head(case['flood'], case['c'], case['offset'], case['scaling'], info)
+    return info, (chosen, n_vox, nb_obj)
+
+
+@pytest.mark.parametrize('name,scaling', K.SCALINGS, ids=[n for n, _ in K.SCALINGS])
+def test_nearest_array_form_is_ckdtrees_distance(name, scaling):
+    """``nearest_d2`` -- both points scaled, then subtracted, ((dx dx) + dy dy) + dz dz in float64 with every operation rounded -- gives
+    the distance cKDTree returns bit for bit, and, wherever one object is strictly nearest in it, cKDTree's pick; for voxel sizes as
+    float64 and as float32, with window offsets and without.  Every random case is decided; the mirrored pairs around an unsymmetric c or
+    with an offset are decided by the reference's rounding for the float64 non-integer sizes only (the products of a float32 or an
+    integral voxel size with these integers are exact, so those pairs stay exact ties)."""
+    cases = [K.random_objects(seed, off, scaling) for off in K.OFFSETS for seed in K.RANDOM_SEEDS]
+    n_random = len(cases)
+    for c, off in K.NEAR_TIES:
+        cases += K.mirrored(c, off, scaling, K.N_NEAR, seed=2)
+    decided = []
+    for i, case in enumerate(cases):
+        info, (chosen, n_vox, nb_obj) = _select(case)
+        assert info['branch'] == 'nearest' and nb_obj >= 2
+        assert np.float64(np.sqrt(info['d2'].min())).tobytes() == np.float64(info['dist']).tobytes(), (name, i)
+        if info['decided']:
+            assert chosen == info['ref_id'] == info['ids'][np.argmin(info['d2'])], (name, i)
+        else:
+            assert chosen <= info['ref_id']                          # the project's rule: the lowest of the tied ids
+        assert info['decided'] or i >= n_random, (name, i)
+        if i >= n_random:
+            decided.append(chosen if info['decided'] else 0)
+    inexact = scaling.dtype == np.float64 and name != '10-control'
+    assert ({1, 2} <= set(decided)) == inexact and (0 in decided or inexact)
+
+
+@pytest.mark.parametrize('name,scaling', K.SCALINGS, ids=[n for n, _ in K.SCALINGS])
+def test_mirrored_pairs_tie_exactly(name, scaling):
+    """c[0] == c[1], equal x and y voxel sizes, offset 0: the voxels c + (a, b, k) and c + (b, a, k) are exact ties in the reference's
+    arithmetic, so the project's rule picks id 1, the first in raster order, with its single voxel."""
+    cases = K.mirrored((30, 30, 4), (0, 0, 0), scaling, K.N_MIRRORED, seed=1)
+    assert len(cases) >= 100
+    for case in cases:
+        info, got = _select(case)
+        assert info['branch'] == 'nearest' and not info['decided'] and got == (1, 1, 2)
+        assert len(info['d2']) == 2 and info['d2'][0].tobytes() == info['d2'][1].tobytes()
+
+
+def test_slice_rule_cases():
+    """The directed cases give what was worked out by hand; the random ones reach both branches, every (extent, c) pair on every axis."""
+    for name, case, want in K.directed_slice_cases():
+        assert _select(case)[1] == want, name
+    cases = K.slice_cases()
+    pairs = set(K.axis_pairs())
+    assert len(pairs) == 41 and (9, 8) in pairs and (9, 9) not in pairs and (33, 21) in pairs and (20, 8) in pairs
+    for a in range(3):
+        assert {(c['flood'].shape[a], int(c['c'][a])) for c in cases} == pairs
+    branches = [_select(c)[0]['branch'] for c in cases]
+    assert branches.count('slice') >= 30 and branches.count('nearest') >= 30
+    assert all(set(np.unique(c['flood']).tolist()) == {0, 1, 2, 9} for c in cases)
 
 
 def test_golden_holds_its_cases(g22):

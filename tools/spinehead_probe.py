@@ -95,7 +95,7 @@ def main():
             runner.vote(1, pts, lab, ds.astype(np.float64), K)
         ev[3].record()
         if len(pts):
-            runner.flood_select(0, rep - off, SCALING.astype(np.float64))
+            runner.flood_select(0, rep - off, off, SCALING.astype(np.float64))
         ev[4].record()
         out = runner.res32[0].cpu().numpy()
         wall = time.perf_counter() - t0
