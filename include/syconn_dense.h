@@ -712,6 +712,72 @@ int sd_skel_components(const int64_t* edges_dev, const uint64_t* edge_begin_dev,
                        size_t n_edges, const uint8_t* classes_dev, int soma_class, int one_class, int zero_class, uint8_t* out_dev,
                        uint64_t* counts_dev, void* temp_dev, size_t temp_bytes, void* stream);
 
+/* ---- cells from the supervoxel graph, organelles to cells (csrc/sd_cell_assembly.hip) -----------------------------------
+ * The array form of /root/reference/syconn/exec/exec_init.py run_create_rag (:299-367) and the apply_ssv_size_threshold branch of
+ * run_create_neuron_ssd (:61-80) with proc/graphs.py create_ccsize_dict (:220-249); of the cell properties of reps/
+ * super_segmentation_object.py (:713-727, :1148-1168); of proc/sd_proc.py:1063-1084 with proc/ssd_proc.py
+ * _aggregate_segmentation_object_mappings_thread (:55-91) and _apply_mapping_decisions_thread (:126-238); and of
+ * map_synssv_objects_thread (:315-342).  Ids use all 64 bits, 0 is "no object".  A supervoxel table is ids_dev uint64[n_ids] strictly
+ * ascending, sizes_dev int64[n_ids] (voxels), rep_coords_dev int32[n_ids][3], box_begin_dev uint64[n_ids + 1] (ascending from 0 to
+ * n_boxes) into boxes_dev int32[n_boxes][6] (min | max, one box per chunk that holds the id).  Cells are a CSR table: sv_begin_dev
+ * uint64[n_cells + 1] into sv_ids_dev uint64[n_sv].  counts_dev uint64[8] is zeroed by every call; counts[7] != 0: an offset table does
+ * not ascend from 0 to its total or an id table does not ascend strictly (nothing is read out of range through either).  Every count
+ * per call stays below 2^31 (SD_ERR_INVALID beyond).  Asynchronous on the stream; no float atomics anywhere.
+ *   sd_svgraph_components  edges_dev uint64[n_edges][2] (self loops, duplicates and endpoints 0 are legal).  Nodes = the table ids and
+ *                        every endpoint, without 0 (:319-320, with its edges); a table id without an edge is a component of its own
+ *                        (:327-330).  node_ids_dev uint64[n_ids + 2 n_edges] = the nodes ascending, counts[0] of them; node_comp_dev =
+ *                        per node the smallest id of its component (the reference's cc_dict key, :80), or 0 where the component is
+ *                        dropped; node_size_dev double = per node the size of its component, create_ccsize_dict's value:
+ *                        sqrt(((dx dx) + dy dy) + dz dz) over d = max * scaling - min * scaling of ALL corners of all boxes of the
+ *                        component's table supervoxels (an endpoint outside the table joins the component and has no box), every
+ *                        product and sum rounded on its own, the root correctly rounded.  A component without any box: counts[6] = 1,
+ *                        counts[5] = one of its ids (the reference raises ValueError, graphs.py:241-242).  Dropped: size <=
+ *                        min_cc_size (strict != 0, :349) or size < min_cc_size (strict == 0, :75).  The kept cells as CSR:
+ *                        ssv_ids_dev ascending (counts[1] cells), sv_begin_dev, sv_ids_dev ascending inside a cell (counts[2]); arrays
+ *                        of n_ids + 2 n_edges (+ 1) entries.  edges_out_dev uint64[n_edges][2] = the edges whose component is kept, in
+ *                        input order (counts[3]; the pruned graph, :359).  counts[4] = the voxels of the kept table supervoxels
+ *                        (total_size, :352-354).  scaling_xyz HOST double[3] > 0.  Scratch: sd_svgraph_components_temp_bytes.
+ *   sd_cell_props        per cell of a CSR table (any order inside a cell): cell_size_dev int64 = the sum of its supervoxels' sizes
+ *                        (:1152), cell_box_dev int32[6] = min of the lower, max of the upper corners (:1166-1167), cell_rep_dev
+ *                        int32[3] = the representative coordinate of its FIRST supervoxel (:725).  counts[0] = supervoxels that are not
+ *                        in the table (counts[5] = one of them): they contribute nothing; a cell without a known supervoxel has size
+ *                        0 and the zero box (:1158-1161).
+ *   sd_cell_mapping      records (rec_sub_dev organelle id, rec_sv_dev supervoxel id, rec_count_dev int64 voxels) of ONE organelle
+ *                        kind, in any order; org_ids_dev / org_sizes_dev its table.  A record is dropped when its organelle is not in
+ *                        the table (sd_proc.py:1075-1077), its supervoxel is 0 or in no cell, or its count is <= 0 (a Counter keeps no
+ *                        such entry).  ratio = count / size in float64 (:1081); per (cell, organelle) the ratios are added ONE AFTER
+ *                        ANOTHER in the order of the cell's supervoxel list, starting from 0.0 (Counter.__iadd__, ssd_proc.py:83).
+ *                        Pairs ascend by (cell row, organelle id): cell_begin_dev uint64[n_cells + 1] into pair_org_dev /
+ *                        pair_ratio_dev / pair_accepted_dev (n_records entries each, counts[1] used).  Accepted (:222-231): ratio >
+ *                        lower_ratio, and ratio <= upper_ratio unless upper_ratio >= 1, and (double) size > size_threshold.
+ *                        acc_begin_dev uint64[n_cells + 1] into acc_org_dev (counts[2]): the accepted organelles per cell.
+ *                        org_n_cells_dev uint32[n_org] = accepting cells, org_first_cell_dev uint32[n_org] = the smallest row among
+ *                        them (0xffffffff: none).  counts[0] = records kept.  counts[6] != 0: a supervoxel appears twice in the cell
+ *                        lists, or 0 does.  Scratch: sd_cell_mapping_temp_bytes(n_records, n_sv).
+ *   sd_cell_synapses     partners_dev uint64[n_syn][2], keep_dev uint8[n_syn] (the caller's `syn_prob > thresh`, :329-330),
+ *                        ssv_ids_dev uint64[n_cells] strictly ascending.  syn_begin_dev uint64[n_cells + 1] into out_ids_dev
+ *                        uint64[2 n_syn] (counts[0] used): per cell the kept syn_ids_dev with the cell in slot 0, in row order, then
+ *                        those with it in slot 1 (:338-340).  Scratch: sd_cell_synapses_temp_bytes(n_syn).
+ * One grid stride of every kernel is SD_CELLASM_GRID blocks of 256 items. */
+#define SD_CELLASM_GRID 1024
+size_t sd_svgraph_components_temp_bytes(size_t n_ids, size_t n_edges);
+int sd_svgraph_components(const uint64_t* edges_dev, size_t n_edges, const uint64_t* ids_dev, const int64_t* sizes_dev, const uint64_t* box_begin_dev,
+                          const int32_t* boxes_dev, size_t n_ids, size_t n_boxes, const double* scaling_xyz, double min_cc_size, int strict,
+                          uint64_t* node_ids_dev, uint64_t* node_comp_dev, double* node_size_dev, uint64_t* ssv_ids_dev, uint64_t* sv_begin_dev,
+                          uint64_t* sv_ids_dev, uint64_t* edges_out_dev, uint64_t* counts_dev, void* temp_dev, size_t temp_bytes, void* stream);
+int sd_cell_props(const uint64_t* sv_begin_dev, const uint64_t* sv_ids_dev, size_t n_cells, size_t n_sv, const uint64_t* ids_dev, const int64_t* sizes_dev,
+                  const int32_t* rep_coords_dev, const uint64_t* box_begin_dev, const int32_t* boxes_dev, size_t n_ids, size_t n_boxes,
+                  int64_t* cell_size_dev, int32_t* cell_box_dev, int32_t* cell_rep_dev, uint64_t* counts_dev, void* stream);
+size_t sd_cell_mapping_temp_bytes(size_t n_records, size_t n_sv);
+int sd_cell_mapping(const uint64_t* rec_sub_dev, const uint64_t* rec_sv_dev, const int64_t* rec_count_dev, size_t n_records, const uint64_t* org_ids_dev,
+                    const int64_t* org_sizes_dev, size_t n_org, const uint64_t* sv_begin_dev, const uint64_t* sv_ids_dev, size_t n_cells, size_t n_sv,
+                    double lower_ratio, double upper_ratio, double size_threshold, uint64_t* cell_begin_dev, uint64_t* pair_org_dev,
+                    double* pair_ratio_dev, uint8_t* pair_accepted_dev, uint64_t* acc_begin_dev, uint64_t* acc_org_dev, uint32_t* org_n_cells_dev,
+                    uint32_t* org_first_cell_dev, uint64_t* counts_dev, void* temp_dev, size_t temp_bytes, void* stream);
+size_t sd_cell_synapses_temp_bytes(size_t n_syn);
+int sd_cell_synapses(const uint64_t* partners_dev, const uint8_t* keep_dev, const uint64_t* syn_ids_dev, size_t n_syn, const uint64_t* ssv_ids_dev,
+                     size_t n_cells, uint64_t* syn_begin_dev, uint64_t* out_ids_dev, uint64_t* counts_dev, void* temp_dev, size_t temp_bytes, void* stream);
+
 /* ---- host-side helpers of the chunk pipeline (no GPU) -----------------------------------------------------------------
  * Multi-threaded strided copy of an (nz, ny, nx)-byte box between two uint8 host arrays whose x-rows are contiguous
  * (strides in bytes), and a multi-threaded memset: what numpy slicing does on one core when the reference cuts a chunk

@@ -17,6 +17,7 @@ SD_SYNSSV_MAP_ITEM = 1024
 SD_SPINEHEAD_VOX_GRID, SD_SPINEHEAD_VERT_GRID, SD_SPINEHEAD_ID_GRID = 8192, 1024, 1024
 SD_SYN_PROPS_MAX_K, SD_SYN_PROPS_CELL_GRID, SD_SYN_PROPS_POINT_GRID, SD_SYN_PROPS_QUERY_GRID, SD_SYN_PROPS_FOREST_GRID = 64, 4096, 1024, 8192, 1024
 SD_SKEL_MAX_CLASSES, SD_SKEL_LDS_NODES, SD_SKEL_VOTE_GRID, SD_SKEL_NODE_GRID, SD_SKEL_EDGE_GRID, SD_SKEL_REDO_GRID, SD_SKEL_REDO_BYTES = 64, 512, 2048, 1024, 1024, 1024, 1 << 28
+SD_CELLASM_GRID = 1024
 
 LIB_NAME = 'libsyconn_dense_hip.so'
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), os.environ.get('SD_LIB_NAME', LIB_NAME))
@@ -39,7 +40,9 @@ EXPORTS = ['sd_init', 'sd_device_count', 'sd_model_create', 'sd_model_destroy', 
            'sd_syn_props_knn_temp_bytes', 'sd_syn_props_knn', 'sd_syn_props_forest', 'sd_spinehead_workspace_bytes', 'sd_edt_squared',
            'sd_spinehead_window_mask', 'sd_spinehead_fill_holes', 'sd_spinehead_peaks', 'sd_spinehead_box_vertices_temp_bytes',
            'sd_spinehead_box_vertices', 'sd_spinehead_queries', 'sd_spinehead_markers', 'sd_spinehead_select', 'sd_skel_csr_temp_bytes', 'sd_skel_csr',
-           'sd_skel_vote_temp_bytes', 'sd_skel_vote', 'sd_skel_components_temp_bytes', 'sd_skel_components']
+           'sd_skel_vote_temp_bytes', 'sd_skel_vote', 'sd_skel_components_temp_bytes', 'sd_skel_components',
+           'sd_svgraph_components_temp_bytes', 'sd_svgraph_components', 'sd_cell_props', 'sd_cell_mapping_temp_bytes', 'sd_cell_mapping',
+           'sd_cell_synapses_temp_bytes', 'sd_cell_synapses']
 
 
 class OpDesc(C.Structure):
@@ -205,6 +208,16 @@ def load():
     lib.sd_skel_vote.argtypes = [vp, vp, vp, sz, vp, sz, sz, sz, vp, i32, C.c_double, vp, vp, vp, vp, sz, vp]; lib.sd_skel_vote.restype = i32
     lib.sd_skel_components_temp_bytes.argtypes = [sz]; lib.sd_skel_components_temp_bytes.restype = sz
     lib.sd_skel_components.argtypes = [vp, vp, vp, sz, sz, sz, vp, i32, i32, i32, vp, vp, vp, sz, vp]; lib.sd_skel_components.restype = i32
+    # exec/exec_init.py:299-367, :61-80 with proc/graphs.py:220-249 (cells from the supervoxel graph), reps/super_segmentation_object.py:713-727,
+    # :1148-1168 (cell properties), proc/sd_proc.py:1063-1084 with proc/ssd_proc.py:55-91, :126-238 (organelles to cells), :315-342 (synapses)
+    f64 = C.c_double
+    lib.sd_svgraph_components_temp_bytes.argtypes = [sz, sz]; lib.sd_svgraph_components_temp_bytes.restype = sz
+    lib.sd_svgraph_components.argtypes = [vp, sz, vp, vp, vp, vp, sz, sz, f64p, f64, i32] + [vp] * 8 + [vp, sz, vp]; lib.sd_svgraph_components.restype = i32
+    lib.sd_cell_props.argtypes = [vp, vp, sz, sz, vp, vp, vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]; lib.sd_cell_props.restype = i32
+    lib.sd_cell_mapping_temp_bytes.argtypes = [sz, sz]; lib.sd_cell_mapping_temp_bytes.restype = sz
+    lib.sd_cell_mapping.argtypes = [vp, vp, vp, sz, vp, vp, sz, vp, vp, sz, sz, f64, f64, f64] + [vp] * 9 + [vp, sz, vp]; lib.sd_cell_mapping.restype = i32
+    lib.sd_cell_synapses_temp_bytes.argtypes = [sz]; lib.sd_cell_synapses_temp_bytes.restype = sz
+    lib.sd_cell_synapses.argtypes = [vp, vp, vp, sz, vp, sz, vp, vp, vp, vp, sz, vp]; lib.sd_cell_synapses.restype = i32
     _lib = lib
     return lib
 

@@ -27,6 +27,8 @@ DEFAULTS = {
     # synapse-type datasets (config.py:700-707): False = no sym / asym masks (cs_extraction_steps.py:431-433)
     'syntype_avail': False,
     'process_cell_organelles': ['mi', 'vc'],      # config.yml:15
+    # cells from the supervoxel graph (config.yml:60): components whose bounding box diagonal (nm) is not above this are dropped
+    'min_cc_size_ssv': 5000,
     'dense_prediction': {
         'overlap_shape_tiles': [30, 31, 20],   # xyz, prediction.py:672
         'chunk_size': [482, 481, 236],         # prediction.py:674
@@ -77,6 +79,11 @@ DEFAULTS = {
         'max_rep_coord_dist_nm': 4000,
         # export_matrix(threshold_syn=None) keeps the synapses with a probability above this (config.yml:161)
         'thresh_synssv_proba': 0.5,
+        # organelles to cells (config.yml:92-106): an organelle belongs to a cell that holds more than the lower and at most the upper
+        # share of its voxels (an upper ratio of 1 or more is not tested) if it has more voxels than the size threshold
+        'lower_mapping_ratios': {'mi': 0.5, 'sj': 0.1, 'vc': 0.5},
+        'upper_mapping_ratios': {'mi': 1., 'sj': 0.9, 'vc': 1.},
+        'sizethresholds': {'mi': 2786, 'sj': 498, 'vc': 1584},
     },
     # partner properties of the cell-level synapses (config.yml:271-274, :278, :288, :303): the vote over the k nearest mesh vertices
     # (every ds_vertices-th one, without the ignored labels), the skeleton key of the compartment, the length of the embedding
