@@ -19,7 +19,7 @@
 // inside every segment whatever order the records of one chunk were appended in.
 #include "../../include/syconn_dense.h"
 #include "sd_sortseg.h"
-#include "sd_pointtiles.h"
+#include "sd_tables.h"
 
 namespace {
 
@@ -31,7 +31,7 @@ __global__ __launch_bounds__(256) void k_csm_append(const int64_t* __restrict__ 
                                                     u64* cursors) {
     const int off[3] = {ox, oy, oz};
     const u64 vbase = cursors[2];                           // advanced by k_csm_vox_advance after this kernel
-    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256) {
+    for (u64 i = grid_tid(); i < n; i += grid_stride()) {
         const int64_t* r = rec + i * SD_CST_COLS;
         const u64 o = atomicAdd(&cursors[0], 1ull);
         if (o < max_cs) {
@@ -59,7 +59,7 @@ __global__ __launch_bounds__(256) void k_csm_append(const int64_t* __restrict__ 
 __global__ __launch_bounds__(256) void k_csm_vox_append(const int64_t* __restrict__ vox, u64 n_rows, u32* __restrict__ dst, u64 max_rows,
                                                         const u64* cursors) {
     const u64 base = cursors[2];
-    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < 3 * n_rows; i += (u64)gridDim.x * 256) {
+    for (u64 i = grid_tid(); i < 3 * n_rows; i += grid_stride()) {
         const u64 row = base + i / 3;
         if (row < max_rows) dst[3 * base + i] = (u32)vox[i];
     }
@@ -71,7 +71,7 @@ __global__ void k_csm_vox_advance(u64* cursors, u64 n_rows) { cursors[2] += n_ro
 __global__ __launch_bounds__(256) void k_csm_keep(const u64* skey, const u32* perm, const u32* head, const u32* seg, const u64* sizes, u64 n,
                                                   u64 min_vx, const u64* join_ids, const u64* join_sizes, u64 n_join, int join,
                                                   u32* keepseg, u64* joined) {
-    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256) {
+    for (u64 i = grid_tid(); i < n; i += grid_stride()) {
         if (!head[i]) continue;
         const u64 k = skey[i];
         u64 sum = 0;
@@ -90,7 +90,7 @@ __global__ __launch_bounds__(256) void k_csm_keep(const u64* skey, const u32* pe
 // per sorted record: kept head, kept record, kept voxel rows (the inputs of the three scans)
 __global__ __launch_bounds__(256) void k_csm_flags(const u32* perm, const u32* head, const u32* seg, const u32* keepseg, const u64* sizes,
                                                    int with_vox, u64 n, u32* f_head, u32* f_rec, u32* f_vox) {
-    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256) {
+    for (u64 i = grid_tid(); i < n; i += grid_stride()) {
         const u32 keep = keepseg[seg[i] - 1u];
         f_head[i] = keep & head[i]; f_rec[i] = keep;
         f_vox[i] = (keep && with_vox) ? (u32)sizes[perm[i]] : 0u;
@@ -108,7 +108,7 @@ __global__ __launch_bounds__(256) void k_csm_reduce(const u64* skey, const u32* 
                                                     const u32* s_head, const u32* s_rec, const u32* s_vox, const u64* joined,
                                                     const u64* sizes, const int* rc, const int* bb, const u64* asym, const u64* sym, u64 n,
                                                     CsmOut o) {
-    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256) {
+    for (u64 i = grid_tid(); i < n; i += grid_stride()) {
         if (i == n - 1) { o.counts[0] = s_head[i]; o.counts[1] = s_rec[i]; o.counts[2] = s_vox[i]; o.counts[3] = seg[i]; }
         const u32 s = seg[i] - 1u;
         if (!keepseg[s]) continue;
@@ -142,7 +142,7 @@ __global__ __launch_bounds__(256) void k_csm_reduce(const u64* skey, const u32* 
 __global__ __launch_bounds__(256) void k_csm_copy_runs(const u32* perm, const u32* s_vox, const u64* sizes, const u64* vpos, u64 n,
                                                        const u32* __restrict__ vox_src, u64 n_vox_src, u32* __restrict__ vox_out) {
     const u64 total = min((u64)s_vox[n - 1], n_vox_src);    // kept rows never exceed the rows there are: vox_out holds n_vox_src
-    for (u64 r = (u64)blockIdx.x * 256 + threadIdx.x; r < total; r += (u64)gridDim.x * 256) {
+    for (u64 r = grid_tid(); r < total; r += grid_stride()) {
         u64 lo = 0, hi = n - 1;                             // s_vox[n - 1] > r
         while (lo < hi) {
             const u64 mid = lo + (hi - lo) / 2;
@@ -171,28 +171,25 @@ struct CsmIn {
 
 int csm_merge(const char* what, const CsmIn& in, size_t n, u64 min_vx, const CsmOut& o, u32* vox_out, void* temp, size_t temp_bytes,
               hipStream_t s) {
-    if (!o.counts) return sd_fail_msg(SD_ERR_INVALID, "sd_cs_merge: null counts");
-    if (hipMemsetAsync(o.counts, 0, 4 * sizeof(u64), s) != hipSuccess) return sd_fail_msg(SD_ERR_HIP, "memset failed");
-    if (n == 0) return SD_OK;
-    if (n >= (1ull << 32) || in.n_vox >= (1ull << 32)) return sd_fail_msg(SD_ERR_INVALID, "sd_cs_merge: < 2^32 records and voxel rows per call");
-    CsmScratch w;
-    if (!temp || temp_bytes < layout(w, temp, n)) return sd_fail_msg(SD_ERR_INVALID, "sd_cs_merge: scratch smaller than sd_cs_merge_temp_bytes(n)");
     const char* who = "sd_cs_merge";
-    const int g = grid_for(n, 4096);
+    if (!o.counts) return fail(who, ": null counts");
+    if (int rc = zero_counts(o.counts, 4, s); rc != SD_OK) return rc;
+    if (n == 0) return SD_OK;
+    if (n >= (1ull << 32) || in.n_vox >= (1ull << 32)) return fail(who, ": < 2^32 records and voxel rows per call");
+    CsmScratch w;
+    if (int rc = check_scratch(who, temp, temp_bytes, layout(w, temp, n), "sd_cs_merge_temp_bytes(n)"); rc != SD_OK) return rc;
     if (int rc = sort_by_key(who, w.prim, in.ids, w.skey, w.i0, w.perm, n, 64, s); rc != SD_OK) return rc;
     if (int rc = number_segments(who, w.prim, w.skey, nullptr, w.head, w.seg, n, s); rc != SD_OK) return rc;
-    hipLaunchKernelGGL(k_csm_keep, dim3(g), dim3(256), 0, s, w.skey, w.perm, w.head, w.seg, in.sizes, (u64)n, min_vx, in.join_ids,
-                       in.join_sizes, in.n_join, in.join, w.keepseg, w.joined);
-    hipLaunchKernelGGL(k_csm_flags, dim3(g), dim3(256), 0, s, w.perm, w.head, w.seg, w.keepseg, in.sizes, in.vpos ? 1 : 0, (u64)n, w.f_head,
-                       w.f_rec, w.f_vox);
+    launch_1d(k_csm_keep, n, 4096, s, w.skey, w.perm, w.head, w.seg, in.sizes, (u64)n, min_vx, in.join_ids, in.join_sizes, in.n_join, in.join,
+              w.keepseg, w.joined);
+    launch_1d(k_csm_flags, n, 4096, s, w.perm, w.head, w.seg, w.keepseg, in.sizes, in.vpos ? 1 : 0, (u64)n, w.f_head, w.f_rec, w.f_vox);
     if (int rc = scan_u32(who, w.prim, w.f_head, w.s_head, n, s); rc != SD_OK) return rc;
     if (int rc = scan_u32(who, w.prim, w.f_rec, w.s_rec, n, s); rc != SD_OK) return rc;
     if (int rc = scan_u32(who, w.prim, w.f_vox, w.s_vox, n, s); rc != SD_OK) return rc;
-    hipLaunchKernelGGL(k_csm_reduce, dim3(g), dim3(256), 0, s, w.skey, w.perm, w.head, w.seg, w.keepseg, w.s_head, w.s_rec, w.s_vox, w.joined,
-                       in.sizes, in.rc, in.bb, in.asym, in.sym, (u64)n, o);
+    launch_1d(k_csm_reduce, n, 4096, s, w.skey, w.perm, w.head, w.seg, w.keepseg, w.s_head, w.s_rec, w.s_vox, w.joined, in.sizes, in.rc, in.bb,
+              in.asym, in.sym, (u64)n, o);
     if (in.vpos && in.n_vox)
-        hipLaunchKernelGGL(k_csm_copy_runs, dim3(grid_for(in.n_vox, 4096)), dim3(256), 0, s, w.perm, w.s_vox, in.sizes, in.vpos, (u64)n, in.vox,
-                           in.n_vox, vox_out);
+        launch_1d(k_csm_copy_runs, in.n_vox, 4096, s, w.perm, w.s_vox, in.sizes, in.vpos, (u64)n, in.vox, in.n_vox, vox_out);
     return launch_status(what);
 }
 
@@ -214,13 +211,12 @@ int sd_cs_merge_append(const int64_t* rec_dev, size_t n, const int64_t* vox_dev,
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     u64* cur = reinterpret_cast<u64*>(cursors_dev);
     if (n)
-        hipLaunchKernelGGL(k_csm_append, dim3(grid_for(n, 4096)), dim3(256), 0, s, rec_dev, (u64)n, ox, oy, oz, reinterpret_cast<u64*>(cs_ids_dev),
-                           cs_rc_dev, cs_bbox_dev, reinterpret_cast<u64*>(cs_sizes_dev), (u64)max_cs, reinterpret_cast<u64*>(syn_ids_dev),
-                           syn_rc_dev, syn_bbox_dev, reinterpret_cast<u64*>(syn_sizes_dev), reinterpret_cast<u64*>(syn_asym_dev),
-                           reinterpret_cast<u64*>(syn_sym_dev), reinterpret_cast<u64*>(syn_vpos_dev), (u64)max_syn, cur);
+        launch_1d(k_csm_append, n, 4096, s, rec_dev, (u64)n, ox, oy, oz, reinterpret_cast<u64*>(cs_ids_dev), cs_rc_dev, cs_bbox_dev,
+                  reinterpret_cast<u64*>(cs_sizes_dev), (u64)max_cs, reinterpret_cast<u64*>(syn_ids_dev), syn_rc_dev, syn_bbox_dev,
+                  reinterpret_cast<u64*>(syn_sizes_dev), reinterpret_cast<u64*>(syn_asym_dev), reinterpret_cast<u64*>(syn_sym_dev),
+                  reinterpret_cast<u64*>(syn_vpos_dev), (u64)max_syn, cur);
     if (n_vox) {
-        hipLaunchKernelGGL(k_csm_vox_append, dim3(grid_for(3 * (u64)n_vox, 4096)), dim3(256), 0, s, vox_dev, (u64)n_vox, vox_all_dev, (u64)max_vox,
-                           cur);
+        launch_1d(k_csm_vox_append, 3 * (u64)n_vox, 4096, s, vox_dev, (u64)n_vox, vox_all_dev, (u64)max_vox, cur);
         hipLaunchKernelGGL(k_csm_vox_advance, dim3(1), dim3(1), 0, s, cur, (u64)n_vox);
     }
     return launch_status("sd_cs_merge_append: launch failed");

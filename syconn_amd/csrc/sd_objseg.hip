@@ -15,11 +15,11 @@
 // (x,y) row of the volume padded by P = largest `iterations` per side.  A morphology step is then a handful of word loads,
 // funnel shifts and AND / OR per 32 voxels (an HBM/L2 stream of 1/8 byte per voxel) instead of 15 byte loads per voxel.
 // Connected components: labels start as the linear index of the voxel's z-RUN start (read off the bit mask, no atomics), so
-// only run heads and run/run adjacencies along y and x touch the union-find (atomicMin links, larger root under smaller: a
+// only run heads and run/run adjacencies along y and x touch the union-find (uf_union of sd_tables.h: a
 // component's root is its first voxel in raster order); roots are ranked by an exclusive scan -> ids 1..N in
 // scipy.ndimage.label's order, bit-exact.
 #include "../../include/syconn_dense.h"
-#include "sd_host_util.h"
+#include "sd_tables.h"
 #include <stdint.h>
 #include <algorithm>
 #include <cmath>
@@ -153,22 +153,7 @@ __global__ __launch_bounds__(256) void k_morph_bits(const uint32_t* src, uint32_
 }
 
 // ---- connected components ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ int cc_find(const int* L, int a) {
-    int p = __hip_atomic_load(&L[a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    while (p != a) { a = p; p = __hip_atomic_load(&L[a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-    return a;
-}
-__device__ __forceinline__ void cc_union(int* L, int a, int b) {
-    while (true) {
-        a = cc_find(L, a);
-        b = cc_find(L, b);
-        if (a == b) return;
-        if (a < b) { const int t = a; a = b; b = t; }        // link the larger root under the smaller one
-        const int old = atomicMin(&L[a], b);
-        if (old == a) return;
-        a = old;                                             // somebody else re-linked a meanwhile: retry from there
-    }
-}
+// union-find: uf_find / uf_union of sd_tables.h on int labels
 
 // foreground bit of volume voxel (x,y,z) (unpadded coordinates inside the volume)
 __device__ __forceinline__ bool fg(const uint32_t* A, const Dom& d, int x, int y, int z) {
@@ -258,7 +243,7 @@ __global__ __launch_bounds__(256) void k_cc_merge_runs(const uint32_t* A, Dom d,
                 const int bit = __builtin_ctz(starts);
                 starts &= starts - 1;
                 const int ha = max(run_start_pz(row, zw, bit), d.P), hb = max(run_start_pz(nrow, zw, bit), d.P);
-                cc_union(L, rbase + ha, rbase - noff + hb);
+                uf_union(L, rbase + ha, rbase - noff + hb);
             }
         }
     }
@@ -283,7 +268,7 @@ __global__ __launch_bounds__(256) void k_cc_compress_count(const uint32_t* A, Do
         while (h) {
             const int i = ibase + __builtin_ctz(h);
             h &= h - 1;
-            const int r = cc_find(L, i);
+            const int r = uf_find(L, i);
             L[i] = r;
             c += r == i ? 1 : 0;
         }

@@ -1,5 +1,5 @@
-// What the point queries over sorted tables share (sd_synssv_map.hip, sd_syn_props.hip; the searches also serve sd_cs_merge.hip and
-// sd_syn_ssv.hip): binary searches over ascending arrays, the float64 distances, and the segmented tile index.
+// What the point queries over sorted tables share (sd_synssv_map.hip, sd_syn_props.hip): the float64 distances and the segmented tile
+// index.  The searches they walk the tables with are those of sd_tables.h.
 //   index     segment s owns points[begin[s] : begin[s + 1]].  A key per point holds the segment number in the high bits and a spatial
 //             code below it; sort_by_key (sd_sortseg.h) orders the points and the caller places them in sorted order as float64.
 //             Every TILE sorted points of a segment are a tile with one box (min | max); tile t of segment s is slot
@@ -13,46 +13,6 @@
 #include <cmath>
 
 namespace {
-
-const size_t LIM31 = (size_t)1 << 31;                        // counts per call stay below it (32-bit permutations, int grids)
-
-// bits that hold every value of [0, n), n < 2^31: the segment field of a key
-inline int bits_for(u64 n) {
-    int b = 0;
-    while (b < 31 && ((n - 1) >> b)) ++b;
-    return b;
-}
-
-// ---- searches over an ascending a[0 .. n) -----------------------------------------------------------------------------------------
-// first index whose element is >= key (n if none)
-template <class T> __device__ __forceinline__ u64 lower_bound(const T* a, u64 n, u64 key) {
-    u64 lo = 0, hi = n;
-    while (lo < hi) {
-        const u64 mid = lo + (hi - lo) / 2;
-        if ((u64)a[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-// first index whose element is > key (n if none)
-template <class T> __device__ __forceinline__ u64 upper_bound(const T* a, u64 n, u64 key) {
-    u64 lo = 0, hi = n;
-    while (lo < hi) {
-        const u64 mid = lo + (hi - lo) / 2;
-        if ((u64)a[mid] <= key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-// first index that holds `key`, or -1
-template <class T> __device__ __forceinline__ long find_exact(const T* a, u64 n, u64 key) {
-    const u64 lo = lower_bound(a, n, key);
-    return (lo < n && (u64)a[lo] == key) ? (long)lo : -1;
-}
-// the segment of item j under the offsets begin[0 .. n_segments]; clamped into [0, n_segments) whatever the table holds
-template <class T> __device__ __forceinline__ u64 segment_of(const T* begin, u64 n_segments, u64 j) {
-    u64 s = upper_bound(begin, n_segments + 1, j);
-    s = s ? s - 1 : 0;
-    return s < n_segments ? s : n_segments - 1;
-}
 
 // ---- distances --------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ double sq_dist(const double* p, const double* q) {

@@ -126,9 +126,9 @@ int sd_chunkprops_append(const void* table, size_t cap_obj, int X, int Y, int Z,
                          uint64_t* cursor_dev, void* stream) {
     if (!table || !pow2(cap_obj) || X <= 0 || Y <= 0 || Z <= 0 || !ids_dev || !rc_dev || !bbox_dev || !sizes_dev || !cursor_dev)
         return sd_fail_msg(SD_ERR_INVALID, "sd_chunkprops_append: bad argument");
-    hipLaunchKernelGGL(k_chunkprops_append, dim3(grid_for(cap_obj, 4096)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                       tab_view(table, cap_obj), X, Y, Z, ox, oy, oz, (u64)min_obj_vx, reinterpret_cast<u64*>(ids_dev), rc_dev, bbox_dev,
-                       reinterpret_cast<u64*>(sizes_dev), (u64)max_records, reinterpret_cast<u64*>(cursor_dev));
+    launch_1d(k_chunkprops_append, cap_obj, 4096, reinterpret_cast<hipStream_t>(stream), tab_view(table, cap_obj), X, Y, Z, ox, oy, oz,
+              (u64)min_obj_vx, reinterpret_cast<u64*>(ids_dev), rc_dev, bbox_dev, reinterpret_cast<u64*>(sizes_dev), (u64)max_records,
+              reinterpret_cast<u64*>(cursor_dev));
     return launch_status("sd_chunkprops_append: launch failed");
 }
 
@@ -139,10 +139,9 @@ int sd_chunkpairs_append(const void* pair_table, size_t cap_pair, const void* su
         !cell_ids_dev || !counts_dev || !cursor_dev)
         return sd_fail_msg(SD_ERR_INVALID, "sd_chunkpairs_append: bad argument");
     const u64* pk = reinterpret_cast<const u64*>(pair_table);
-    hipLaunchKernelGGL(k_chunkpairs_append, dim3(grid_for(cap_pair, 4096)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), pk,
-                       pk + cap_pair, (u64)cap_pair, tab_view(sub_table, cap_obj), reinterpret_cast<const u64*>(cell_table), X, Y, Z,
-                       (u64)min_obj_vx, reinterpret_cast<u64*>(sub_ids_dev), reinterpret_cast<u64*>(cell_ids_dev),
-                       reinterpret_cast<u64*>(counts_dev), (u64)max_records, reinterpret_cast<u64*>(cursor_dev));
+    launch_1d(k_chunkpairs_append, cap_pair, 4096, reinterpret_cast<hipStream_t>(stream), pk, pk + cap_pair, (u64)cap_pair,
+              tab_view(sub_table, cap_obj), reinterpret_cast<const u64*>(cell_table), X, Y, Z, (u64)min_obj_vx, reinterpret_cast<u64*>(sub_ids_dev),
+              reinterpret_cast<u64*>(cell_ids_dev), reinterpret_cast<u64*>(counts_dev), (u64)max_records, reinterpret_cast<u64*>(cursor_dev));
     return launch_status("sd_chunkpairs_append: launch failed");
 }
 
@@ -153,7 +152,7 @@ int sd_propmerge_objects(const uint64_t* ids_dev, const uint64_t* sizes_dev, con
                          int32_t* bbox_sorted_dev, uint64_t* n_unique_dev, void* temp_dev, size_t temp_bytes, void* stream) {
     if (!n_unique_dev) return sd_fail_msg(SD_ERR_INVALID, "sd_propmerge_objects: null count");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (hipMemsetAsync(n_unique_dev, 0, sizeof(uint64_t), s) != hipSuccess) return sd_fail_msg(SD_ERR_HIP, "memset failed");
+    if (int rc = zero_counts(n_unique_dev, 1, s); rc != SD_OK) return rc;
     if (n == 0) return SD_OK;
     if (n >= (1ull << 32)) return sd_fail_msg(SD_ERR_INVALID, "sd_propmerge_objects: < 2^32 records per call");
     Scratch w;
@@ -161,12 +160,11 @@ int sd_propmerge_objects(const uint64_t* ids_dev, const uint64_t* sizes_dev, con
         !bbox_sorted_dev || !temp_dev || temp_bytes < layout(w, temp_dev, n))
         return sd_fail_msg(SD_ERR_INVALID, "sd_propmerge_objects: bad argument / scratch smaller than sd_propmerge_temp_bytes(n)");
     const char* who = "sd_propmerge_objects";
-    const int g = grid_for(n, 4096);
     if (int rc = sort_by_key(who, w.prim, reinterpret_cast<const u64*>(ids_dev), w.k0, w.i0, w.i1, n, 64, s); rc != SD_OK) return rc;
     if (int rc = number_segments(who, w.prim, w.k0, nullptr, w.head, w.seg, n, s); rc != SD_OK) return rc;
-    hipLaunchKernelGGL(k_reduce_objects, dim3(g), dim3(256), 0, s, w.k0, w.i1, w.head, w.seg, reinterpret_cast<const u64*>(sizes_dev),
-                       rc_dev, bbox_dev, (u64)n, reinterpret_cast<u64*>(uniq_ids_dev), reinterpret_cast<u64*>(tot_sizes_dev), last_rc_dev,
-                       seg_begin_dev, bbox_sorted_dev, reinterpret_cast<u64*>(n_unique_dev));
+    launch_1d(k_reduce_objects, n, 4096, s, w.k0, w.i1, w.head, w.seg, reinterpret_cast<const u64*>(sizes_dev), rc_dev, bbox_dev, (u64)n,
+              reinterpret_cast<u64*>(uniq_ids_dev), reinterpret_cast<u64*>(tot_sizes_dev), last_rc_dev, seg_begin_dev, bbox_sorted_dev,
+              reinterpret_cast<u64*>(n_unique_dev));
     return launch_status("sd_propmerge_objects: launch failed");
 }
 
@@ -175,7 +173,7 @@ int sd_propmerge_pairs(const uint64_t* sub_ids_dev, const uint64_t* cell_ids_dev
                        size_t temp_bytes, void* stream) {
     if (!n_unique_dev) return sd_fail_msg(SD_ERR_INVALID, "sd_propmerge_pairs: null count");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (hipMemsetAsync(n_unique_dev, 0, sizeof(uint64_t), s) != hipSuccess) return sd_fail_msg(SD_ERR_HIP, "memset failed");
+    if (int rc = zero_counts(n_unique_dev, 1, s); rc != SD_OK) return rc;
     if (n == 0) return SD_OK;
     if (n >= (1ull << 32)) return sd_fail_msg(SD_ERR_INVALID, "sd_propmerge_pairs: < 2^32 records per call");
     Scratch w;
@@ -183,18 +181,17 @@ int sd_propmerge_pairs(const uint64_t* sub_ids_dev, const uint64_t* cell_ids_dev
         temp_bytes < layout(w, temp_dev, n))
         return sd_fail_msg(SD_ERR_INVALID, "sd_propmerge_pairs: bad argument / scratch smaller than sd_propmerge_temp_bytes(n)");
     const char* who = "sd_propmerge_pairs";
-    const int g = grid_for(n, 4096);
     const u64* sub = reinterpret_cast<const u64*>(sub_ids_dev);
     const u64* cell = reinterpret_cast<const u64*>(cell_ids_dev);
     // lexicographic (subcell id, cell id): stable sort by the minor key first, then by the major key
     if (int rc = sort_by_key(who, w.prim, cell, w.k0, w.i0, w.i1, n, 64, s); rc != SD_OK) return rc;
-    hipLaunchKernelGGL(k_gather64, dim3(g), dim3(256), 0, s, sub, w.i1, w.k1, (u64)n);
+    launch_1d(k_gather64, n, 4096, s, sub, w.i1, w.k1, (u64)n);
     if (int rc = sort_carry(who, w.prim, w.k1, w.k2, w.i1, w.i0, n, 64, s); rc != SD_OK) return rc;
-    hipLaunchKernelGGL(k_gather64, dim3(g), dim3(256), 0, s, cell, w.i0, w.k0, (u64)n);       // k2 = sorted subcell ids, k0 = their cell ids
+    launch_1d(k_gather64, n, 4096, s, cell, w.i0, w.k0, (u64)n);                               // k2 = sorted subcell ids, k0 = their cell ids
     if (int rc = number_segments(who, w.prim, w.k2, w.k0, w.head, w.seg, n, s); rc != SD_OK) return rc;
-    hipLaunchKernelGGL(k_reduce_pairs, dim3(g), dim3(256), 0, s, w.k2, w.k0, w.i0, w.head, w.seg, reinterpret_cast<const u64*>(counts_dev),
-                       (u64)n, reinterpret_cast<u64*>(out_sub_dev), reinterpret_cast<u64*>(out_cell_dev),
-                       reinterpret_cast<u64*>(out_counts_dev), reinterpret_cast<u64*>(n_unique_dev));
+    launch_1d(k_reduce_pairs, n, 4096, s, w.k2, w.k0, w.i0, w.head, w.seg, reinterpret_cast<const u64*>(counts_dev), (u64)n,
+              reinterpret_cast<u64*>(out_sub_dev), reinterpret_cast<u64*>(out_cell_dev), reinterpret_cast<u64*>(out_counts_dev),
+              reinterpret_cast<u64*>(n_unique_dev));
     return launch_status("sd_propmerge_pairs: launch failed");
 }
 

@@ -19,14 +19,13 @@
 //            A window of more than SD_SKEL_LDS_NODES nodes does not fit: the source is flagged, counted in counts[0], and redone by
 //            the second kernel over per-wave arrays in the scratch that are indexed by the node's index inside its cell (no hashing),
 //            sized by the largest cell.  Nothing is truncated.
-//   comps    union-find over the edges whose two nodes are not soma (atomicMin links, larger root under smaller, the rule of
-//            sd_objseg.hip), key (root, class) per node, sort_by_key, the length of every (root, class) run by a search for its end,
-//            the best (count, smallest class) of every root by a 64-bit atomic maximum, then per node the rule 50 c1 < 33 total.
+//   comps    union-find over the edges whose two nodes are not soma (uf_union of sd_tables.h), key (root, class) per node, sort_by_key,
+//            the length of every (root, class) run by a search for its end, the best (count, smallest class) of every root by a 64-bit atomic maximum, then per node the rule 50 c1 < 33 total.
 //
 // Every index read from device memory is clamped or checked before it is used.  No scalar memory writes, no inline assembly.
 #include "../../include/syconn_dense.h"
 #include "sd_sortseg.h"
-#include "sd_pointtiles.h"
+#include "sd_tables.h"
 
 namespace {
 
@@ -40,15 +39,7 @@ static_assert(SLOTS == (1u << LOG_SLOTS) && SLOTS <= 65536, "slots are a power o
 static_assert(SD_SKEL_MAX_CLASSES == 64, "one class count per lane");
 static_assert(4 * (SLOTS * (8 + 4 + 2) + LISTN * 2) <= 65536, "four waves' tables in one block's LDS");
 
-__device__ __forceinline__ u64 clamp_u64(u64 v, u64 hi) { return v < hi ? v : hi; }
-
 // ---- csr --------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_skel_offsets(const u64* __restrict__ begin, u64 n_cells, u64 n_items, u64* counts) {
-    for (u64 c = (u64)blockIdx.x * 256 + threadIdx.x; c < n_cells; c += (u64)gridDim.x * 256) {
-        const u64 b0 = begin[c], b1 = begin[c + 1];
-        if (b1 < b0 || b1 > n_items || (c == 0 && b0 != 0) || (c == n_cells - 1 && b1 != n_items)) counts[7] = 1;
-    }
-}
 // the two table rows of edge e, or false where one of them is outside the cell
 __device__ __forceinline__ bool edge_rows(const long long* __restrict__ edges, const u64* __restrict__ edge_begin, const u64* __restrict__ node_begin,
                                           u64 n_cells, u64 n_nodes, u64 e, u64& ga, u64& gb) {
@@ -62,7 +53,7 @@ __device__ __forceinline__ bool edge_rows(const long long* __restrict__ edges, c
 }
 __global__ __launch_bounds__(256) void k_csr_keys(const long long* __restrict__ edges, const u64* __restrict__ edge_begin, const u64* __restrict__ node_begin,
                                                   u64 n_cells, u64 n_nodes, u64 n_edges, u64* key, u64* counts) {
-    for (u64 j = (u64)blockIdx.x * 256 + threadIdx.x; j < 2 * n_edges; j += (u64)gridDim.x * 256) {
+    for (u64 j = grid_tid(); j < 2 * n_edges; j += grid_stride()) {
         u64 ga = 0, gb = 0;
         const bool ok = edge_rows(edges, edge_begin, node_begin, n_cells, n_nodes, j >> 1, ga, gb);
         if (!ok) counts[7] = 1;
@@ -71,7 +62,7 @@ __global__ __launch_bounds__(256) void k_csr_keys(const long long* __restrict__ 
 }
 __global__ __launch_bounds__(256) void k_csr_place(const long long* __restrict__ edges, const double* __restrict__ weight, const u64* __restrict__ skey,
                                                    const u32* __restrict__ perm, u64 n_nodes, u64 n_edges, u32* adj_nbr, double* adj_w, u64* counts) {
-    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < 2 * n_edges; i += (u64)gridDim.x * 256) {
+    for (u64 i = grid_tid(); i < 2 * n_edges; i += grid_stride()) {
         const u64 j = clamp_u64(perm[i], 2 * n_edges - 1), e = j >> 1;
         double w = weight[e];
         if (!(w >= 0.0)) { w = INFINITY; counts[7] = 1; }                        // negative or NaN: never relaxed below a finite max_dist
@@ -80,7 +71,7 @@ __global__ __launch_bounds__(256) void k_csr_place(const long long* __restrict__
     }
 }
 __global__ __launch_bounds__(256) void k_csr_rows(const u64* __restrict__ skey, u64 n_nodes, u64 n_adj, u64* adj_begin) {
-    for (u64 g = (u64)blockIdx.x * 256 + threadIdx.x; g <= n_nodes; g += (u64)gridDim.x * 256) adj_begin[g] = n_adj ? lower_bound(skey, n_adj, g) : 0;
+    for (u64 g = grid_tid(); g <= n_nodes; g += grid_stride()) adj_begin[g] = n_adj ? lower_bound(skey, n_adj, g) : 0;
 }
 
 // ---- vote -------------------------------------------------------------------------------------------------------------------------
@@ -195,7 +186,7 @@ __global__ __launch_bounds__(256) void k_skel_vote_lds(const u64* __restrict__ a
     __shared__ unsigned short s_queue[4][SLOTS];
     __shared__ unsigned short s_list[4][LISTN];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const u64 wave = ((u64)blockIdx.x * 256 + threadIdx.x) >> 6, n_waves = ((u64)gridDim.x * 256) >> 6;
+    const u64 wave = grid_tid() >> 6, n_waves = grid_stride() >> 6;
     const WaveTab<false, unsigned short> t{s_dist[w], s_key[w], s_queue[w], s_list[w], SLOTS};
     t.clear(SLOTS, lane);
     u64 n_steps = 0, n_redo = 0;
@@ -224,7 +215,7 @@ __global__ __launch_bounds__(256) void k_skel_vote_glb(const u64* __restrict__ a
                                                        int n_classes, double max_dist, uint8_t* vote, u32* n_reached, const uint8_t* __restrict__ redo,
                                                        u64* g_dist, u32* g_key, u32* g_queue, u32* g_list, u64 m, u64* counts) {
     const int lane = threadIdx.x & 63;
-    const u64 wave = ((u64)blockIdx.x * 256 + threadIdx.x) >> 6, n_waves = ((u64)gridDim.x * 256) >> 6;
+    const u64 wave = grid_tid() >> 6, n_waves = grid_stride() >> 6;
     const WaveTab<true, u32> t{g_dist + wave * m, g_key + wave * m, g_queue + wave * m, g_list + wave * m, (u32)m};
     bool ready = false;
     u64 n_steps = 0;
@@ -243,42 +234,26 @@ __global__ __launch_bounds__(256) void k_skel_vote_glb(const u64* __restrict__ a
 }
 
 // ---- components -------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ u32 cc_find(const u32* L, u32 a) {
-    u32 p = __hip_atomic_load(&L[a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    while (p != a) { a = p; p = __hip_atomic_load(&L[a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-    return a;
-}
-__device__ __forceinline__ void cc_union(u32* L, u32 a, u32 b) {
-    while (true) {
-        a = cc_find(L, a);
-        b = cc_find(L, b);
-        if (a == b) return;
-        if (a < b) { const u32 x = a; a = b; b = x; }                            // link the larger root under the smaller one
-        const u32 old = atomicMin(&L[a], b);
-        if (old == a) return;
-        a = old;                                                                 // somebody else re-linked a meanwhile: retry from there
-    }
-}
 __global__ __launch_bounds__(256) void k_cc_union(const long long* __restrict__ edges, const u64* __restrict__ edge_begin, const u64* __restrict__ node_begin,
                                                   u64 n_cells, u64 n_nodes, u64 n_edges, const uint8_t* __restrict__ classes, int soma, u32* parent, u64* counts) {
-    for (u64 e = (u64)blockIdx.x * 256 + threadIdx.x; e < n_edges; e += (u64)gridDim.x * 256) {
+    for (u64 e = grid_tid(); e < n_edges; e += grid_stride()) {
         u64 ga = 0, gb = 0;
         if (!edge_rows(edges, edge_begin, node_begin, n_cells, n_nodes, e, ga, gb)) { counts[7] = 1; continue; }
         if ((int)classes[ga] == soma || (int)classes[gb] == soma) continue;
-        cc_union(parent, (u32)ga, (u32)gb);
+        uf_union(parent, (u32)ga, (u32)gb);
     }
 }
 __global__ __launch_bounds__(256) void k_cc_keys(const u32* __restrict__ parent, const uint8_t* __restrict__ classes, int soma, u64 n_nodes, u32* root, u64* key) {
-    for (u64 g = (u64)blockIdx.x * 256 + threadIdx.x; g < n_nodes; g += (u64)gridDim.x * 256) {
+    for (u64 g = grid_tid(); g < n_nodes; g += grid_stride()) {
         const int cls = classes[g];
-        const u32 r = cls == soma ? (u32)n_nodes : cc_find(parent, (u32)g);
+        const u32 r = cls == soma ? (u32)n_nodes : uf_find(parent, (u32)g);
         root[g] = r;
         key[g] = (u64)r << 6 | (u64)(cls & 63);
     }
 }
 // at the first record of every (root, class) run: its length against the root's best (count, smallest class)
 __global__ __launch_bounds__(256) void k_cc_best(const u64* __restrict__ skey, const u32* __restrict__ head, u64 n_nodes, u64* best) {
-    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n_nodes; i += (u64)gridDim.x * 256) {
+    for (u64 i = grid_tid(); i < n_nodes; i += grid_stride()) {
         const u64 k = skey[i], r = k >> 6;
         if (!head[i] || r >= n_nodes) continue;
         const u64 cnt = upper_bound(skey, n_nodes, k) - i;
@@ -287,7 +262,7 @@ __global__ __launch_bounds__(256) void k_cc_best(const u64* __restrict__ skey, c
 }
 __global__ __launch_bounds__(256) void k_cc_write(const u64* __restrict__ skey, const u32* __restrict__ root, const u64* __restrict__ best,
                                                   const uint8_t* __restrict__ classes, int one, int zero, u64 n_nodes, uint8_t* out, u64* counts) {
-    for (u64 g = (u64)blockIdx.x * 256 + threadIdx.x; g < n_nodes; g += (u64)gridDim.x * 256) {
+    for (u64 g = grid_tid(); g < n_nodes; g += grid_stride()) {
         const u64 r = root[g];
         if (r >= n_nodes) { out[g] = classes[g]; continue; }                    // soma keeps its label
         const u64 b = best[r];
@@ -332,7 +307,7 @@ size_t layout(CompScratch& w, void* base, size_t n_nodes) {
 
 int check_tables(const char* who, size_t n_cells, size_t n_nodes, size_t n_edges) {
     if (n_cells >= LIM31 || n_nodes >= LIM31 - 1 || n_edges >= LIM31 / 2)
-        return sd_fail_msg(SD_ERR_INVALID, (std::string(who) + ": cells, nodes and half edges < 2^31 per call").c_str());
+        return fail(who, ": cells, nodes and half edges < 2^31 per call");
     return SD_OK;
 }
 
@@ -350,34 +325,33 @@ int sd_skel_csr(const int64_t* edges_dev, const uint64_t* edge_begin_dev, const 
                 void* temp_dev, size_t temp_bytes, void* stream) {
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const char* who = "sd_skel_csr";
-    if (!counts_dev) return sd_fail_msg(SD_ERR_INVALID, "sd_skel_csr: null counts");
+    if (!counts_dev) return fail(who, ": null counts");
     if (int rc = check_tables(who, n_cells, n_nodes, n_edges); rc != SD_OK) return rc;
     u64* counts = reinterpret_cast<u64*>(counts_dev);
-    if (hipMemsetAsync(counts, 0, 8 * sizeof(u64), s) != hipSuccess) return sd_fail_msg(SD_ERR_HIP, "memset failed");
+    if (int rc = zero_counts(counts, 8, s); rc != SD_OK) return rc;
     if (n_cells == 0) {
-        if (n_nodes || n_edges) return sd_fail_msg(SD_ERR_INVALID, "sd_skel_csr: nodes or edges without cells");
+        if (n_nodes || n_edges) return fail(who, ": nodes or edges without cells");
         return SD_OK;
     }
     if (!edge_begin_dev || !node_begin_dev || !adj_begin_dev || (n_edges && (!edges_dev || !weight_dev || !adj_nbr_dev || !adj_w_dev)))
-        return sd_fail_msg(SD_ERR_INVALID, "sd_skel_csr: bad argument");
-    if (n_edges && (!temp_dev || temp_bytes < sd_skel_csr_temp_bytes(n_edges)))
-        return sd_fail_msg(SD_ERR_INVALID, "sd_skel_csr: scratch smaller than sd_skel_csr_temp_bytes(n_edges)");
+        return fail(who, ": bad argument");
+    if (n_edges)
+        if (int rc = check_scratch(who, temp_dev, temp_bytes, sd_skel_csr_temp_bytes(n_edges), "sd_skel_csr_temp_bytes(n_edges)"); rc != SD_OK) return rc;
     const u64 Cn = n_cells, N = n_nodes, E = n_edges;
     const u64* eb = reinterpret_cast<const u64*>(edge_begin_dev);
     const u64* nb = reinterpret_cast<const u64*>(node_begin_dev);
     const long long* edges = reinterpret_cast<const long long*>(edges_dev);
     u64* adj_begin = reinterpret_cast<u64*>(adj_begin_dev);
-    hipLaunchKernelGGL(k_skel_offsets, dim3(grid_for(Cn, SD_SKEL_NODE_GRID)), dim3(256), 0, s, nb, Cn, N, counts);
-    hipLaunchKernelGGL(k_skel_offsets, dim3(grid_for(Cn, SD_SKEL_NODE_GRID)), dim3(256), 0, s, eb, Cn, E, counts);
+    launch_1d(k_check_offsets, Cn, SD_SKEL_NODE_GRID, s, nb, Cn, N, counts);
+    launch_1d(k_check_offsets, Cn, SD_SKEL_NODE_GRID, s, eb, Cn, E, counts);
     CsrScratch w;
     layout(w, temp_dev, E ? 2 * E : 1);
     if (E) {
-        const int ge = grid_for(2 * E, SD_SKEL_EDGE_GRID);
-        hipLaunchKernelGGL(k_csr_keys, dim3(ge), dim3(256), 0, s, edges, eb, nb, Cn, N, E, w.key, counts);
+        launch_1d(k_csr_keys, 2 * E, SD_SKEL_EDGE_GRID, s, edges, eb, nb, Cn, N, E, w.key, counts);
         if (int rc = sort_by_key(who, w.prim, w.key, w.skey, w.i0, w.perm, 2 * n_edges, bits_for(N + 1), s); rc != SD_OK) return rc;
-        hipLaunchKernelGGL(k_csr_place, dim3(ge), dim3(256), 0, s, edges, weight_dev, w.skey, w.perm, N, E, adj_nbr_dev, adj_w_dev, counts);
+        launch_1d(k_csr_place, 2 * E, SD_SKEL_EDGE_GRID, s, edges, weight_dev, w.skey, w.perm, N, E, adj_nbr_dev, adj_w_dev, counts);
     }
-    hipLaunchKernelGGL(k_csr_rows, dim3(grid_for(N + 1, SD_SKEL_NODE_GRID)), dim3(256), 0, s, w.skey, N, 2 * E, adj_begin);
+    launch_1d(k_csr_rows, N + 1, SD_SKEL_NODE_GRID, s, w.skey, N, 2 * E, adj_begin);
     return launch_status("sd_skel_csr: launch failed");
 }
 
@@ -390,27 +364,28 @@ int sd_skel_vote(const uint64_t* adj_begin_dev, const uint32_t* adj_nbr_dev, con
                  size_t n_cells, size_t n_nodes, size_t max_cell_nodes, const uint8_t* classes_dev, int n_classes, double max_dist,
                  uint8_t* vote_dev, uint32_t* n_reached_dev, uint64_t* counts_dev, void* temp_dev, size_t temp_bytes, void* stream) {
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (!counts_dev) return sd_fail_msg(SD_ERR_INVALID, "sd_skel_vote: null counts");
-    if (int rc = check_tables("sd_skel_vote", n_cells, n_nodes, n_adj / 2); rc != SD_OK) return rc;
-    if (n_classes < 1 || n_classes > SD_SKEL_MAX_CLASSES) return sd_fail_msg(SD_ERR_INVALID, "sd_skel_vote: 1 <= n_classes <= 64");
-    if (!(max_dist >= 0.0)) return sd_fail_msg(SD_ERR_INVALID, "sd_skel_vote: max_dist >= 0");
+    const char* who = "sd_skel_vote";
+    if (!counts_dev) return fail(who, ": null counts");
+    if (int rc = check_tables(who, n_cells, n_nodes, n_adj / 2); rc != SD_OK) return rc;
+    if (n_classes < 1 || n_classes > SD_SKEL_MAX_CLASSES) return fail(who, ": 1 <= n_classes <= 64");
+    if (!(max_dist >= 0.0)) return fail(who, ": max_dist >= 0");
     u64* counts = reinterpret_cast<u64*>(counts_dev);
-    if (hipMemsetAsync(counts, 0, 8 * sizeof(u64), s) != hipSuccess) return sd_fail_msg(SD_ERR_HIP, "memset failed");
+    if (int rc = zero_counts(counts, 8, s); rc != SD_OK) return rc;
     if (n_nodes == 0) return SD_OK;
-    if (n_cells == 0) return sd_fail_msg(SD_ERR_INVALID, "sd_skel_vote: nodes without cells");
+    if (n_cells == 0) return fail(who, ": nodes without cells");
     if (!adj_begin_dev || !node_begin_dev || !classes_dev || !vote_dev || (n_adj && (!adj_nbr_dev || !adj_w_dev)))
-        return sd_fail_msg(SD_ERR_INVALID, "sd_skel_vote: bad argument");
-    if (max_cell_nodes < 1 || max_cell_nodes > n_nodes) return sd_fail_msg(SD_ERR_INVALID, "sd_skel_vote: 1 <= max_cell_nodes <= n_nodes");
-    if (!temp_dev || temp_bytes < sd_skel_vote_temp_bytes(n_nodes, max_cell_nodes))
-        return sd_fail_msg(SD_ERR_INVALID, "sd_skel_vote: scratch smaller than sd_skel_vote_temp_bytes(n_nodes, max_cell_nodes)");
+        return fail(who, ": bad argument");
+    if (max_cell_nodes < 1 || max_cell_nodes > n_nodes) return fail(who, ": 1 <= max_cell_nodes <= n_nodes");
+    if (int rc = check_scratch(who, temp_dev, temp_bytes, sd_skel_vote_temp_bytes(n_nodes, max_cell_nodes), "sd_skel_vote_temp_bytes(n_nodes, max_cell_nodes)"); rc != SD_OK)
+        return rc;
     VoteScratch w;
     layout(w, temp_dev, n_nodes, max_cell_nodes);
     if (hipMemsetAsync(w.redo, 0, n_nodes, s) != hipSuccess) return sd_fail_msg(SD_ERR_HIP, "memset failed");
     const u64* adj_begin = reinterpret_cast<const u64*>(adj_begin_dev);
     const u64* nb = reinterpret_cast<const u64*>(node_begin_dev);
     const u64 N = n_nodes, Cn = n_cells, A = n_adj;
-    hipLaunchKernelGGL(k_skel_vote_lds, dim3(grid_for(64 * N, SD_SKEL_VOTE_GRID)), dim3(256), 0, s, adj_begin, adj_nbr_dev, adj_w_dev, A, nb, Cn, N,
-                       classes_dev, n_classes, max_dist, vote_dev, n_reached_dev, w.redo, counts);
+    launch_1d(k_skel_vote_lds, 64 * N, SD_SKEL_VOTE_GRID, s, adj_begin, adj_nbr_dev, adj_w_dev, A, nb, Cn, N, classes_dev, n_classes, max_dist,
+              vote_dev, n_reached_dev, w.redo, counts);
     hipLaunchKernelGGL(k_skel_vote_glb, dim3((unsigned)w.blocks), dim3(256), 0, s, adj_begin, adj_nbr_dev, adj_w_dev, A, nb, Cn, N, classes_dev, n_classes,
                        max_dist, vote_dev, n_reached_dev, w.redo, w.dist, w.key, w.queue, w.list, (u64)w.m, counts);
     return launch_status("sd_skel_vote: launch failed");
@@ -426,37 +401,34 @@ int sd_skel_components(const int64_t* edges_dev, const uint64_t* edge_begin_dev,
                        uint64_t* counts_dev, void* temp_dev, size_t temp_bytes, void* stream) {
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const char* who = "sd_skel_components";
-    if (!counts_dev) return sd_fail_msg(SD_ERR_INVALID, "sd_skel_components: null counts");
+    if (!counts_dev) return fail(who, ": null counts");
     if (int rc = check_tables(who, n_cells, n_nodes, n_edges); rc != SD_OK) return rc;
     if (soma_class < -1 || soma_class >= SD_SKEL_MAX_CLASSES || one_class < -1 || one_class >= SD_SKEL_MAX_CLASSES || zero_class < 0 ||
         zero_class >= SD_SKEL_MAX_CLASSES)
-        return sd_fail_msg(SD_ERR_INVALID, "sd_skel_components: classes are below 64 (soma and one may be -1: absent)");
+        return fail(who, ": classes are below 64 (soma and one may be -1: absent)");
     u64* counts = reinterpret_cast<u64*>(counts_dev);
-    if (hipMemsetAsync(counts, 0, 8 * sizeof(u64), s) != hipSuccess) return sd_fail_msg(SD_ERR_HIP, "memset failed");
+    if (int rc = zero_counts(counts, 8, s); rc != SD_OK) return rc;
     if (n_nodes == 0) return SD_OK;
-    if (n_cells == 0) return sd_fail_msg(SD_ERR_INVALID, "sd_skel_components: nodes without cells");
+    if (n_cells == 0) return fail(who, ": nodes without cells");
     if (!edge_begin_dev || !node_begin_dev || !classes_dev || !out_dev || (n_edges && !edges_dev))
-        return sd_fail_msg(SD_ERR_INVALID, "sd_skel_components: bad argument");
-    if (!temp_dev || temp_bytes < sd_skel_components_temp_bytes(n_nodes))
-        return sd_fail_msg(SD_ERR_INVALID, "sd_skel_components: scratch smaller than sd_skel_components_temp_bytes(n_nodes)");
+        return fail(who, ": bad argument");
+    if (int rc = check_scratch(who, temp_dev, temp_bytes, sd_skel_components_temp_bytes(n_nodes), "sd_skel_components_temp_bytes(n_nodes)"); rc != SD_OK) return rc;
     CompScratch w;
     layout(w, temp_dev, n_nodes);
     const u64 Cn = n_cells, N = n_nodes, E = n_edges;
     const u64* eb = reinterpret_cast<const u64*>(edge_begin_dev);
     const u64* nb = reinterpret_cast<const u64*>(node_begin_dev);
     const long long* edges = reinterpret_cast<const long long*>(edges_dev);
-    const int gn = grid_for(N, SD_SKEL_NODE_GRID);
-    hipLaunchKernelGGL(k_skel_offsets, dim3(grid_for(Cn, SD_SKEL_NODE_GRID)), dim3(256), 0, s, nb, Cn, N, counts);
-    hipLaunchKernelGGL(k_skel_offsets, dim3(grid_for(Cn, SD_SKEL_NODE_GRID)), dim3(256), 0, s, eb, Cn, E, counts);
-    hipLaunchKernelGGL(k_iota, dim3(gn), dim3(256), 0, s, w.parent, N);
+    launch_1d(k_check_offsets, Cn, SD_SKEL_NODE_GRID, s, nb, Cn, N, counts);
+    launch_1d(k_check_offsets, Cn, SD_SKEL_NODE_GRID, s, eb, Cn, E, counts);
+    launch_1d(k_iota, N, SD_SKEL_NODE_GRID, s, w.parent, N);
     if (hipMemsetAsync(w.best, 0, n_nodes * sizeof(u64), s) != hipSuccess) return sd_fail_msg(SD_ERR_HIP, "memset failed");
-    if (E)
-        hipLaunchKernelGGL(k_cc_union, dim3(grid_for(E, SD_SKEL_EDGE_GRID)), dim3(256), 0, s, edges, eb, nb, Cn, N, E, classes_dev, soma_class, w.parent, counts);
-    hipLaunchKernelGGL(k_cc_keys, dim3(gn), dim3(256), 0, s, w.parent, classes_dev, soma_class, N, w.root, w.key);
+    if (E) launch_1d(k_cc_union, E, SD_SKEL_EDGE_GRID, s, edges, eb, nb, Cn, N, E, classes_dev, soma_class, w.parent, counts);
+    launch_1d(k_cc_keys, N, SD_SKEL_NODE_GRID, s, w.parent, classes_dev, soma_class, N, w.root, w.key);
     if (int rc = sort_by_key(who, w.prim, w.key, w.skey, w.i0, w.perm, n_nodes, bits_for(N + 1) + 6, s); rc != SD_OK) return rc;
-    hipLaunchKernelGGL(k_heads, dim3(gn), dim3(256), 0, s, w.skey, (const u64*)nullptr, w.head, N);
-    hipLaunchKernelGGL(k_cc_best, dim3(gn), dim3(256), 0, s, w.skey, w.head, N, w.best);
-    hipLaunchKernelGGL(k_cc_write, dim3(gn), dim3(256), 0, s, w.skey, w.root, w.best, classes_dev, one_class, zero_class, N, out_dev, counts);
+    launch_1d(k_heads, N, SD_SKEL_NODE_GRID, s, w.skey, (const u64*)nullptr, w.head, N);
+    launch_1d(k_cc_best, N, SD_SKEL_NODE_GRID, s, w.skey, w.head, N, w.best);
+    launch_1d(k_cc_write, N, SD_SKEL_NODE_GRID, s, w.skey, w.root, w.best, classes_dev, one_class, zero_class, N, out_dev, counts);
     return launch_status("sd_skel_components: launch failed");
 }
 

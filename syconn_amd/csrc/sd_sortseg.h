@@ -1,4 +1,5 @@
-// The scratch rule and the sort / segment sequence of the dataset merges (sd_propmerge.hip, sd_cs_merge.hip, sd_syn_ssv.hip).
+// The scratch rule and the sort / segment sequence of the dataset merges (sd_propmerge.hip, sd_cs_merge.hip, sd_syn_ssv.hip, ...), over
+// the types, the grid-stride walk and the searches of sd_tables.h.
 //   scratch   a merge lists its scratch arrays ONCE, in a function that takes them from a ScratchAlloc: without a base pointer that
 //             function is the size query (*_temp_bytes), over the caller's buffer it hands out the pointers.  Every array starts on a
 //             256-byte boundary; the rocPRIM scratch (take_prim) serves every sort and scan of the call.
@@ -6,7 +7,7 @@
 //             that exists already), a head flag at the first record of every key and an inclusive scan of the flags that numbers the
 //             segments (number_segments); scan_u32 is the bare scan.  Failures read "<entry point>: radix sort failed" / ": scan failed".
 #pragma once
-#include "sd_host_util.h"
+#include "sd_tables.h"
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include <stdint.h>
@@ -15,15 +16,12 @@
 
 namespace {
 
-typedef unsigned long long u64;
-typedef unsigned int u32;
-
 __global__ __launch_bounds__(256) void k_iota(u32* p, u64 n) {
-    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256) p[i] = (u32)i;
+    for (u64 i = grid_tid(); i < n; i += grid_stride()) p[i] = (u32)i;
 }
 // head[i] = 1 where a new key starts in the sorted order
 __global__ __launch_bounds__(256) void k_heads(const u64* ka, const u64* kb /* may be nullptr */, u32* head, u64 n) {
-    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256)
+    for (u64 i = grid_tid(); i < n; i += grid_stride())
         head[i] = (i == 0 || ka[i] != ka[i - 1] || (kb && kb[i] != kb[i - 1])) ? 1u : 0u;
 }
 
@@ -65,7 +63,7 @@ inline int sort_carry(const char* who, const PrimScratch& prim, Keys keys, u64* 
 template <class Keys>
 inline int sort_by_key(const char* who, const PrimScratch& prim, Keys keys, u64* keys_sorted, u32* iota, u32* perm_out, size_t n, int bits,
                        hipStream_t s) {
-    hipLaunchKernelGGL(k_iota, dim3(grid_for(n, 4096)), dim3(256), 0, s, iota, (u64)n);
+    launch_1d(k_iota, n, 4096, s, iota, (u64)n);
     return sort_carry(who, prim, keys, keys_sorted, iota, perm_out, n, bits, s);
 }
 inline int scan_u32(const char* who, const PrimScratch& prim, u32* in, u32* out, size_t n, hipStream_t s) {
@@ -76,7 +74,7 @@ inline int scan_u32(const char* who, const PrimScratch& prim, u32* in, u32* out,
 // head flags of the sorted keys (ka, and kb where given) and the 1-based segment number of every record
 inline int number_segments(const char* who, const PrimScratch& prim, const u64* ka, const u64* kb, u32* head, u32* seg, size_t n,
                            hipStream_t s) {
-    hipLaunchKernelGGL(k_heads, dim3(grid_for(n, 4096)), dim3(256), 0, s, ka, kb, head, (u64)n);
+    launch_1d(k_heads, n, 4096, s, ka, kb, head, (u64)n);
     return scan_u32(who, prim, head, seg, n, s);
 }
 

@@ -46,7 +46,7 @@ __device__ __forceinline__ u64 spread3(u32 v) {              // bit i of v -> bi
 __global__ __launch_bounds__(256) void k_knn_cell_box(const void* __restrict__ pts, int f32, const u64* __restrict__ begin, u64 n_cells, u64 n_pts,
                                                       double* cbox, u64* counts) {
     const int lane = threadIdx.x & 63;
-    const u64 wave = ((u64)blockIdx.x * 256 + threadIdx.x) >> 6, n_waves = ((u64)gridDim.x * 256) >> 6;
+    const u64 wave = grid_tid() >> 6, n_waves = grid_stride() >> 6;
     for (u64 c = wave; c < n_cells; c += n_waves) {
         const u64 b0 = begin[c], b1 = begin[c + 1];
         const bool bad = b1 < b0 || b1 > n_pts || (c == 0 && b0 != 0) || (c == n_cells - 1 && b1 != n_pts);
@@ -67,7 +67,7 @@ __global__ __launch_bounds__(256) void k_knn_cell_box(const void* __restrict__ p
 }
 __global__ __launch_bounds__(256) void k_knn_keys(const void* __restrict__ pts, int f32, const u64* __restrict__ begin, const double* __restrict__ cbox,
                                                   u64 n_cells, u64 n_pts, u64* key) {
-    for (u64 j = (u64)blockIdx.x * 256 + threadIdx.x; j < n_pts; j += (u64)gridDim.x * 256) {
+    for (u64 j = grid_tid(); j < n_pts; j += grid_stride()) {
         const u64 c = segment_of(begin, n_cells, j);
         const double g = cbox[4 * c + 3];
         u64 k = 0;
@@ -81,7 +81,7 @@ __global__ __launch_bounds__(256) void k_knn_keys(const void* __restrict__ pts, 
     }
 }
 __global__ __launch_bounds__(256) void k_knn_place(const void* __restrict__ pts, int f32, const u32* __restrict__ perm, u64 n_pts, double* spts) {
-    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n_pts; i += (u64)gridDim.x * 256) {
+    for (u64 i = grid_tid(); i < n_pts; i += grid_stride()) {
         u64 j = perm[i];
         if (j >= n_pts) j = n_pts - 1;
 #pragma unroll
@@ -127,7 +127,7 @@ __global__ __launch_bounds__(256) void k_knn_query(const double* __restrict__ sp
                                                    const u32* __restrict__ q_cell, const double* __restrict__ q_xyz, u64 n_q, int k, int* vote,
                                                    int* nn_idx, double* nn_d2, u64* counts) {
     const int lane = threadIdx.x & 63;
-    const u64 wave = ((u64)blockIdx.x * 256 + threadIdx.x) >> 6, n_waves = ((u64)gridDim.x * 256) >> 6;
+    const u64 wave = grid_tid() >> 6, n_waves = grid_stride() >> 6;
     u64 n_visit = 0, n_skip = 0;
     bool bad = false;
     for (u64 q = wave; q < n_q; q += n_waves) {
@@ -206,7 +206,7 @@ __global__ __launch_bounds__(256) void k_forest(const double* __restrict__ rows,
                                                 const double* __restrict__ proba, const int* __restrict__ tree_begin, int n_trees, int n_nodes,
                                                 int n_classes, double* out, u64* counts) {
     bool bad = false;
-    for (u64 r = (u64)blockIdx.x * 256 + threadIdx.x; r < n_rows; r += (u64)gridDim.x * 256) {
+    for (u64 r = grid_tid(); r < n_rows; r += grid_stride()) {
         double* o = out + r * (u64)n_classes;
         for (int c = 0; c < n_classes; ++c) o[c] = 0.0;
         for (int t = 0; t < n_trees; ++t) {
@@ -258,19 +258,19 @@ int sd_syn_props_knn(const void* points_dev, int points_f32, const uint64_t* beg
                      void* stream) {
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const char* who = "sd_syn_props_knn";
-    if (!counts_dev) return sd_fail_msg(SD_ERR_INVALID, "sd_syn_props_knn: null counts");
-    if (k < 1 || k > SD_SYN_PROPS_MAX_K) return sd_fail_msg(SD_ERR_INVALID, "sd_syn_props_knn: 1 <= k <= 64");
+    if (!counts_dev) return fail(who, ": null counts");
+    if (k < 1 || k > SD_SYN_PROPS_MAX_K) return fail(who, ": 1 <= k <= 64");
     if (n_points >= LIM31 || n_q >= LIM31 || n_cells >= LIM31)
-        return sd_fail_msg(SD_ERR_INVALID, "sd_syn_props_knn: points, queries and cells < 2^31 per call");
+        return fail(who, ": points, queries and cells < 2^31 per call");
     u64* counts = reinterpret_cast<u64*>(counts_dev);
-    if (hipMemsetAsync(counts, 0, 8 * sizeof(u64), s) != hipSuccess) return sd_fail_msg(SD_ERR_HIP, "memset failed");
+    if (int rc = zero_counts(counts, 8, s); rc != SD_OK) return rc;
     if (n_cells == 0 || !(stages & 3)) {
-        if (n_q) return sd_fail_msg(SD_ERR_INVALID, "sd_syn_props_knn: queries without cells");
+        if (n_q) return fail(who, ": queries without cells");
         return SD_OK;
     }
-    if (!begin_dev || (n_points && !points_dev)) return sd_fail_msg(SD_ERR_INVALID, "sd_syn_props_knn: bad argument");
-    if (!temp_dev || temp_bytes < sd_syn_props_knn_temp_bytes(n_points, n_cells))
-        return sd_fail_msg(SD_ERR_INVALID, "sd_syn_props_knn: scratch smaller than sd_syn_props_knn_temp_bytes(n_points, n_cells)");
+    if (!begin_dev || (n_points && !points_dev)) return fail(who, ": bad argument");
+    if (int rc = check_scratch(who, temp_dev, temp_bytes, sd_syn_props_knn_temp_bytes(n_points, n_cells), "sd_syn_props_knn_temp_bytes(n_points, n_cells)"); rc != SD_OK)
+        return rc;
     KnnScratch w;
     layout(w, temp_dev, n_points ? n_points : 1, n_cells);
     const u64 N = n_points, Cn = n_cells, Q = n_q;
@@ -278,20 +278,18 @@ int sd_syn_props_knn(const void* points_dev, int points_f32, const uint64_t* beg
     const int f32 = points_f32 ? 1 : 0;
     if (stages & 1) {
         const int cbits = bits_for(Cn);
-        const int gc = grid_for(64 * Cn, SD_SYN_PROPS_CELL_GRID);
-        hipLaunchKernelGGL(k_knn_cell_box, dim3(gc), dim3(256), 0, s, points_dev, f32, begin, Cn, N, w.cbox, counts);
+        launch_1d(k_knn_cell_box, 64 * Cn, SD_SYN_PROPS_CELL_GRID, s, points_dev, f32, begin, Cn, N, w.cbox, counts);
         if (N) {
-            const int gp = grid_for(N, SD_SYN_PROPS_POINT_GRID);
-            hipLaunchKernelGGL(k_knn_keys, dim3(gp), dim3(256), 0, s, points_dev, f32, begin, w.cbox, Cn, N, w.key);
+            launch_1d(k_knn_keys, N, SD_SYN_PROPS_POINT_GRID, s, points_dev, f32, begin, w.cbox, Cn, N, w.key);
             if (int rc = sort_by_key(who, w.prim, w.key, w.skey, w.i0, w.perm, n_points, cbits + 3 * KNN_BITS, s); rc != SD_OK) return rc;
-            hipLaunchKernelGGL(k_knn_place, dim3(gp), dim3(256), 0, s, points_dev, f32, w.perm, N, w.spts);
-            hipLaunchKernelGGL(k_tile_boxes<false>, dim3(gc), dim3(256), 0, s, w.spts, begin, Cn, N, (u64)w.n_slots, w.tbox, (double*)nullptr);
+            launch_1d(k_knn_place, N, SD_SYN_PROPS_POINT_GRID, s, points_dev, f32, w.perm, N, w.spts);
+            launch_1d(k_tile_boxes<false>, 64 * Cn, SD_SYN_PROPS_CELL_GRID, s, w.spts, begin, Cn, N, (u64)w.n_slots, w.tbox, (double*)nullptr);
         }
     }
     if ((stages & 2) && Q) {
-        if (!q_cell_dev || !q_xyz_dev || !vote_dev) return sd_fail_msg(SD_ERR_INVALID, "sd_syn_props_knn: bad argument");
-        hipLaunchKernelGGL(k_knn_query, dim3(grid_for(64 * Q, SD_SYN_PROPS_QUERY_GRID)), dim3(256), 0, s, w.spts, w.perm, labels_dev, begin, Cn, N,
-                           w.tbox, (u64)w.n_slots, q_cell_dev, q_xyz_dev, Q, k, vote_dev, nn_idx_dev, nn_d2_dev, counts);
+        if (!q_cell_dev || !q_xyz_dev || !vote_dev) return fail(who, ": bad argument");
+        launch_1d(k_knn_query, 64 * Q, SD_SYN_PROPS_QUERY_GRID, s, w.spts, w.perm, labels_dev, begin, Cn, N, w.tbox, (u64)w.n_slots, q_cell_dev,
+                  q_xyz_dev, Q, k, vote_dev, nn_idx_dev, nn_d2_dev, counts);
     }
     return launch_status("sd_syn_props_knn: launch failed");
 }
@@ -300,16 +298,16 @@ int sd_syn_props_forest(const double* rows_dev, size_t n_rows, int n_features, c
                         const int32_t* left_dev, const int32_t* right_dev, const double* proba_dev, const int32_t* tree_begin_dev, int n_trees,
                         int n_nodes, int n_classes, double* out_dev, uint64_t* counts_dev, void* stream) {
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (!counts_dev) return sd_fail_msg(SD_ERR_INVALID, "sd_syn_props_forest: null counts");
+    const char* who = "sd_syn_props_forest";
+    if (!counts_dev) return fail(who, ": null counts");
     if (n_features < 1 || n_trees < 1 || n_nodes < n_trees || n_classes < 1 || n_rows >= LIM31)
-        return sd_fail_msg(SD_ERR_INVALID, "sd_syn_props_forest: features, trees, classes >= 1, a node per tree, rows < 2^31");
-    if (hipMemsetAsync(counts_dev, 0, 8 * sizeof(u64), s) != hipSuccess) return sd_fail_msg(SD_ERR_HIP, "memset failed");
+        return fail(who, ": features, trees, classes >= 1, a node per tree, rows < 2^31");
+    if (int rc = zero_counts(counts_dev, 8, s); rc != SD_OK) return rc;
     if (n_rows == 0) return SD_OK;
     if (!rows_dev || !feature_dev || !threshold_dev || !left_dev || !right_dev || !proba_dev || !tree_begin_dev || !out_dev)
-        return sd_fail_msg(SD_ERR_INVALID, "sd_syn_props_forest: bad argument");
-    hipLaunchKernelGGL(k_forest, dim3(grid_for(n_rows, SD_SYN_PROPS_FOREST_GRID)), dim3(256), 0, s, rows_dev, (u64)n_rows, n_features, feature_dev,
-                       threshold_dev, left_dev, right_dev, proba_dev, tree_begin_dev, n_trees, n_nodes, n_classes, out_dev,
-                       reinterpret_cast<u64*>(counts_dev));
+        return fail(who, ": bad argument");
+    launch_1d(k_forest, n_rows, SD_SYN_PROPS_FOREST_GRID, s, rows_dev, (u64)n_rows, n_features, feature_dev, threshold_dev, left_dev, right_dev,
+              proba_dev, tree_begin_dev, n_trees, n_nodes, n_classes, out_dev, reinterpret_cast<u64*>(counts_dev));
     return launch_status("sd_syn_props_forest: launch failed");
 }
 

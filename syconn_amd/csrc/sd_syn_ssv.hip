@@ -15,7 +15,7 @@
 //   link     one wave per cell walks the lexicographically upper half of its neighbourhood (64 neighbours per trip, found by binary
 //            search in the sorted cell keys).  From the two tight boxes: smallest possible distance >= gap -> nothing; largest
 //            possible distance < gap -> union (both with a margin of 1e-9 for rounding, so that only point_d2 decides at the gap); otherwise, unless both are in one set already, the 64 lanes test voxel pairs and
-//            stop at the first hit (ballot).  Union-find over the cells as in sd_objseg.hip (larger root under the smaller, atomicMin).
+//            stop at the first hit (ballot).  Union-find over the cells: uf_union of sd_tables.h (larger root under the smaller).
 //   number   smallest flat index per root; a flag at that index, scanned over the flat order, numbers the components in ascending
 //            order of their smallest flat index -- which is the reference's order, and group-major because the flat order is.
 //   stats    stable sort of the voxels by component (flat order survives inside a component), head flags over (component,
@@ -27,7 +27,7 @@
 // assembly.
 #include "../../include/syconn_dense.h"
 #include "sd_sortseg.h"
-#include "sd_pointtiles.h"
+#include "sd_tables.h"
 
 namespace {
 
@@ -36,23 +36,6 @@ struct SsvGeom {
     double gap2_lo, gap2_hi; // gap2 (1 -+ 1e-9): the box tests decide only what rounding cannot change; the rest is left to point_d2
     int c[3], b[3], r[3];   // cell dimension in voxels, key bits per axis, reach in cells per axis
 };
-
-__device__ __forceinline__ u32 uf_find(const u32* L, u32 a) {
-    u32 p = __hip_atomic_load(&L[a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    while (p != a) { a = p; p = __hip_atomic_load(&L[a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-    return a;
-}
-__device__ __forceinline__ void uf_union(u32* L, u32 a, u32 b) {
-    while (true) {
-        a = uf_find(L, a);
-        b = uf_find(L, b);
-        if (a == b) return;
-        if (a < b) { const u32 t = a; a = b; b = t; }        // the larger root goes under the smaller one
-        const u32 old = atomicMin(&L[a], b);
-        if (old == a) return;
-        a = old;
-    }
-}
 
 // do all 64 lanes of the wave hold a valid item with the same key?  (called by every lane)
 __device__ __forceinline__ bool wave_same(u32 key, bool active) {
@@ -63,7 +46,7 @@ __device__ __forceinline__ bool wave_same(u32 key, bool active) {
 // ---- cells ------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_ssv_keys(const int* __restrict__ vox, const u32* __restrict__ vfrag, const u32* __restrict__ fgroup,
                                                   const int* __restrict__ gorg, u64 n, u64 n_frag, u64 n_group, SsvGeom g, u64* key, u64* counts) {
-    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256) {
+    for (u64 i = grid_tid(); i < n; i += grid_stride()) {
         const u32 f = vfrag[i];
         u64 grp = f < n_frag ? fgroup[f] : n_group;
         bool bad = grp >= n_group;
@@ -83,7 +66,7 @@ __global__ __launch_bounds__(256) void k_ssv_keys(const int* __restrict__ vox, c
 // per cell: start in the sorted order, key, itself as union-find parent, an empty box; the sentinel start and the cell count
 __global__ __launch_bounds__(256) void k_ssv_cells(const u64* skey, const u32* head, const u32* seg, u64 n, u32* cell_start, u64* cell_key,
                                                    u32* parent, u32* minflat, int* box, u64* counts) {
-    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256) {
+    for (u64 i = grid_tid(); i < n; i += grid_stride()) {
         if (head[i]) {
             const u32 c = seg[i] - 1u;
             cell_start[c] = (u32)i; cell_key[c] = skey[i]; parent[c] = c; minflat[c] = 0xffffffffu;
@@ -97,7 +80,7 @@ __global__ __launch_bounds__(256) void k_ssv_cells(const u64* skey, const u32* h
 // the voxel rows in sorted order and the tight box of every cell (one atomic per wave where the wave holds one cell)
 __global__ __launch_bounds__(256) void k_ssv_cell_boxes(const int* __restrict__ vox, const u32* perm, const u32* seg, u64 n, int* svox, int* box) {
     const int lane = threadIdx.x & 63;
-    for (u64 base = (u64)blockIdx.x * 256; base < n; base += (u64)gridDim.x * 256) {
+    for (u64 base = (u64)blockIdx.x * 256; base < n; base += grid_stride()) {
         const u64 i = base + threadIdx.x;
         const bool act = i < n;
         u32 c = 0; int v[3] = {0, 0, 0};
@@ -169,7 +152,7 @@ __device__ bool pair_test(const int* __restrict__ svox, u32 a0, u32 a1, u32 b0, 
 __global__ __launch_bounds__(256) void k_ssv_link(const int* __restrict__ svox, const u32* cell_start, const u64* cell_key, const int* box,
                                                   u32* parent, SsvGeom g, u64* counts) {
     const int lane = threadIdx.x & 63;
-    const u64 wave = ((u64)blockIdx.x * 256 + threadIdx.x) >> 6, n_waves = ((u64)gridDim.x * 256) >> 6;
+    const u64 wave = grid_tid() >> 6, n_waves = grid_stride() >> 6;
     const u64 n_cells = counts[1];
     const int wy = 2 * g.r[1] + 1, wz = 2 * g.r[2] + 1;
     const int T = (2 * g.r[0] + 1) * wy * wz, M = (T - 1) / 2;                  // the upper half of the neighbourhood: t > T / 2
@@ -240,23 +223,23 @@ __global__ __launch_bounds__(256) void k_ssv_link(const int* __restrict__ svox, 
 
 __global__ __launch_bounds__(256) void k_ssv_compress(u32* parent, const u64* counts) {
     const u64 n_cells = counts[1];
-    for (u64 c = (u64)blockIdx.x * 256 + threadIdx.x; c < n_cells; c += (u64)gridDim.x * 256) parent[c] = uf_find(parent, (u32)c);
+    for (u64 c = grid_tid(); c < n_cells; c += grid_stride()) parent[c] = uf_find(parent, (u32)c);
 }
 
 // ---- number -----------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_ssv_rootmin(const u32* parent, const u32* cell_start, const u32* perm, u32* minflat, const u64* counts) {
     const u64 n_cells = counts[1];
-    for (u64 c = (u64)blockIdx.x * 256 + threadIdx.x; c < n_cells; c += (u64)gridDim.x * 256)
+    for (u64 c = grid_tid(); c < n_cells; c += grid_stride())
         atomicMin(&minflat[parent[c]], perm[cell_start[c]]);                     // stable sort: the first voxel of a cell is its smallest
 }
 __global__ __launch_bounds__(256) void k_ssv_flag(const u32* parent, const u32* minflat, u32* flag, const u64* counts) {
     const u64 n_cells = counts[1];
-    for (u64 c = (u64)blockIdx.x * 256 + threadIdx.x; c < n_cells; c += (u64)gridDim.x * 256)
+    for (u64 c = grid_tid(); c < n_cells; c += grid_stride())
         if (parent[c] == (u32)c) flag[minflat[c]] = 1u;
 }
 __global__ __launch_bounds__(256) void k_ssv_labels(const u32* perm, const u32* seg, const u32* parent, const u32* minflat, const u32* fscan,
                                                     u64 n, int* labels, u64* counts) {
-    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256) {
+    for (u64 i = grid_tid(); i < n; i += grid_stride()) {
         labels[perm[i]] = (int)(fscan[minflat[parent[seg[i] - 1u]]] - 1u);
         if (i == n - 1) counts[0] = fscan[n - 1];
     }
@@ -264,14 +247,14 @@ __global__ __launch_bounds__(256) void k_ssv_labels(const u32* perm, const u32* 
 
 // ---- statistics -------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_ssv_compkeys(const int* labels, u64 n, u64 K, u64* key, u64* counts) {
-    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256) {
+    for (u64 i = grid_tid(); i < n; i += grid_stride()) {
         const u64 k = (u64)(u32)labels[i];
         if (k >= K) counts[3] = 1;
         key[i] = k < K ? k : K - 1;
     }
 }
 __global__ __launch_bounds__(256) void k_ssv_stat_init(u64 K, int* bbox, u64* sums, u64* best, u32* rep) {
-    for (u64 k = (u64)blockIdx.x * 256 + threadIdx.x; k < K; k += (u64)gridDim.x * 256) {
+    for (u64 k = grid_tid(); k < K; k += grid_stride()) {
 #pragma unroll
         for (int a = 0; a < 3; ++a) { bbox[6 * k + a] = 0x7fffffff; bbox[6 * k + 3 + a] = (int)0x80000000; sums[3 * k + a] = 0; }
         best[k] = ~0ull; rep[k] = 0xffffffffu;
@@ -279,7 +262,7 @@ __global__ __launch_bounds__(256) void k_ssv_stat_init(u64 K, int* bbox, u64* su
 }
 // heads of the components and of the (component, fragment) runs in the sorted order
 __global__ __launch_bounds__(256) void k_ssv_stat_heads(const u64* skey, const u32* sflat, const u32* vfrag, u64 n, u32* headp, u32* comp_begin) {
-    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256) {
+    for (u64 i = grid_tid(); i < n; i += grid_stride()) {
         const bool hc = i == 0 || skey[i] != skey[i - 1];
         headp[i] = (hc || vfrag[sflat[i]] != vfrag[sflat[i - 1]]) ? 1u : 0u;
         if (hc) comp_begin[skey[i]] = (u32)i;
@@ -288,7 +271,7 @@ __global__ __launch_bounds__(256) void k_ssv_stat_heads(const u64* skey, const u
 }
 __global__ __launch_bounds__(256) void k_ssv_stat_pairs(const u64* skey, const u32* sflat, const u32* vfrag, const u32* headp, const u32* pscan,
                                                         u64 n, u32* pair_comp, u32* pair_frag, u32* pair_begin, u64* counts) {
-    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256) {
+    for (u64 i = grid_tid(); i < n; i += grid_stride()) {
         if (headp[i]) {
             const u32 p = pscan[i] - 1u;
             pair_comp[p] = (u32)skey[i]; pair_frag[p] = vfrag[sflat[i]]; pair_begin[p] = (u32)i;
@@ -298,7 +281,7 @@ __global__ __launch_bounds__(256) void k_ssv_stat_pairs(const u64* skey, const u
 }
 __global__ __launch_bounds__(256) void k_ssv_stat_reduce(const int* __restrict__ vox, const u64* skey, const u32* sflat, u64 n, int* bbox, u64* sums) {
     const int lane = threadIdx.x & 63;
-    for (u64 base = (u64)blockIdx.x * 256; base < n; base += (u64)gridDim.x * 256) {
+    for (u64 base = (u64)blockIdx.x * 256; base < n; base += grid_stride()) {
         const u64 i = base + threadIdx.x;
         const bool act = i < n;
         u32 k = 0; int v[3] = {0, 0, 0};
@@ -333,7 +316,7 @@ __global__ __launch_bounds__(256) void k_ssv_stat_reduce(const int* __restrict__
 __global__ __launch_bounds__(256) void k_ssv_stat_dist(const int* __restrict__ vox, const u64* skey, const u32* sflat, const u32* comp_begin,
                                                        const u64* sums, u64 n, SsvGeom g, u64* d2bits, u64* best) {
     const int lane = threadIdx.x & 63;
-    for (u64 base = (u64)blockIdx.x * 256; base < n; base += (u64)gridDim.x * 256) {
+    for (u64 base = (u64)blockIdx.x * 256; base < n; base += grid_stride()) {
         const u64 i = base + threadIdx.x;
         const bool act = i < n;
         u32 k = 0; u64 bits = ~0ull;
@@ -361,20 +344,20 @@ __global__ __launch_bounds__(256) void k_ssv_stat_dist(const int* __restrict__ v
     }
 }
 __global__ __launch_bounds__(256) void k_ssv_stat_rep(const u64* skey, const u32* sflat, const u64* d2bits, const u64* best, u64 n, u32* rep) {
-    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256) {
+    for (u64 i = grid_tid(); i < n; i += grid_stride()) {
         const u64 k = skey[i];
         if (d2bits[i] == best[k]) atomicMin(&rep[k], sflat[i]);
     }
 }
 __global__ __launch_bounds__(256) void k_ssv_stat_keep(const u64* skey, const u32* comp_begin, u64 n, u64 min_vx, u32* keep) {
-    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256) {
+    for (u64 i = grid_tid(); i < n; i += grid_stride()) {
         const u64 k = skey[i];
         keep[i] = (u64)(comp_begin[k + 1] - comp_begin[k]) >= min_vx ? 1u : 0u;
     }
 }
 __global__ __launch_bounds__(256) void k_ssv_stat_gather(const int* __restrict__ vox, const u32* sflat, const u32* keep, const u32* kscan, u64 n,
                                                          u32* vox_out, u64* counts) {
-    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256) {
+    for (u64 i = grid_tid(); i < n; i += grid_stride()) {
         if (keep[i]) {
             const u64 o = kscan[i] - 1u, p = sflat[i];
             vox_out[3 * o] = (u32)vox[3 * p]; vox_out[3 * o + 1] = (u32)vox[3 * p + 1]; vox_out[3 * o + 2] = (u32)vox[3 * p + 2];
@@ -440,46 +423,43 @@ int sd_syn_ssv_components(const int32_t* vox_dev, const uint32_t* vox_frag_dev, 
                           const int32_t* bits_host, int stages, int32_t* labels_dev, uint64_t* counts_dev, void* temp_dev, size_t temp_bytes,
                           void* stream) {
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (!counts_dev) return sd_fail_msg(SD_ERR_INVALID, "sd_syn_ssv_components: null counts");
+    const char* who = "sd_syn_ssv_components";
+    if (!counts_dev) return fail(who, ": null counts");
     u64* counts = reinterpret_cast<u64*>(counts_dev);
-    if ((stages & 1) && hipMemsetAsync(counts, 0, 8 * sizeof(u64), s) != hipSuccess) return sd_fail_msg(SD_ERR_HIP, "memset failed");
+    if (stages & 1)
+        if (int rc = zero_counts(counts, 8, s); rc != SD_OK) return rc;
     if (n_vox == 0) return SD_OK;
     if (!vox_dev || !vox_frag_dev || !frag_group_dev || !group_origin_dev || !labels_dev || !n_frag || !n_group)
-        return sd_fail_msg(SD_ERR_INVALID, "sd_syn_ssv_components: bad argument");
-    if (n_vox >= (1ull << 31)) return sd_fail_msg(SD_ERR_INVALID, "sd_syn_ssv_components: < 2^31 voxel rows per call");
+        return fail(who, ": bad argument");
+    if (n_vox >= LIM31) return fail(who, ": < 2^31 voxel rows per call");
     SsvGeom g;
     if (!ssv_geom(scale_host, gap_nm, cell_host, bits_host, g))
-        return sd_fail_msg(SD_ERR_INVALID, "sd_syn_ssv_components: bad geometry (the scaled diagonal of a cell must be below the gap)");
+        return fail(who, ": bad geometry (the scaled diagonal of a cell must be below the gap)");
     int gbits = 0;
     while (gbits < 64 && ((u64)(n_group - 1) >> gbits)) ++gbits;
     const int kbits = gbits + g.b[0] + g.b[1] + g.b[2];
-    if (kbits > 63) return sd_fail_msg(SD_ERR_INVALID, "sd_syn_ssv_components: group and cell coordinates need more than 63 key bits");
-    if (!temp_dev || temp_bytes < sd_syn_ssv_temp_bytes(n_vox))
-        return sd_fail_msg(SD_ERR_INVALID, "sd_syn_ssv_components: scratch smaller than sd_syn_ssv_temp_bytes(n_vox)");
+    if (kbits > 63) return fail(who, ": group and cell coordinates need more than 63 key bits");
+    if (int rc = check_scratch(who, temp_dev, temp_bytes, sd_syn_ssv_temp_bytes(n_vox), "sd_syn_ssv_temp_bytes(n_vox)"); rc != SD_OK) return rc;
     SsvCompScratch w;
     layout(w, temp_dev, n_vox);
-    const char* who = "sd_syn_ssv_components";
     const u64 n = n_vox;
-    const int gv = grid_for(n, 4096);
     if (stages & 1) {
-        hipLaunchKernelGGL(k_ssv_keys, dim3(gv), dim3(256), 0, s, vox_dev, vox_frag_dev, frag_group_dev, group_origin_dev, n, (u64)n_frag,
-                           (u64)n_group, g, w.key, counts);
+        launch_1d(k_ssv_keys, n, 4096, s, vox_dev, vox_frag_dev, frag_group_dev, group_origin_dev, n, (u64)n_frag, (u64)n_group, g, w.key, counts);
         if (int rc = sort_by_key(who, w.prim, w.key, w.skey, w.i0, w.perm, n_vox, kbits > 0 ? kbits : 1, s); rc != SD_OK) return rc;
         if (int rc = number_segments(who, w.prim, w.skey, nullptr, w.head, w.seg, n_vox, s); rc != SD_OK) return rc;
-        hipLaunchKernelGGL(k_ssv_cells, dim3(gv), dim3(256), 0, s, w.skey, w.head, w.seg, n, w.cell_start, w.cell_key, w.parent, w.minflat, w.box,
-                           counts);
-        hipLaunchKernelGGL(k_ssv_cell_boxes, dim3(gv), dim3(256), 0, s, vox_dev, w.perm, w.seg, n, w.svox, w.box);
+        launch_1d(k_ssv_cells, n, 4096, s, w.skey, w.head, w.seg, n, w.cell_start, w.cell_key, w.parent, w.minflat, w.box, counts);
+        launch_1d(k_ssv_cell_boxes, n, 4096, s, vox_dev, w.perm, w.seg, n, w.svox, w.box);
     }
     if (stages & 2) {
-        hipLaunchKernelGGL(k_ssv_link, dim3(grid_for(64 * n, 4096)), dim3(256), 0, s, w.svox, w.cell_start, w.cell_key, w.box, w.parent, g, counts);
-        hipLaunchKernelGGL(k_ssv_compress, dim3(gv), dim3(256), 0, s, w.parent, counts);
+        launch_1d(k_ssv_link, 64 * n, 4096, s, w.svox, w.cell_start, w.cell_key, w.box, w.parent, g, counts);
+        launch_1d(k_ssv_compress, n, 4096, s, w.parent, counts);
     }
     if (stages & 4) {
         if (hipMemsetAsync(w.flag, 0, n * sizeof(u32), s) != hipSuccess) return sd_fail_msg(SD_ERR_HIP, "memset failed");
-        hipLaunchKernelGGL(k_ssv_rootmin, dim3(gv), dim3(256), 0, s, w.parent, w.cell_start, w.perm, w.minflat, counts);
-        hipLaunchKernelGGL(k_ssv_flag, dim3(gv), dim3(256), 0, s, w.parent, w.minflat, w.flag, counts);
+        launch_1d(k_ssv_rootmin, n, 4096, s, w.parent, w.cell_start, w.perm, w.minflat, counts);
+        launch_1d(k_ssv_flag, n, 4096, s, w.parent, w.minflat, w.flag, counts);
         if (int rc = scan_u32(who, w.prim, w.flag, w.fscan, n_vox, s); rc != SD_OK) return rc;
-        hipLaunchKernelGGL(k_ssv_labels, dim3(gv), dim3(256), 0, s, w.perm, w.seg, w.parent, w.minflat, w.fscan, n, labels_dev, counts);
+        launch_1d(k_ssv_labels, n, 4096, s, w.perm, w.seg, w.parent, w.minflat, w.fscan, n, labels_dev, counts);
     }
     return launch_status("sd_syn_ssv_components: launch failed");
 }
@@ -489,40 +469,37 @@ int sd_syn_ssv_stats(const int32_t* vox_dev, const uint32_t* vox_frag_dev, const
                      uint32_t* pair_comp_dev, uint32_t* pair_frag_dev, uint32_t* pair_begin_dev, uint32_t* vox_out_dev, uint64_t* counts_dev,
                      void* temp_dev, size_t temp_bytes, void* stream) {
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (!counts_dev) return sd_fail_msg(SD_ERR_INVALID, "sd_syn_ssv_stats: null counts");
+    const char* who = "sd_syn_ssv_stats";
+    if (!counts_dev) return fail(who, ": null counts");
     u64* counts = reinterpret_cast<u64*>(counts_dev);
-    if (hipMemsetAsync(counts, 0, 4 * sizeof(u64), s) != hipSuccess) return sd_fail_msg(SD_ERR_HIP, "memset failed");
+    if (int rc = zero_counts(counts, 4, s); rc != SD_OK) return rc;
     if (n_vox == 0) return SD_OK;
     if (!vox_dev || !vox_frag_dev || !labels_dev || !n_comp || n_comp > n_vox || !comp_begin_dev || !bbox_dev || !rep_flat_dev || !pair_comp_dev ||
         !pair_frag_dev || !pair_begin_dev || !vox_out_dev)
-        return sd_fail_msg(SD_ERR_INVALID, "sd_syn_ssv_stats: bad argument");
-    if (n_vox >= (1ull << 31)) return sd_fail_msg(SD_ERR_INVALID, "sd_syn_ssv_stats: < 2^31 voxel rows per call");
+        return fail(who, ": bad argument");
+    if (n_vox >= LIM31) return fail(who, ": < 2^31 voxel rows per call");
     SsvGeom g{};
-    if (!scale_host) return sd_fail_msg(SD_ERR_INVALID, "sd_syn_ssv_stats: null scale");
+    if (!scale_host) return fail(who, ": null scale");
     for (int a = 0; a < 3; ++a) {
-        if (!(scale_host[a] > 0.0)) return sd_fail_msg(SD_ERR_INVALID, "sd_syn_ssv_stats: bad scale");
+        if (!(scale_host[a] > 0.0)) return fail(who, ": bad scale");
         g.s[a] = scale_host[a];
     }
-    if (!temp_dev || temp_bytes < sd_syn_ssv_temp_bytes(n_vox))
-        return sd_fail_msg(SD_ERR_INVALID, "sd_syn_ssv_stats: scratch smaller than sd_syn_ssv_temp_bytes(n_vox)");
+    if (int rc = check_scratch(who, temp_dev, temp_bytes, sd_syn_ssv_temp_bytes(n_vox), "sd_syn_ssv_temp_bytes(n_vox)"); rc != SD_OK) return rc;
     SsvStatScratch w;
     layout(w, temp_dev, n_vox);
-    const char* who = "sd_syn_ssv_stats";
     const u64 n = n_vox, K = n_comp;
-    const int gv = grid_for(n, 4096);
-    hipLaunchKernelGGL(k_ssv_compkeys, dim3(gv), dim3(256), 0, s, labels_dev, n, K, w.key, counts);
+    launch_1d(k_ssv_compkeys, n, 4096, s, labels_dev, n, K, w.key, counts);
     if (int rc = sort_by_key(who, w.prim, w.key, w.skey, w.i0, w.sflat, n_vox, 32, s); rc != SD_OK) return rc;
-    hipLaunchKernelGGL(k_ssv_stat_init, dim3(grid_for(K, 4096)), dim3(256), 0, s, K, bbox_dev, w.sums, w.best, rep_flat_dev);
-    hipLaunchKernelGGL(k_ssv_stat_heads, dim3(gv), dim3(256), 0, s, w.skey, w.sflat, vox_frag_dev, n, w.headp, comp_begin_dev);
+    launch_1d(k_ssv_stat_init, K, 4096, s, K, bbox_dev, w.sums, w.best, rep_flat_dev);
+    launch_1d(k_ssv_stat_heads, n, 4096, s, w.skey, w.sflat, vox_frag_dev, n, w.headp, comp_begin_dev);
     if (int rc = scan_u32(who, w.prim, w.headp, w.pscan, n_vox, s); rc != SD_OK) return rc;
-    hipLaunchKernelGGL(k_ssv_stat_pairs, dim3(gv), dim3(256), 0, s, w.skey, w.sflat, vox_frag_dev, w.headp, w.pscan, n, pair_comp_dev,
-                       pair_frag_dev, pair_begin_dev, counts);
-    hipLaunchKernelGGL(k_ssv_stat_reduce, dim3(gv), dim3(256), 0, s, vox_dev, w.skey, w.sflat, n, bbox_dev, w.sums);
-    hipLaunchKernelGGL(k_ssv_stat_dist, dim3(gv), dim3(256), 0, s, vox_dev, w.skey, w.sflat, comp_begin_dev, w.sums, n, g, w.d2bits, w.best);
-    hipLaunchKernelGGL(k_ssv_stat_rep, dim3(gv), dim3(256), 0, s, w.skey, w.sflat, w.d2bits, w.best, n, rep_flat_dev);
-    hipLaunchKernelGGL(k_ssv_stat_keep, dim3(gv), dim3(256), 0, s, w.skey, comp_begin_dev, n, (u64)min_obj_vx, w.keep);
+    launch_1d(k_ssv_stat_pairs, n, 4096, s, w.skey, w.sflat, vox_frag_dev, w.headp, w.pscan, n, pair_comp_dev, pair_frag_dev, pair_begin_dev, counts);
+    launch_1d(k_ssv_stat_reduce, n, 4096, s, vox_dev, w.skey, w.sflat, n, bbox_dev, w.sums);
+    launch_1d(k_ssv_stat_dist, n, 4096, s, vox_dev, w.skey, w.sflat, comp_begin_dev, w.sums, n, g, w.d2bits, w.best);
+    launch_1d(k_ssv_stat_rep, n, 4096, s, w.skey, w.sflat, w.d2bits, w.best, n, rep_flat_dev);
+    launch_1d(k_ssv_stat_keep, n, 4096, s, w.skey, comp_begin_dev, n, (u64)min_obj_vx, w.keep);
     if (int rc = scan_u32(who, w.prim, w.keep, w.kscan, n_vox, s); rc != SD_OK) return rc;
-    hipLaunchKernelGGL(k_ssv_stat_gather, dim3(gv), dim3(256), 0, s, vox_dev, w.sflat, w.keep, w.kscan, n, vox_out_dev, counts);
+    launch_1d(k_ssv_stat_gather, n, 4096, s, vox_dev, w.sflat, w.keep, w.kscan, n, vox_out_dev, counts);
     return launch_status("sd_syn_ssv_stats: launch failed");
 }
 

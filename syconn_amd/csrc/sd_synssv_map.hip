@@ -41,7 +41,7 @@ __global__ __launch_bounds__(256) void k_map_pairs(const u64* __restrict__ side_
                                                    const int* __restrict__ org_rep, u64 m, MapGeom g, const u32* side_begin, u32* cnt,
                                                    u32* pair_obj, u64 pair_cap) {
     const int lane = threadIdx.x & 63;
-    const u64 wave = ((u64)blockIdx.x * 256 + threadIdx.x) >> 6, n_waves = ((u64)gridDim.x * 256) >> 6;
+    const u64 wave = grid_tid() >> 6, n_waves = grid_stride() >> 6;
     for (u64 side = wave; side < n_sides; side += n_waves) {
         const u64 c = side_cell[side];
         u32 base = 0;
@@ -70,7 +70,7 @@ __global__ __launch_bounds__(256) void k_map_pairs(const u64* __restrict__ side_
     }
 }
 __global__ __launch_bounds__(256) void k_map_side_begin(const u32* scan, u64 n, u32* side_begin, u64* counts) {
-    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256) {
+    for (u64 i = grid_tid(); i < n; i += grid_stride()) {
         if (i == 0) side_begin[0] = 0;
         side_begin[i + 1] = scan[i];
         if (i == n - 1) counts[0] = scan[i];
@@ -88,7 +88,7 @@ __device__ __forceinline__ u64 vox_row(const u64* vb, const u64* svb, u64 s, u64
 __global__ __launch_bounds__(256) void k_map_syn_corner(const u32* __restrict__ vox, const u64* __restrict__ vb, const u64* __restrict__ svb,
                                                         u64 n_syn, u64 n_vox, u64 n_sv, u32 f, u32* corner, u64* counts) {
     const int lane = threadIdx.x & 63;
-    const u64 wave = ((u64)blockIdx.x * 256 + threadIdx.x) >> 6, n_waves = ((u64)gridDim.x * 256) >> 6;
+    const u64 wave = grid_tid() >> 6, n_waves = grid_stride() >> 6;
     for (u64 s = wave; s < n_syn; s += n_waves) {
         const u64 b0 = vb[s], b1 = vb[s + 1], s0 = svb[s], s1 = svb[s + 1];
         const bool bad = b1 < b0 || b1 > n_vox || s1 < s0 || s1 > n_sv || s1 - s0 != (b1 - b0 + f - 1) / f || (s == 0 && s0 != 0) ||
@@ -110,7 +110,7 @@ __global__ __launch_bounds__(256) void k_map_syn_corner(const u32* __restrict__ 
 }
 __global__ __launch_bounds__(256) void k_map_vox_keys(const u32* __restrict__ vox, const u64* __restrict__ vb, const u64* __restrict__ svb,
                                                       const u32* __restrict__ corner, u64 n_syn, u64 n_vox, u64 n_sv, u32 f, int b, u64* key) {
-    for (u64 j = (u64)blockIdx.x * 256 + threadIdx.x; j < n_sv; j += (u64)gridDim.x * 256) {
+    for (u64 j = grid_tid(); j < n_sv; j += grid_stride()) {
         const u64 s = segment_of(svb, n_syn, j);
         const u64 row = vox_row(vb, svb, s, j, f, n_vox);
         u64 k = s;
@@ -125,7 +125,7 @@ __global__ __launch_bounds__(256) void k_map_vox_keys(const u32* __restrict__ vo
 __global__ __launch_bounds__(256) void k_map_vox_place(const u32* __restrict__ vox, const u64* __restrict__ vb, const u64* __restrict__ svb,
                                                        const u64* __restrict__ skey, const u32* __restrict__ perm, u64 n_syn, u64 n_vox,
                                                        u64 n_sv, u32 f, int b, MapGeom g, double* pts) {
-    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n_sv; i += (u64)gridDim.x * 256) {
+    for (u64 i = grid_tid(); i < n_sv; i += grid_stride()) {
         u64 s = skey[i] >> (3 * b);
         if (s >= n_syn) s = n_syn - 1;
         u64 j = perm[i];
@@ -140,7 +140,7 @@ __global__ __launch_bounds__(256) void k_map_vox_place(const u32* __restrict__ v
 __global__ __launch_bounds__(256) void k_map_pair_init(const u32* __restrict__ pair_obj, const u64* __restrict__ vtb, u64 P, u64 n_org,
                                                        u64 n_vert, u32 f, u32* pair_len, u32* pair_close, u64* pair_min, u32* icnt, u64* counts) {
     const int lane = threadIdx.x & 63;
-    for (u64 base = (u64)blockIdx.x * 256; base < P; base += (u64)gridDim.x * 256) {
+    for (u64 base = (u64)blockIdx.x * 256; base < P; base += grid_stride()) {
         const u64 p = base + threadIdx.x;
         u32 items = 0;
         if (p < P) {
@@ -317,30 +317,28 @@ int sd_synssv_map_pairs(const uint64_t* side_cell_dev, const int32_t* syn_rep_de
                         void* temp_dev, size_t temp_bytes, void* stream) {
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const char* who = "sd_synssv_map_pairs";
-    if (!counts_dev || !side_begin_dev) return sd_fail_msg(SD_ERR_INVALID, "sd_synssv_map_pairs: null counts or side_begin");
+    if (!counts_dev || !side_begin_dev) return fail(who, ": null counts or side_begin");
     u64* counts = reinterpret_cast<u64*>(counts_dev);
     if (n_sides >= LIM31 || (n_sides & 1) || n_org >= LIM31 || pair_cap >= LIM31)
-        return sd_fail_msg(SD_ERR_INVALID, "sd_synssv_map_pairs: an even number of sides, sides, organelles and pairs < 2^31 per call");
+        return fail(who, ": an even number of sides, sides, organelles and pairs < 2^31 per call");
     MapGeom g;
-    if (!map_geom(scale_host, max_rep_dist_nm, g)) return sd_fail_msg(SD_ERR_INVALID, "sd_synssv_map_pairs: bad scale or distance");
+    if (!map_geom(scale_host, max_rep_dist_nm, g)) return fail(who, ": bad scale or distance");
     if (!pair_obj_dev) {
-        if (hipMemsetAsync(counts, 0, 8 * sizeof(u64), s) != hipSuccess) return sd_fail_msg(SD_ERR_HIP, "memset failed");
+        if (int rc = zero_counts(counts, 8, s); rc != SD_OK) return rc;
         if (hipMemsetAsync(side_begin_dev, 0, sizeof(u32), s) != hipSuccess) return sd_fail_msg(SD_ERR_HIP, "memset failed");
     }
     if (n_sides == 0) return SD_OK;
     if (!side_cell_dev || !syn_rep_dev || (n_org && (!org_cell_dev || !org_row_dev || !org_rep_dev)))
-        return sd_fail_msg(SD_ERR_INVALID, "sd_synssv_map_pairs: bad argument");
-    if (!temp_dev || temp_bytes < sd_synssv_map_pairs_temp_bytes(n_sides))
-        return sd_fail_msg(SD_ERR_INVALID, "sd_synssv_map_pairs: scratch smaller than sd_synssv_map_pairs_temp_bytes(n_sides)");
+        return fail(who, ": bad argument");
+    if (int rc = check_scratch(who, temp_dev, temp_bytes, sd_synssv_map_pairs_temp_bytes(n_sides), "sd_synssv_map_pairs_temp_bytes(n_sides)"); rc != SD_OK) return rc;
     MapPairScratch w;
     layout(w, temp_dev, n_sides);
     const u64 n = n_sides;
-    hipLaunchKernelGGL(k_map_pairs, dim3(grid_for(64 * n, 4096)), dim3(256), 0, s, reinterpret_cast<const u64*>(side_cell_dev), syn_rep_dev, n,
-                       reinterpret_cast<const u64*>(org_cell_dev), org_row_dev, org_rep_dev, (u64)n_org, g, side_begin_dev, w.cnt, pair_obj_dev,
-                       (u64)pair_cap);
+    launch_1d(k_map_pairs, 64 * n, 4096, s, reinterpret_cast<const u64*>(side_cell_dev), syn_rep_dev, n, reinterpret_cast<const u64*>(org_cell_dev),
+              org_row_dev, org_rep_dev, (u64)n_org, g, side_begin_dev, w.cnt, pair_obj_dev, (u64)pair_cap);
     if (!pair_obj_dev) {
         if (int rc = scan_u32(who, w.prim, w.cnt, w.scan, n_sides, s); rc != SD_OK) return rc;
-        hipLaunchKernelGGL(k_map_side_begin, dim3(grid_for(n, 4096)), dim3(256), 0, s, w.scan, n, side_begin_dev, counts);
+        launch_1d(k_map_side_begin, n, 4096, s, w.scan, n, side_begin_dev, counts);
     }
     return launch_status("sd_synssv_map_pairs: launch failed");
 }
@@ -358,19 +356,19 @@ int sd_synssv_map_query(const uint32_t* vox_dev, const uint64_t* vox_begin_dev, 
                         void* stream) {
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const char* who = "sd_synssv_map_query";
-    if (!counts_dev) return sd_fail_msg(SD_ERR_INVALID, "sd_synssv_map_query: null counts");
+    if (!counts_dev) return fail(who, ": null counts");
     u64* counts = reinterpret_cast<u64*>(counts_dev);
     if (n_syn >= LIM31 / 2 || n_sampled_vox >= LIM31 || n_pairs >= LIM31 || n_org >= LIM31 || n_pairs > scratch_pairs || sample_fact < 1)
-        return sd_fail_msg(SD_ERR_INVALID, "sd_synssv_map_query: synapses < 2^30, sampled voxels, organelles and pairs < 2^31 per call, "
+        return fail(who, ": synapses < 2^30, sampled voxels, organelles and pairs < 2^31 per call, "
                                            "sample_fact >= 1");
     MapGeom g;
-    if (!map_geom(scale_host, max_vert_dist_nm, g)) return sd_fail_msg(SD_ERR_INVALID, "sd_synssv_map_query: bad scale or distance");
-    if (hipMemsetAsync(counts, 0, 8 * sizeof(u64), s) != hipSuccess) return sd_fail_msg(SD_ERR_HIP, "memset failed");
+    if (!map_geom(scale_host, max_vert_dist_nm, g)) return fail(who, ": bad scale or distance");
+    if (int rc = zero_counts(counts, 8, s); rc != SD_OK) return rc;
     if (n_syn == 0 || !(stages & 3)) return SD_OK;
     if (!vox_begin_dev || !sampled_begin_dev || (n_sampled_vox && (!vox_dev || !n_vox)))
-        return sd_fail_msg(SD_ERR_INVALID, "sd_synssv_map_query: bad argument");
-    if (!temp_dev || temp_bytes < sd_synssv_map_query_temp_bytes(n_syn, n_sampled_vox, scratch_pairs))
-        return sd_fail_msg(SD_ERR_INVALID, "sd_synssv_map_query: scratch smaller than sd_synssv_map_query_temp_bytes(...)");
+        return fail(who, ": bad argument");
+    if (int rc = check_scratch(who, temp_dev, temp_bytes, sd_synssv_map_query_temp_bytes(n_syn, n_sampled_vox, scratch_pairs), "sd_synssv_map_query_temp_bytes(...)"); rc != SD_OK)
+        return rc;
     MapQueryScratch w;
     layout(w, temp_dev, n_syn, n_sampled_vox ? n_sampled_vox : 1, scratch_pairs ? scratch_pairs : 1);
     const u64 S = n_syn, V = n_sampled_vox, P = n_pairs;
@@ -379,24 +377,21 @@ int sd_synssv_map_query(const uint32_t* vox_dev, const uint64_t* vox_begin_dev, 
     const u64* svb = reinterpret_cast<const u64*>(sampled_begin_dev);
     if (stages & 1) {
         const int sbits = bits_for(S), b = std::min(10, (64 - sbits) / 3);
-        hipLaunchKernelGGL(k_map_syn_corner, dim3(grid_for(64 * S, 4096)), dim3(256), 0, s, vox_dev, vb, svb, S, (u64)n_vox, V, f, w.corner,
-                           counts);
+        launch_1d(k_map_syn_corner, 64 * S, 4096, s, vox_dev, vb, svb, S, (u64)n_vox, V, f, w.corner, counts);
         if (V) {
-            const int gv = grid_for(V, 4096);
-            hipLaunchKernelGGL(k_map_vox_keys, dim3(gv), dim3(256), 0, s, vox_dev, vb, svb, w.corner, S, (u64)n_vox, V, f, b, w.key);
+            launch_1d(k_map_vox_keys, V, 4096, s, vox_dev, vb, svb, w.corner, S, (u64)n_vox, V, f, b, w.key);
             if (int rc = sort_by_key(who, w.prim, w.key, w.skey, w.i0, w.perm, n_sampled_vox, sbits + 3 * b, s); rc != SD_OK) return rc;
-            hipLaunchKernelGGL(k_map_vox_place, dim3(gv), dim3(256), 0, s, vox_dev, vb, svb, w.skey, w.perm, S, (u64)n_vox, V, f, b, g, w.pts);
+            launch_1d(k_map_vox_place, V, 4096, s, vox_dev, vb, svb, w.skey, w.perm, S, (u64)n_vox, V, f, b, g, w.pts);
         }
-        hipLaunchKernelGGL(k_tile_boxes<true>, dim3(grid_for(64 * S, 4096)), dim3(256), 0, s, w.pts, svb, S, V, (u64)w.n_slots, w.tbox, w.sbox);
+        launch_1d(k_tile_boxes<true>, 64 * S, 4096, s, w.pts, svb, S, V, (u64)w.n_slots, w.tbox, w.sbox);
     }
     if ((stages & 2) && P) {
         if (!vert_begin_dev || !side_begin_dev || !pair_obj_dev || !pair_close_dev || !pair_len_dev || !pair_min_d2_dev || !n_org ||
             (n_vert && !vert_dev))
-            return sd_fail_msg(SD_ERR_INVALID, "sd_synssv_map_query: bad argument");
+            return fail(who, ": bad argument");
         const u64* vtb = reinterpret_cast<const u64*>(vert_begin_dev);
         u64* pmin = reinterpret_cast<u64*>(pair_min_d2_dev);
-        hipLaunchKernelGGL(k_map_pair_init, dim3(grid_for(P, 4096)), dim3(256), 0, s, pair_obj_dev, vtb, P, (u64)n_org, (u64)n_vert, f,
-                           pair_len_dev, pair_close_dev, pmin, w.icnt, counts);
+        launch_1d(k_map_pair_init, P, 4096, s, pair_obj_dev, vtb, P, (u64)n_org, (u64)n_vert, f, pair_len_dev, pair_close_dev, pmin, w.icnt, counts);
         if (int rc = scan_u32(who, w.prim, w.icnt, w.iscan, n_pairs, s); rc != SD_OK) return rc;
         const u64 want = n_items_hint ? n_items_hint : MAP_QUERY_GRID;
         const int grid = (int)std::min<u64>(want, MAP_QUERY_GRID);
