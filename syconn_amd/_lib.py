@@ -1,7 +1,7 @@
 """ctypes binding of ``libsyconn_dense_hip.so`` (C ABI: ``include/syconn_dense.h``).
 
-There is deliberately no fallback: if the shared library is missing (not built) loading raises, and if no
-MI355X is visible ``sd_init`` returns ``SD_ERR_NODEVICE`` which is raised as ``RuntimeError``.
+There is deliberately no fallback: if the shared library is missing (not built) loading raises, and if no MI355X is visible ``sd_init``
+returns ``SD_ERR_NODEVICE`` which is raised as ``RuntimeError``.  Device entries outside the prediction path are called through ``_dev.call``.
 """
 import ctypes as C
 import os

@@ -13,9 +13,10 @@ import ctypes as C
 import numpy as np
 import torch
 
+from .. import _dev as D
 from .. import _lib as L
 from ..proc.records import OBJECT_FIELDS, Records, segment_offsets
-from .find_object_properties import _cs_device, segstats
+from .find_object_properties import segstats
 
 # summed box volume (bytes per workspace plane) of one batch of sites; a single larger box gets a batch of its own
 WS_BUDGET = 1 << 28
@@ -25,7 +26,7 @@ def _u64_volume(arr, device) -> torch.Tensor:
     if isinstance(arr, np.ndarray):
         if arr.dtype != np.uint64:
             raise TypeError(f'contact volumes must be uint64, got {arr.dtype}')
-        t = torch.from_numpy(np.ascontiguousarray(arr).view(np.int64)).to(device)
+        t = D.up(arr, device)
     else:
         if arr.dtype not in (torch.uint64, torch.int64):
             raise TypeError(f'contact volumes must be 64-bit integer tensors, got {arr.dtype}')
@@ -77,24 +78,20 @@ def plan_sites(c0: torch.Tensor, n_closings: int, device, ws_budget: int = WS_BU
         tab[:, 1:4] = lo[start:end]
         tab[:, 4:7] = ext[start:end]
         tab[:, 7] = np.concatenate([[0], np.cumsum(vol[start:end])[:-1]])
-        batches.append((torch.from_numpy(tab).to(device), end - start, int(vol[start:end].sum())))
+        batches.append((D.up(tab, device), end - start, int(vol[start:end].sum())))
         start = end
     return SitePlan((X, Y, Z), ids, batches, 2 * max(tot for _, _, tot in batches))
 
 
 def run_sites(c0: torch.Tensor, plan: SitePlan, n_closings: int, cs_dilation: int, out: torch.Tensor, ws: torch.Tensor):
     """The sd_cs_close_dilate launches of a plan (asynchronous on the current stream; `ws` >= plan.ws_bytes bytes)."""
-    lib = L.load()
     X, Y, Z = plan.shape
-    stream = torch.cuda.current_stream(c0.device).cuda_stream
     if not plan.batches:
-        L.check(lib.sd_cs_close_dilate(c0.data_ptr(), X, Y, Z, None, 0, 0, n_closings, cs_dilation,
-                                       L.SD_CS_FIRST | L.SD_CS_LAST, out.data_ptr(), None, 0, stream), 'sd_cs_close_dilate')
+        D.call('sd_cs_close_dilate', c0.device, c0, X, Y, Z, None, 0, 0, n_closings, cs_dilation, L.SD_CS_FIRST | L.SD_CS_LAST, out, None, 0)
         return out
     for b, (tab_d, n_obj, tot) in enumerate(plan.batches):
         flags = (L.SD_CS_FIRST if b == 0 else 0) | (L.SD_CS_LAST if b == len(plan.batches) - 1 else 0)
-        L.check(lib.sd_cs_close_dilate(c0.data_ptr(), X, Y, Z, tab_d.data_ptr(), n_obj, tot, n_closings, cs_dilation, flags,
-                                       out.data_ptr(), ws.data_ptr(), ws.numel(), stream), 'sd_cs_close_dilate')
+        D.call('sd_cs_close_dilate', c0.device, c0, X, Y, Z, tab_d, n_obj, tot, n_closings, cs_dilation, flags, out, ws, ws.numel())
     return out
 
 
@@ -107,11 +104,11 @@ def close_and_dilate_cs(contacts, n_closings: int, cs_dilation: int, return_devi
     n_closings, cs_dilation = int(n_closings), int(cs_dilation)
     if n_closings < 0 or cs_dilation < 0:
         raise ValueError('n_closings and cs_dilation must be >= 0')
-    dev = _cs_device(device)
+    dev = D.device(device)
     c0 = _u64_volume(contacts, dev)
     plan = plan_sites(c0, n_closings, dev, ws_budget)
     out = torch.empty_like(c0)
-    ws = torch.empty(max(plan.ws_bytes, 1), dtype=torch.uint8, device=dev)
+    ws = D.empty(plan.ws_bytes, D.u8, dev)
     run_sites(c0, plan, n_closings, cs_dilation, out, ws)
     return out if return_device else out.cpu().numpy().view(np.uint64)
 
@@ -122,8 +119,7 @@ def binary_morphology(mask, morph_ops, structure, threshold: float = 0.0, return
     0/1 mask ``mask > threshold`` of a uint8 (x, y, z) volume: runs of equal operations are merged, each run acts inside the
     bounding box of the current foreground (zero pad for closing / dilation), an empty mask stays empty.  -> uint8 0/1 volume."""
     from .object_extraction_steps import _MOPS, _count_subsequent_mops
-    lib = L.load()
-    dev = _cs_device(device)
+    dev = D.device(device)
     t = torch.from_numpy(np.ascontiguousarray(mask)) if isinstance(mask, np.ndarray) else mask
     if t.dtype == torch.bool:
         t = t.to(torch.uint8)
@@ -138,24 +134,20 @@ def binary_morphology(mask, morph_ops, structure, threshold: float = 0.0, return
     st = np.ascontiguousarray(np.asarray(structure)).astype(np.uint8)
     X, Y, Z = (int(s) for s in t.shape)
     pmax = max([c for n, c in zip(names, counts) if n in ('binary_closing', 'binary_dilation')], default=0)
-    ws_bytes = lib.sd_objseg_workspace_bytes(X, Y, Z, pmax)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    ws = D.scratch('sd_objseg_workspace_bytes', dev, X, Y, Z, pmax)
     out = torch.empty((X, Y, Z), dtype=torch.uint8, device=dev)
     n = len(names)
     ops_a = (C.c_int32 * max(n, 1))(*[_MOPS[m] for m in names])
     it_a = (C.c_int32 * max(n, 1))(*counts)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    L.check(lib.sd_binary_morphology(t.data_ptr(), X, Y, Z, float(threshold), ops_a, it_a, n, st.ctypes.data_as(C.c_void_p),
-                                     *[int(s) for s in st.shape], out.data_ptr(), ws.data_ptr(), ws_bytes, stream),
-            'sd_binary_morphology')
+    D.call('sd_binary_morphology', dev, t, X, Y, Z, float(threshold), ops_a, it_a, n, st.ctypes.data_as(C.c_void_p),
+           *[int(s) for s in st.shape], out, ws, ws.numel())
     return out if return_device else out.cpu().numpy()
 
 
 def syntype_masks(vol, label_a=None, label_b=None, device=None):
     """The syn-type masks of the worker (:411-430) from one loaded (x, y, z) volume, as uint8 device tensors: uint8 raw data ->
     ``vol >= 123``; uint64 labels -> ``(vol == label_a, vol == label_b)`` (the second only when `label_b` is given)."""
-    lib = L.load()
-    dev = _cs_device(device)
+    dev = D.device(device)
     t = torch.from_numpy(np.ascontiguousarray(vol)) if isinstance(vol, np.ndarray) else vol
     if t.dtype == torch.uint8:
         dtype = L.SD_U8
@@ -168,19 +160,14 @@ def syntype_masks(vol, label_a=None, label_b=None, device=None):
     t = t.to(dev).contiguous()
     a = torch.empty(t.shape, dtype=torch.uint8, device=dev)
     b = torch.empty(t.shape, dtype=torch.uint8, device=dev) if (dtype == L.SD_U64 and label_b is not None) else None
-    stream = torch.cuda.current_stream(dev).cuda_stream
     lab = lambda v: int(np.uint64(0 if v is None else int(v) % 2 ** 64))
-    L.check(lib.sd_syntype_masks(t.data_ptr(), dtype, t.numel(), lab(label_a), lab(label_b), a.data_ptr(),
-                                 b.data_ptr() if b is not None else None, stream), 'sd_syntype_masks')
+    D.call('sd_syntype_masks', dev, t, dtype, t.numel(), lab(label_a), lab(label_b), a, b)
     return (a, b) if b is not None else a
 
 
 def _upload_xyz(arr_zyx: np.ndarray, dev) -> torch.Tensor:
     """A (z, y, x) array as KnossosDataset loads it -> contiguous (x, y, z) device tensor (the reference's ``.swapaxes(0, 2)``)."""
-    a = np.ascontiguousarray(arr_zyx)
-    if a.dtype == np.uint64:
-        a = a.view(np.int64)
-    return torch.from_numpy(a).to(dev).permute(2, 1, 0).contiguous()
+    return D.up(arr_zyx, dev).permute(2, 1, 0).contiguous()
 
 
 def _check_worker_config(cfg):
@@ -226,7 +213,7 @@ class _ChunkExtractor:
         self.cs_dilation = int(cfg['cell_objects']['cs_dilation'])
         self.stencil_offset = self.cs_filtersize // 2
         self.sj_ops = list(morph_ops['sj']) if 'sj' in morph_ops else []
-        self.dev = _cs_device(device)
+        self.dev = D.device(device)
         self.scan = CsSyntypeScan(self.dev)
 
     def run(self, chunk):
@@ -245,7 +232,7 @@ class _ChunkExtractor:
         del seg
         plan = plan_sites(c0, overlap, dev)
         contacts = torch.empty_like(c0)
-        ws = torch.empty(max(plan.ws_bytes, 1), dtype=torch.uint8, device=dev)
+        ws = D.empty(plan.ws_bytes, D.u8, dev)
         run_sites(c0, plan, overlap, self.cs_dilation, contacts, ws)
         del c0, ws
         # 4. sj mask (:392-408) and syn-type masks (:411-433)
@@ -258,7 +245,7 @@ class _ChunkExtractor:
             if self.sj_ops and np.any(sj_h > 1):
                 raise ValueError('transf_func_sj_seg returned values other than 0 and 1 while sj morphology is configured: the '
                                  'reference would apply it per label; this build takes binary sj masks only (DESIGN.md section 7)')
-            sj_d = torch.from_numpy(np.ascontiguousarray(sj_h)).to(dev)
+            sj_d = D.up(sj_h, dev)
             if self.sj_ops:
                 sj_d = binary_morphology(sj_d, self.sj_ops, self.struct, threshold=0, return_device=True, device=dev)
         if self.syntype:
@@ -399,11 +386,10 @@ class ContactSiteMerger:
     arrays are sized from them and ``add_chunk`` neither waits for the device nor copies anything to the host."""
 
     def __init__(self, min_obj_vx: dict, device, capacity: int = 1 << 14, vox_capacity: int = 1 << 18):
-        self.lib = L.load()
         self.device = torch.device(device)
         self.min_cs, self.min_syn = int(min_obj_vx['cs']), int(min_obj_vx['syn'])
         syn = OBJECT_FIELDS + [('asym', 'int64', 1), ('sym', 'int64', 1), ('vpos', 'int64', 1)]
-        self.cursors = torch.zeros(3, dtype=torch.int64, device=self.device)
+        self.cursors = D.counters(self.device, 3)
         self.cs = Records(self.device, OBJECT_FIELDS, capacity, self.cursors[0:1])
         self.syn = Records(self.device, syn, capacity, self.cursors[1:2])
         self.vox = Records(self.device, [('rows', 'int32', 3)], vox_capacity, self.cursors[2:3])
@@ -419,52 +405,44 @@ class ContactSiteMerger:
         self.syn.room_for(self.n_cs, n)
         self.vox.room_for(self.n_vox, n_vox)
         ox, oy, oz = (int(v) for v in origin)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        L.check(self.lib.sd_cs_merge_append(result.rec.data_ptr() if n else None, n, result.voxels.data_ptr() if n_vox else None, n_vox,
-                                            ox, oy, oz, *self.cs.ptrs(), self.cs.capacity, *self.syn.ptrs(), self.syn.capacity,
-                                            *self.vox.ptrs(), self.vox.capacity, self.cursors.data_ptr(), stream), 'sd_cs_merge_append')
+        D.call('sd_cs_merge_append', self.device, result.rec if n else None, n, result.voxels if n_vox else None, n_vox, ox, oy, oz,
+               *self.cs.ptrs(), self.cs.capacity, *self.syn.ptrs(), self.syn.capacity, *self.vox.ptrs(), self.vox.capacity, self.cursors)
         self.n_cs += n
         self.n_vox += n_vox
         self.n_chunks += 1
 
     def finish(self):
         """-> (``CsTable``, ``SynTable``).  One merge of each kind on the device, then the download of the compacted tables."""
-        lib, dev = self.lib, self.device
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        n_cs, n_syn, n_vox = (int(v) for v in self.cursors.cpu().numpy())
+        dev = self.device
+        n_cs, n_syn, n_vox = (int(v) for v in D.down(self.cursors))
         if n_cs > self.cs.capacity or n_syn > self.syn.capacity or n_vox > self.vox.capacity:
             raise RuntimeError(f'sd_cs_merge_append: record arrays overran ({n_cs}/{self.cs.capacity} cs, {n_syn}/{self.syn.capacity} '
                                f'syn, {n_vox}/{self.vox.capacity} voxel rows)')
-        tmp = torch.empty(lib.sd_cs_merge_temp_bytes(max(n_cs, n_syn, 1)), dtype=torch.uint8, device=dev)
-        new = lambda n, w, dt: torch.empty((max(n, 1), w) if w > 1 else (max(n, 1),), dtype=dt, device=dev)
+        tmp = D.scratch('sd_cs_merge_temp_bytes', dev, max(n_cs, n_syn, 1))
 
         def common(n):
-            return [new(n, 1, torch.int64), new(n, 1, torch.int64), new(n, 3, torch.int32), new(n, 6, torch.int32),
-                    new(n, 1, torch.int32), new(n, 6, torch.int32)]
-        c_out, c_cnt = common(n_cs), torch.zeros(4, dtype=torch.int64, device=dev)
+            return [D.empty(n, D.i64, dev), D.empty(n, D.i64, dev), D.empty((n, 3), D.i32, dev), D.empty((n, 6), D.i32, dev),
+                    D.empty(n, D.i32, dev), D.empty((n, 6), D.i32, dev)]
+        c_out, c_cnt = common(n_cs), D.counters(dev, 4)
         a = self.cs.arrays
-        L.check(lib.sd_cs_merge_objects(a['ids'].data_ptr(), a['sizes'].data_ptr(), a['rc'].data_ptr(), a['bb'].data_ptr(), n_cs,
-                                        self.min_cs, *[t.data_ptr() for t in c_out], c_cnt.data_ptr(), tmp.data_ptr(), tmp.numel(),
-                                        stream), 'sd_cs_merge_objects')
-        u_cs, b_cs, _, self.n_cs_all = (int(v) for v in c_cnt.cpu().numpy())
-        s_out, s_cnt = common(n_syn), torch.zeros(4, dtype=torch.int64, device=dev)
-        s_more = [new(n_syn, 1, torch.int64), new(n_syn, 1, torch.int64), new(n_syn, 1, torch.int64), new(n_syn, 1, torch.int32),
-                  new(n_vox, 3, torch.int32)]
+        D.call('sd_cs_merge_objects', dev, a['ids'], a['sizes'], a['rc'], a['bb'], n_cs, self.min_cs, *c_out, c_cnt, tmp, tmp.numel())
+        u_cs, b_cs, _, self.n_cs_all = (int(v) for v in D.down(c_cnt))
+        s_out, s_cnt = common(n_syn), D.counters(dev, 4)
+        s_more = [D.empty(n_syn, D.i64, dev), D.empty(n_syn, D.i64, dev), D.empty(n_syn, D.i64, dev), D.empty(n_syn, D.i32, dev),
+                  D.empty((n_vox, 3), D.i32, dev)]
         a = self.syn.arrays
-        L.check(lib.sd_cs_merge_synapses(*[a[k].data_ptr() for k in ('ids', 'sizes', 'rc', 'bb', 'asym', 'sym', 'vpos')], n_syn,
-                                         self.vox.arrays['rows'].data_ptr(), n_vox, c_out[0].data_ptr(), c_out[1].data_ptr(), u_cs,
-                                         self.min_syn, *[t.data_ptr() for t in s_out + s_more], s_cnt.data_ptr(), tmp.data_ptr(),
-                                         tmp.numel(), stream), 'sd_cs_merge_synapses')
-        u_syn, b_syn, v_syn, self.n_syn_all = (int(v) for v in s_cnt.cpu().numpy())
+        D.call('sd_cs_merge_synapses', dev, *[a[k] for k in ('ids', 'sizes', 'rc', 'bb', 'asym', 'sym', 'vpos')], n_syn, self.vox.arrays['rows'],
+               n_vox, c_out[0], c_out[1], u_cs, self.min_syn, *s_out, *s_more, s_cnt, tmp, tmp.numel())
+        u_syn, b_syn, v_syn, self.n_syn_all = (int(v) for v in D.down(s_cnt))
 
         def table(out, u, b):
             ids, tot, rc, ubox, beg, boxes = out
-            return [ids[:u].cpu().numpy().view(np.uint64), tot[:u].cpu().numpy(), rc[:u].cpu().numpy(),
-                    ubox[:u].cpu().numpy().reshape(u, 2, 3), boxes[:b].cpu().numpy().reshape(b, 2, 3), segment_offsets(beg, u, b)]
+            return [D.down(ids, u, np.uint64), D.down(tot, u), D.down(rc, u), D.down(ubox, u).reshape(u, 2, 3),
+                    D.down(boxes, b).reshape(b, 2, 3), segment_offsets(beg, u, b)]
         cs_t = CsTable(*table(c_out, u_cs, b_cs))
         asym, sym, cs_size, vbeg, vout = s_more
-        syn_t = SynTable(*table(s_out, u_syn, b_syn), asym[:u_syn].cpu().numpy(), sym[:u_syn].cpu().numpy(), cs_size[:u_syn].cpu().numpy(),
-                         vout[:v_syn].cpu().numpy().view(np.uint32), segment_offsets(vbeg, u_syn, v_syn))
+        syn_t = SynTable(*table(s_out, u_syn, b_syn), D.down(asym, u_syn), D.down(sym, u_syn), D.down(cs_size, u_syn),
+                         D.down(vout, v_syn, np.uint32), segment_offsets(vbeg, u_syn, v_syn))
         return cs_t, syn_t
 
 

@@ -12,8 +12,6 @@ There is no CPU fallback for the device parts.
 ``map_objects_from_synssv_partners`` (:811-1093), the call after it, maps the mitochondria and vesicle clouds of the two partner cells
 to every ``syn_ssv`` row (``csrc/sd_synssv_map.hip``) and ``synssv_o_features`` (:1404-1431) lays out the classifier's feature rows.
 """
-import ctypes as C
-
 import numpy as np
 
 from .. import _lib as L
@@ -227,12 +225,9 @@ class _Agglomerator:
     the fragment number of every voxel (ascending), `frag_group` (F) the group of every fragment.  The voxel rows are uploaded once."""
 
     def __init__(self, vox, vox_frag, frag_group, n_group, scaling, cs_gap_nm, device=None):
-        import torch
-        from .find_object_properties import _cs_device
+        from .. import _dev as D
         self.gap, self.scale = _check_gap(cs_gap_nm, scaling)
-        self.lib = L.load()
-        self.dev = _cs_device(device)
-        self.torch = torch
+        self.lib, self.dev = L.load(), D.device(device)
         vox = np.ascontiguousarray(vox, dtype=np.int32).reshape(-1, 3)
         self.n, self.n_frag, self.n_group = len(vox), len(frag_group), int(n_group)
         self.cell = choose_cell(self.scale, self.gap)
@@ -252,24 +247,22 @@ class _Agglomerator:
         self.bits = np.array([int(v - 1).bit_length() for v in n_cells.tolist()], np.int32)
         if int(self.bits.sum()) + int(self.n_group - 1).bit_length() > 63:
             raise ValueError(f'combine_and_split_syn: {self.n_group} groups spanning up to {n_cells.tolist()} cells do not fit a 63-bit key')
-        up = lambda a: torch.from_numpy(a).to(self.dev)
-        self.vox_d, self.frag_d, self.fgroup_d, self.origin_d = up(vox), up(vox_frag.view(np.int32)), up(frag_group.view(np.int32)), up(lo)
-        self.tmp = torch.empty(self.lib.sd_syn_ssv_temp_bytes(self.n), dtype=torch.uint8, device=self.dev)
-        self.labels_d = torch.empty(self.n, dtype=torch.int32, device=self.dev)
-        self.counts_d = torch.zeros(8, dtype=torch.int64, device=self.dev)
-        self._scale_c = (C.c_double * 3)(*self.scale.tolist())
-        self._cell_c = (C.c_int32 * 3)(*self.cell.tolist())
-        self._bits_c = (C.c_int32 * 3)(*self.bits.tolist())
+        self.vox_d, self.frag_d, self.fgroup_d, self.origin_d = (D.up(a, self.dev) for a in (vox, vox_frag, frag_group, lo))
+        self.tmp = D.scratch('sd_syn_ssv_temp_bytes', self.dev, self.n)
+        self.labels_d = D.empty(self.n, D.i32, self.dev)
+        self.counts_d = D.counters(self.dev)
+        self._scale_c, self._cell_c, self._bits_c = D.f64x3(self.scale), D.i32x3(self.cell), D.i32x3(self.bits)
 
     def components(self, stages: int = 7):
         """Launch the stages (bit 0 cells, bit 1 link, bit 2 number) on the current stream; asynchronous."""
         if not self.n:
             return
-        stream = self.torch.cuda.current_stream(self.dev).cuda_stream
+        import torch
+        # written out, not through _dev.call: the first stage's device span starts with this call's host time (profiles/hostcall_ab_probe.json)
         L.check(self.lib.sd_syn_ssv_components(self.vox_d.data_ptr(), self.frag_d.data_ptr(), self.fgroup_d.data_ptr(), self.origin_d.data_ptr(),
                                                self.n, self.n_frag, self.n_group, self._scale_c, self.gap, self._cell_c, self._bits_c,
                                                int(stages), self.labels_d.data_ptr(), self.counts_d.data_ptr(), self.tmp.data_ptr(),
-                                               self.tmp.numel(), stream), 'sd_syn_ssv_components')
+                                               self.tmp.numel(), torch.cuda.current_stream(self.dev).cuda_stream), 'sd_syn_ssv_components')
 
     def read_counts(self):
         """-> counts of ``sd_syn_ssv_components`` on the host (waits for the device)."""
@@ -285,30 +278,27 @@ class _Agglomerator:
     def stats(self, min_obj_vx: int):
         """Per-component statistics of all `n_comp` components and the voxel rows of the kept ones (waits for the device).
         -> dict of numpy arrays for ``build_syn_ssv_table``."""
-        torch, dev, n = self.torch, self.dev, self.n
+        from .. import _dev as D
+        dev, n = self.dev, self.n
         K = int(self.counts[0])
         if not n:
             z = np.zeros(0, np.int64)
             return dict(comp_sizes=z, comp_bbox=np.zeros((0, 2, 3), np.int32), comp_rep_flat=z, pair_comp=z, pair_frag=z, pair_cnt=z,
                         voxels=np.zeros((0, 3), np.uint32))
-        new = lambda m, dt: torch.empty(m, dtype=dt, device=dev)
-        i32 = torch.int32
-        comp_begin, bbox, rep = new(K + 1, i32), new((K, 6), i32), new(K, i32)
-        p_comp, p_frag, p_begin, vout = new(n + 1, i32), new(n + 1, i32), new(n + 1, i32), new((n, 3), i32)
-        cnt = torch.zeros(4, dtype=torch.int64, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        L.check(self.lib.sd_syn_ssv_stats(self.vox_d.data_ptr(), self.frag_d.data_ptr(), self.labels_d.data_ptr(), n, K, self._scale_c,
-                                          int(min_obj_vx), comp_begin.data_ptr(), bbox.data_ptr(), rep.data_ptr(), p_comp.data_ptr(),
-                                          p_frag.data_ptr(), p_begin.data_ptr(), vout.data_ptr(), cnt.data_ptr(), self.tmp.data_ptr(),
-                                          self.tmp.numel(), stream), 'sd_syn_ssv_stats')
-        P, n_kept, _, bad = (int(v) for v in cnt.cpu().numpy())
+        new = lambda m: D.empty(m, D.i32, dev)
+        comp_begin, bbox, rep = new(K + 1), new((K, 6)), new(K)
+        p_comp, p_frag, p_begin, vout = new(n + 1), new(n + 1), new(n + 1), new((n, 3))
+        cnt = D.counters(dev, 4)
+        D.call('sd_syn_ssv_stats', dev, self.vox_d, self.frag_d, self.labels_d, n, K, self._scale_c, int(min_obj_vx), comp_begin, bbox, rep,
+               p_comp, p_frag, p_begin, vout, cnt, self.tmp, self.tmp.numel())
+        P, n_kept, _, bad = (int(v) for v in D.down(cnt))
         if bad:
             raise RuntimeError('sd_syn_ssv_stats: a component label was out of range')
-        u = lambda t: t.cpu().numpy().view(np.uint32).astype(np.int64)
+        u = lambda t, m=None: D.down(t, m, np.uint32).astype(np.int64)
         begin = u(comp_begin)
-        pb = u(p_begin[:P + 1])
-        return dict(comp_sizes=np.diff(begin), comp_bbox=bbox.cpu().numpy().reshape(K, 2, 3), comp_rep_flat=u(rep), pair_comp=u(p_comp[:P]),
-                    pair_frag=u(p_frag[:P]), pair_cnt=np.diff(pb), voxels=vout[:n_kept].cpu().numpy().view(np.uint32))
+        pb = u(p_begin, P + 1)
+        return dict(comp_sizes=np.diff(begin), comp_bbox=D.down(bbox).reshape(K, 2, 3), comp_rep_flat=u(rep), pair_comp=u(p_comp, P),
+                    pair_frag=u(p_frag, P), pair_cnt=np.diff(pb), voxels=D.down(vout, n_kept, np.uint32))
 
 
 def _flatten(voxel_lists):
@@ -537,9 +527,8 @@ class _ObjectMapper:
     and tiled form (``prepare``) serves every organelle type."""
 
     def __init__(self, syn_ssv, scale, sample_fact, device=None):
-        import torch
-        from .find_object_properties import _cs_device
-        self.lib, self.dev, self.torch = L.load(), _cs_device(device), torch
+        from .. import _dev as D
+        self.lib, self.dev = L.load(), D.device(device)
         self.scale, self.f = np.asarray(scale, np.float64), int(sample_fact)
         self.n = n = len(syn_ssv)
         partners = np.ascontiguousarray(syn_ssv.neuron_partners, dtype=np.uint64).reshape(n, 2)
@@ -551,20 +540,17 @@ class _ObjectMapper:
         self.n_vox, self.n_sv = len(vox), int(svb[-1])
         if 2 * n >= 2 ** 31 or self.n_sv >= 2 ** 31:
             raise ValueError('map_objects_from_synssv_partners: fewer than 2^30 synapses and 2^31 sampled voxels per call')
-        up = lambda a: torch.from_numpy(a).to(self.dev)
-        self.cell_d, self.rep_d = up(partners.view(np.int64).reshape(-1)), up(rep)
-        self.vox_d, self.vb_d, self.svb_d = up(vox.view(np.int32)), up(vb), up(svb)
-        self._scale_c = (C.c_double * 3)(*self.scale.tolist())
-        self.pair_tmp = torch.empty(self.lib.sd_synssv_map_pairs_temp_bytes(2 * n), dtype=torch.uint8, device=self.dev)
+        self.cell_d, self.rep_d = D.up(partners.reshape(-1), self.dev), D.up(rep, self.dev)
+        self.vox_d, self.vb_d, self.svb_d = D.up(vox, self.dev), D.up(vb, self.dev), D.up(svb, self.dev)
+        self._scale_c = D.f64x3(self.scale)
+        self.pair_tmp = D.scratch('sd_synssv_map_pairs_temp_bytes', self.dev, 2 * n)
         self.tmp, self.tmp_pairs, self.prepared = None, 0, False
-        self.vox_counts_d = torch.zeros(8, dtype=torch.int64, device=self.dev)
-
-    def _stream(self):
-        return self.torch.cuda.current_stream(self.dev).cuda_stream
+        self.vox_counts_d = D.counters(self.dev)
 
     def candidates(self, table: OrganelleTable, max_rep_dist_nm: float, stage: int = 3):
         """The pair list of one type (both calls of ``sd_synssv_map_pairs``; waits for the count in between).  -> dict."""
-        torch, n = self.torch, self.n
+        from .. import _dev as D
+        n = self.n
         keep = np.flatnonzero(table.cells != 0)
         order = keep[np.argsort(table.cells[keep], kind='stable')]
         c = dict(table=table, m=len(order), P=0, side_begin=np.zeros(2 * n + 1, np.int64), pair_obj=np.zeros(0, np.int64))
@@ -572,46 +558,43 @@ class _ObjectMapper:
             return c
         if len(table) >= 2 ** 31:
             raise ValueError('map_objects_from_synssv_partners: fewer than 2^31 organelles of one type per call')
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
-        c['cell_d'], c['row_d'] = up(table.cells[order].view(np.int64)), up(order.astype(np.uint32).view(np.int32))
-        c['rep_d'] = up(table.rep_coords[order])
-        c['begin_d'] = torch.empty(2 * n + 1, dtype=torch.int32, device=self.dev)
-        c['counts_d'] = torch.zeros(8, dtype=torch.int64, device=self.dev)
+        c['cell_d'], c['row_d'] = D.up(table.cells[order], self.dev), D.up(order.astype(np.uint32), self.dev)
+        c['rep_d'] = D.up(table.rep_coords[order], self.dev)
+        c['begin_d'] = D.empty(2 * n + 1, D.i32, self.dev)
+        c['counts_d'] = D.counters(self.dev)
         c['D'] = float(max_rep_dist_nm)
         self.pairs_call(c, None)
         c['P'] = P = int(c['counts_d'][0].item())
         if P >= 2 ** 31:
             raise ValueError('map_objects_from_synssv_partners: fewer than 2^31 (side, organelle) pairs per type and call')
-        c['side_begin'] = c['begin_d'].cpu().numpy().view(np.uint32).astype(np.int64)
+        c['side_begin'] = D.down(c['begin_d'], view=np.uint32).astype(np.int64)
         if P:
-            c['obj_d'] = torch.empty(P, dtype=torch.int32, device=self.dev)
+            c['obj_d'] = D.empty(P, D.i32, self.dev)
             self.pairs_call(c, c['obj_d'])
-            c['pair_obj'] = c['obj_d'].cpu().numpy().view(np.uint32).astype(np.int64)
+            c['pair_obj'] = D.down(c['obj_d'], view=np.uint32).astype(np.int64)
         return c
 
     def pairs_call(self, c, obj_d):
-        L.check(self.lib.sd_synssv_map_pairs(self.cell_d.data_ptr(), self.rep_d.data_ptr(), 2 * self.n, c['cell_d'].data_ptr(), c['row_d'].data_ptr(),
-                                             c['rep_d'].data_ptr(), c['m'], self._scale_c, c['D'], c['begin_d'].data_ptr(),
-                                             None if obj_d is None else obj_d.data_ptr(), 0 if obj_d is None else obj_d.numel(),
-                                             c['counts_d'].data_ptr(), self.pair_tmp.data_ptr(), self.pair_tmp.numel(), self._stream()),
-                'sd_synssv_map_pairs')
+        from .. import _dev as D
+        D.call('sd_synssv_map_pairs', self.dev, self.cell_d, self.rep_d, 2 * self.n, c['cell_d'], c['row_d'], c['rep_d'], c['m'], self._scale_c,
+               c['D'], c['begin_d'], obj_d, 0 if obj_d is None else obj_d.numel(), c['counts_d'], self.pair_tmp, self.pair_tmp.numel())
 
     def reserve(self, n_pairs: int):
         """Scratch of the query for up to `n_pairs` pairs; a new allocation loses the prepared voxels."""
         if self.tmp is None or n_pairs > self.tmp_pairs:
+            from .. import _dev as D
             self.tmp_pairs = int(n_pairs)
-            self.tmp = self.torch.empty(self.lib.sd_synssv_map_query_temp_bytes(self.n, self.n_sv, self.tmp_pairs), dtype=self.torch.uint8,
-                                        device=self.dev)
+            self.tmp = D.scratch('sd_synssv_map_query_temp_bytes', self.dev, self.n, self.n_sv, self.tmp_pairs)
             self.prepared = False
 
     def _query_call(self, stages, R, c=None, out=None, counts_d=None, n_items=0):
-        z = lambda k: c[k].data_ptr() if c is not None else None
+        from .. import _dev as D
+        z = lambda k: c[k] if c is not None else None
         t = c['table'] if c is not None else None
-        L.check(self.lib.sd_synssv_map_query(self.vox_d.data_ptr(), self.vb_d.data_ptr(), self.svb_d.data_ptr(), self.n, self.n_vox, self.n_sv,
-                                             z('vert_d'), z('vtb_d'), len(t) if t is not None else 0, len(t.vertices) if t is not None else 0,
-                                             z('begin_d'), z('obj_d'), c['P'] if c is not None else 0, self.tmp_pairs, self.f, self._scale_c,
-                                             float(R), int(stages), int(n_items), *(o.data_ptr() if o is not None else None for o in (out or (None,) * 3)),
-                                             counts_d.data_ptr(), self.tmp.data_ptr(), self.tmp.numel(), self._stream()), 'sd_synssv_map_query')
+        D.call('sd_synssv_map_query', self.dev, self.vox_d, self.vb_d, self.svb_d, self.n, self.n_vox, self.n_sv, z('vert_d'), z('vtb_d'),
+               len(t) if t is not None else 0, len(t.vertices) if t is not None else 0, z('begin_d'), z('obj_d'), c['P'] if c is not None else 0,
+               self.tmp_pairs, self.f, self._scale_c, float(R), int(stages), int(n_items), *(out or (None,) * 3), counts_d, self.tmp,
+               self.tmp.numel())
 
     def prepare(self):
         """Stage 1: the sampled voxels of all synapses, sorted and tiled, into the scratch (asynchronous)."""
@@ -622,7 +605,8 @@ class _ObjectMapper:
 
     def query(self, c, max_vert_dist_nm: float):
         """Stage 2 for the pair list `c` of ``candidates`` (waits for the device).  -> (``PairList``, counts as a dict)."""
-        torch, P, table = self.torch, c['P'], c['table']
+        from .. import _dev as D
+        P, table = c['P'], c['table']
         if not P:
             return PairList.empty(self.n), dict.fromkeys(MAP_COUNT_NAMES, 0)
         n_vert = -(-np.diff(table.vert_begin) // self.f)
@@ -639,16 +623,15 @@ class _ObjectMapper:
         if not self.prepared:
             self.prepare()
         if 'vert_d' not in c:
-            c['vert_d'], c['vtb_d'] = torch.from_numpy(table.vertices).to(self.dev), torch.from_numpy(table.vert_begin).to(self.dev)
-        out = (torch.empty(P, dtype=torch.int32, device=self.dev), torch.empty(P, dtype=torch.int32, device=self.dev),
-               torch.empty(P, dtype=torch.int64, device=self.dev))
-        counts_d = torch.zeros(8, dtype=torch.int64, device=self.dev)
+            c['vert_d'], c['vtb_d'] = D.up(table.vertices, self.dev), D.up(table.vert_begin, self.dev)
+        out = (D.empty(P, D.i32, self.dev), D.empty(P, D.i32, self.dev), D.empty(P, D.i64, self.dev))
+        counts_d = D.counters(self.dev)
         self._query_call(2, max_vert_dist_nm, c, out, counts_d, n_items)
-        counts = counts_d.cpu().numpy()
-        if counts[7] or int(self.vox_counts_d.cpu().numpy()[7]):
+        counts = D.down(counts_d)
+        if counts[7] or int(D.down(self.vox_counts_d)[7]):
             raise RuntimeError('sd_synssv_map_query: an offset or an organelle row was out of range')
-        u = lambda t: t.cpu().numpy().view(np.uint32).astype(np.int64)
-        pl = PairList(c['side_begin'], c['pair_obj'], u(out[0]), u(out[1]), out[2].cpu().numpy().view(np.float64))
+        u = lambda t: D.down(t, view=np.uint32).astype(np.int64)
+        pl = PairList(c['side_begin'], c['pair_obj'], u(out[0]), u(out[1]), D.down(out[2], view=np.float64))
         if not np.array_equal(pl.pair_len, plen) or int(counts[1]) != n_items:
             raise RuntimeError('sd_synssv_map_query: the sampled vertex counts of the device differ from the host\'s')
         return pl, dict(zip(MAP_COUNT_NAMES, (int(v) for v in counts[:6])))
@@ -810,24 +793,21 @@ class PackedForest:
 
     def predict_proba(self, features, device=None) -> np.ndarray:
         """float64 (n, classes) on the device: ``RandomForestClassifier.predict_proba`` with ``n_jobs=1``, bit for bit."""
-        import torch
-        from .find_object_properties import _cs_device
+        from .. import _dev as D
         x = self.check_rows(features)
         out = np.zeros((len(x), self.n_classes), np.float64)
         if not len(x):
             return out
         if len(x) >= 2 ** 31:
             raise ValueError('PackedForest.predict_proba: fewer than 2^31 rows per call')
-        lib, dev = L.load(), _cs_device(device)
-        up = lambda a: torch.from_numpy(a).to(dev)
-        arrs = [up(a) for a in (x, self.feature, self.threshold, self.left, self.right, self.proba, self.tree_begin)]
-        out_d = torch.empty(out.shape, dtype=torch.float64, device=dev)
-        counts_d = torch.zeros(8, dtype=torch.int64, device=dev)
-        L.check(lib.sd_syn_props_forest(arrs[0].data_ptr(), len(x), self.n_features, *(a.data_ptr() for a in arrs[1:]), self.n_trees,
-                                        len(self.feature), self.n_classes, out_d.data_ptr(), counts_d.data_ptr(),
-                                        torch.cuda.current_stream(dev).cuda_stream), 'sd_syn_props_forest')
-        out = out_d.cpu().numpy()
-        if int(counts_d.cpu().numpy()[7]):
+        dev = D.device(device)
+        arrs = [D.up(a, dev) for a in (x, self.feature, self.threshold, self.left, self.right, self.proba, self.tree_begin)]
+        out_d = D.empty(out.shape, D.f64, dev)
+        counts_d = D.counters(dev)
+        D.call('sd_syn_props_forest', dev, arrs[0], len(x), self.n_features, *arrs[1:], self.n_trees, len(self.feature), self.n_classes, out_d,
+               counts_d)
+        out = D.down(out_d)
+        if int(D.down(counts_d)[7]):
             raise RuntimeError('sd_syn_props_forest: a node or a feature index was out of range')
         return out
 
@@ -968,8 +948,7 @@ def segmented_knn(points, begin, labels, q_cell, q_xyz, k: int, device=None, ret
     ((dx dx) + dy dy) + dz dz in float64: the label (`labels` int32 per point; None: the row of the point) with the highest count, on
     equal counts the one that occurs first in that order; -1 for a cell without points.  With `return_neighbours` also the rows
     (n_q, k) int32, padded with -1, and d^2 (n_q, k) float64, padded with inf; with `return_counts` the device's counters."""
-    import torch
-    from .find_object_properties import _cs_device
+    from .. import _dev as D
     pts = np.asarray(points)
     pts = np.ascontiguousarray(pts, dtype=np.float32 if pts.dtype == np.float32 else np.float64).reshape(-1, 3)
     begin = np.ascontiguousarray(begin, dtype=np.int64).reshape(-1)
@@ -993,26 +972,23 @@ def segmented_knn(points, begin, labels, q_cell, q_xyz, k: int, device=None, ret
         labels = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
         if len(labels) != len(pts):
             raise ValueError('Size of vertices and their labels does not match!')
-    lib, dev = L.load(), _cs_device(device)
-    up = lambda a: torch.from_numpy(a).to(dev)
-    pts_d, begin_d, lab_d = up(pts), up(begin), None if labels is None else up(labels)
-    qc_d, qx_d = up(q_cell.astype(np.uint32).view(np.int32)), up(q_xyz)
+    dev = D.device(device)
+    pts_d, begin_d, lab_d = D.up(pts, dev), D.up(begin, dev), None if labels is None else D.up(labels, dev)
+    qc_d, qx_d = D.up(q_cell.astype(np.uint32), dev), D.up(q_xyz, dev)
     kk = max(1, min(k, L.SD_SYN_PROPS_MAX_K))
-    vote_d = torch.empty(max(n_q, 1), dtype=torch.int32, device=dev)
-    idx_d = torch.empty((max(n_q, 1), kk), dtype=torch.int32, device=dev) if return_neighbours else None
-    d2_d = torch.empty((max(n_q, 1), kk), dtype=torch.float64, device=dev) if return_neighbours else None
-    counts_d = torch.zeros(8, dtype=torch.int64, device=dev)
-    tmp = torch.empty(lib.sd_syn_props_knn_temp_bytes(len(pts), n_cells), dtype=torch.uint8, device=dev)
-    ptr = lambda t: None if t is None else t.data_ptr()
-    L.check(lib.sd_syn_props_knn(pts_d.data_ptr(), int(pts.dtype == np.float32), begin_d.data_ptr(), n_cells, len(pts), ptr(lab_d), qc_d.data_ptr(),
-                                 qx_d.data_ptr(), n_q, k, 3, vote_d.data_ptr(), ptr(idx_d), ptr(d2_d), counts_d.data_ptr(), tmp.data_ptr(),
-                                 tmp.numel(), torch.cuda.current_stream(dev).cuda_stream), 'sd_syn_props_knn')
-    counts = counts_d.cpu().numpy()
+    vote_d = D.empty(n_q, D.i32, dev)
+    idx_d = D.empty((n_q, kk), D.i32, dev) if return_neighbours else None
+    d2_d = D.empty((n_q, kk), D.f64, dev) if return_neighbours else None
+    counts_d = D.counters(dev)
+    tmp = D.scratch('sd_syn_props_knn_temp_bytes', dev, len(pts), n_cells)
+    D.call('sd_syn_props_knn', dev, pts_d, int(pts.dtype == np.float32), begin_d, n_cells, len(pts), lab_d, qc_d, qx_d, n_q, k, 3, vote_d, idx_d,
+           d2_d, counts_d, tmp, tmp.numel())
+    counts = D.down(counts_d)
     if int(counts[7]):
         raise RuntimeError('sd_syn_props_knn: an offset, a cell row or a point row was out of range')
-    out = [vote_d.cpu().numpy()[:n_q]]
+    out = [D.down(vote_d)[:n_q]]
     if return_neighbours:
-        out += [idx_d.cpu().numpy()[:n_q], d2_d.cpu().numpy()[:n_q]]
+        out += [D.down(idx_d)[:n_q], D.down(d2_d)[:n_q]]
     if return_counts:
         out.append(dict(tiles_visited=int(counts[0]), tiles_skipped=int(counts[1])))
     return out[0] if len(out) == 1 else tuple(out)
@@ -1070,9 +1046,8 @@ def collect_properties_from_ssv_partners(syn_ssv, cells: CellTable, scaling=None
     A cell without mesh vertices gets zeros in every column; one without skeleton nodes -1 and inf; a skeleton without the key -1
     (``latent_morph``: inf).  ValueError: a partner cell that is not in the table, a cell whose vertices are all ignored.
     Not built: storages, ``cache_syn.pkl`` files, batch jobs; k <= 64.  No CPU fallback."""
-    import torch
+    from .. import _dev as D
     from .. import global_params
-    from .find_object_properties import _cs_device
     cfg = global_params.config
     if scaling is None:
         scaling = cfg['scaling']
@@ -1140,14 +1115,14 @@ def collect_properties_from_ssv_partners(syn_ssv, cells: CellTable, scaling=None
             props['latent_morph'][sides] = np.inf
             sk = sides[has_skel[row[sides]]]
             if len(sk):
-                dev = _cs_device(device)
-                near_d = torch.from_numpy(_nearest_nodes(cells, used & has_mesh, row[sk], q_xyz[sk], scale, device)).to(dev)
+                dev = D.device(device)
+                near_d = D.up(_nearest_nodes(cells, used & has_mesh, row[sk], q_xyz[sk], scale, device), dev)
                 if pred_key_ax in cells.node_attrs:
-                    ax = torch.from_numpy(cells.node_attrs[pred_key_ax]).to(dev)[near_d].cpu().numpy()
+                    ax = D.down(D.up(cells.node_attrs[pred_key_ax], dev)[near_d])
                     ok = cells.node_attr_present[pred_key_ax][row[sk]]
                     props['partner_axoness'][sk[ok]] = ax[ok]
                 if 'latent_morph' in cells.node_attrs:
-                    lm = torch.from_numpy(cells.node_attrs['latent_morph']).to(dev)[near_d].cpu().numpy()
+                    lm = D.down(D.up(cells.node_attrs['latent_morph'], dev)[near_d])
                     ok = cells.node_attr_present['latent_morph'][row[sk]]
                     props['latent_morph'][sk[ok]] = lm[ok]
     return SynSsvProperties(partner_axoness=props['partner_axoness'].reshape(n, 2), partner_spiness=props['partner_spiness'].reshape(n, 2),

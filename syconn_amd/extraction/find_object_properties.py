@@ -13,19 +13,16 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from .. import _dev as D
 from .. import _lib as L
 
 
 def _to_device(vol, device) -> Tuple[torch.Tensor, int]:
     """-> (contiguous device tensor viewed as a signed integer type of the same width, SD_U32 | SD_U64)."""
     if isinstance(vol, np.ndarray):
-        if vol.dtype == np.uint64:
-            t = torch.from_numpy(np.ascontiguousarray(vol).view(np.int64))
-        elif vol.dtype == np.uint32:
-            t = torch.from_numpy(np.ascontiguousarray(vol).view(np.int32))
-        else:
+        if vol.dtype not in (np.uint64, np.uint32):
             raise TypeError(f'label volumes must be uint32 or uint64, got {vol.dtype}')   # the fused type n_type of the .pyx
-        t = t.to(device)
+        t = D.up(vol, device)
     else:
         t = vol
         if t.dtype in (torch.uint64, torch.int64):
@@ -62,10 +59,7 @@ class DeviceScan:
 
     def __init__(self, device=None, cap_obj: Optional[int] = None, cap_pair: Optional[int] = None):
         self.lib = L.load()
-        if not torch.cuda.is_available():
-            raise RuntimeError('syconn_amd: no MI355X visible to PyTorch-ROCm; this package has no CPU fallback')
-        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
-        L.check(self.lib.sd_init(self.device.index or 0), 'sd_init')
+        self.device = D.device(device)
         self.cap_obj = _pow2_at_least(cap_obj) if cap_obj else 0
         self.cap_pair = _pow2_at_least(cap_pair) if cap_pair else 0
         self.tabs: List[torch.Tensor] = []
@@ -89,7 +83,7 @@ class DeviceScan:
         `status_out` (int32[2] on the device): the pass writes its overflow flags there and this call does NOT wait for them -- the
         caller reads them later and repeats the work with larger tables (`cap_obj` / `cap_pair` are then the caller's business);
         without it the flags are awaited here and an overflowed pass is repeated with 4x the capacity."""
-        lib, device = self.lib, self.device
+        device = self.device
         vols = [v for v in ([cell] if cell is not None else []) + list(subs)]
         if not vols:
             raise ValueError('no volume given')
@@ -111,17 +105,14 @@ class DeviceScan:
             self.cap_obj = _pow2_at_least(min(2 * nvox, max(1 << 16, nvox // 256)))
         if not self.cap_pair:
             self.cap_pair = self.cap_obj
-        stream = torch.cuda.current_stream(device).cuda_stream
         while True:
             self._room(1 + n_sub, n_sub if cell_t is not None else 0)
             tabs, ptabs = self.tabs, self.ptabs
             sub_ptrs = (C.c_void_p * max(n_sub, 1))(*[t.data_ptr() for t in sub_ts])
             sub_tabs = (C.c_void_p * max(n_sub, 1))(*[t.data_ptr() for t in tabs[1:]])
             pair_tabs = (C.c_void_p * max(n_sub, 1))(*[t.data_ptr() for t in ptabs])
-            L.check(lib.sd_segstats_scan(cell_t.data_ptr() if cell_t is not None else None, sub_ptrs, n_sub, dtype, *shape,
-                                         tabs[0].data_ptr() if cell_t is not None else None, sub_tabs, self.cap_obj, pair_tabs,
-                                         self.cap_pair, 1 if want_props else 0,
-                                         (self.status if status_out is None else status_out).data_ptr(), stream), 'sd_segstats_scan')
+            D.call('sd_segstats_scan', device, cell_t, sub_ptrs, n_sub, dtype, *shape, tabs[0] if cell_t is not None else None, sub_tabs,
+                   self.cap_obj, pair_tabs, self.cap_pair, 1 if want_props else 0, self.status if status_out is None else status_out)
             if status_out is not None:
                 break
             st = self.status.cpu().tolist()
@@ -149,36 +140,28 @@ def segstats(cell, subs: Sequence = (), want_props: bool = True, device=None, ca
              cap_pair: Optional[int] = None) -> SegStats:
     """One streaming pass over `cell` (may be None) and the `subs` volumes, all of one (X, Y, Z) shape and dtype."""
     sc = DeviceScan(device, cap_obj, cap_pair).scan(cell, subs, want_props)
-    lib, device, cap_obj, cap_pair, tabs, ptabs = sc.lib, sc.device, sc.cap_obj, sc.cap_pair, sc.tabs, sc.ptabs
+    device, cap_obj, cap_pair, tabs, ptabs = sc.device, sc.cap_obj, sc.cap_pair, sc.tabs, sc.ptabs
     shape, n_sub = sc.shape, sc.n_sub
     cell_t = True if sc.has_cell else None
-    stream = torch.cuda.current_stream(device).cuda_stream
 
     def objects(tab):
         n_max = cap_obj
-        cnt = torch.zeros(1, dtype=torch.int64, device=device)
-        ids = torch.empty(n_max, dtype=torch.int64, device=device)
-        first = torch.empty(n_max, dtype=torch.int64, device=device)
-        size = torch.empty(n_max, dtype=torch.int64, device=device)
-        bb = torch.empty((n_max, 6), dtype=torch.int32, device=device)
-        L.check(lib.sd_segstats_compact_objects(tab.data_ptr(), cap_obj, ids.data_ptr(), first.data_ptr(), size.data_ptr(),
-                                                bb.data_ptr(), n_max, cnt.data_ptr(), stream), 'sd_segstats_compact_objects')
+        cnt = D.counters(device, 1)
+        ids, first, size = (D.empty(n_max, D.i64, device) for _ in range(3))
+        bb = D.empty((n_max, 6), D.i32, device)
+        D.call('sd_segstats_compact_objects', device, tab, cap_obj, ids, first, size, bb, n_max, cnt)
         n = int(cnt.item())
-        ids_h = ids[:n].cpu().numpy().view(np.uint64)
+        ids_h = D.down(ids, n, np.uint64)
         order = np.argsort(ids_h, kind='stable')
-        return (ids_h[order], first[:n].cpu().numpy()[order], size[:n].cpu().numpy()[order],
-                bb[:n].cpu().numpy().reshape(n, 2, 3)[order])
+        return ids_h[order], D.down(first, n)[order], D.down(size, n)[order], D.down(bb, n).reshape(n, 2, 3)[order]
 
     def pairs(ptab, stab, ctab):
         n_max = cap_pair
-        cnt = torch.zeros(1, dtype=torch.int64, device=device)
-        a, b, c = (torch.empty(n_max, dtype=torch.int64, device=device) for _ in range(3))
-        L.check(lib.sd_segstats_compact_pairs(ptab.data_ptr(), cap_pair, stab.data_ptr(), ctab.data_ptr(), cap_obj,
-                                              a.data_ptr(), b.data_ptr(), c.data_ptr(), n_max, cnt.data_ptr(), stream),
-                'sd_segstats_compact_pairs')
+        cnt = D.counters(device, 1)
+        a, b, c = (D.empty(n_max, D.i64, device) for _ in range(3))
+        D.call('sd_segstats_compact_pairs', device, ptab, cap_pair, stab, ctab, cap_obj, a, b, c, n_max, cnt)
         n = int(cnt.item())
-        s_h, c_h, n_h = (t[:n].cpu().numpy() for t in (a, b, c))
-        s_h, c_h = s_h.view(np.uint64), c_h.view(np.uint64)
+        s_h, c_h, n_h = D.down(a, n, np.uint64), D.down(b, n, np.uint64), D.down(c, n)
         order = np.lexsort((c_h, s_h))
         return s_h[order], c_h[order], n_h[order]
 
@@ -235,21 +218,12 @@ def map_subcell_C(ch, subcell_chs):
 
 
 # ---- contact sites (block_processing_C.pyx:21-75, find_object_properties.py:424-472 of the reference) -------------------------
-def _cs_device(device=None) -> torch.device:
-    lib = L.load()
-    if not torch.cuda.is_available():
-        raise RuntimeError('syconn_amd: no MI355X visible to PyTorch-ROCm; this package has no CPU fallback')
-    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
-    L.check(lib.sd_init(dev.index or 0), 'sd_init')
-    return dev
-
-
 def _u32_volume(arr, device) -> torch.Tensor:
     """uint32 (X, Y, Z) volume -> contiguous int32 device tensor (the same bits)."""
     if isinstance(arr, np.ndarray):
         if arr.dtype != np.uint32:
             raise TypeError(f'the cell segmentation must be uint32, got {arr.dtype}')
-        t = torch.from_numpy(np.ascontiguousarray(arr).view(np.int32)).to(device)
+        t = D.up(arr, device)
     else:
         if arr.dtype not in (torch.uint32, torch.int32):
             raise TypeError(f'the cell segmentation must be a 32-bit integer tensor, got {arr.dtype}')
@@ -272,12 +246,11 @@ def _mask_volume(arr, device) -> torch.Tensor:
 def detect_seg_boundaries(arr, return_device: bool = False, device=None):
     """find_object_properties.py:424-455: boolean mask of the non-zero voxels of `arr` (uint32, x, y, z) that have an in-array
     6-neighbour with another value (0 counts as another value).  ``return_device``: a uint8 device tensor instead."""
-    dev = _cs_device(device)
+    dev = D.device(device)
     seg = _u32_volume(arr, dev)
     X, Y, Z = (int(s) for s in seg.shape)
     mask = torch.empty((X, Y, Z), dtype=torch.uint8, device=dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    L.check(L.load().sd_seg_boundaries(seg.data_ptr(), X, Y, Z, mask.data_ptr(), stream), 'sd_seg_boundaries')
+    D.call('sd_seg_boundaries', dev, seg, X, Y, Z, mask)
     return mask if return_device else mask.cpu().numpy().view(np.bool_)
 
 
@@ -287,7 +260,7 @@ def process_block_nonzero(edges, arr, stencil1=(7, 7, 3), return_device: bool = 
     of shape ``arr.shape - stencil1 + 1``.  ``return_device``: an int64 device tensor holding the uint64 bits."""
     stencil = tuple(int(s) for s in stencil1)
     assert sum(s % 2 for s in stencil) == 3
-    dev = _cs_device(device)
+    dev = D.device(device)
     seg = _u32_volume(arr, dev)
     e = _mask_volume(edges, dev)
     X, Y, Z = (int(s) for s in seg.shape)
@@ -295,12 +268,9 @@ def process_block_nonzero(edges, arr, stencil1=(7, 7, 3), return_device: bool = 
         raise ValueError('edges and arr must have the same shape')
     out_shape = tuple(max(n - s + 1, 0) for n, s in zip((X, Y, Z), stencil))
     out = torch.zeros(out_shape, dtype=torch.int64, device=dev)
-    lib = L.load()
-    ws = torch.empty(lib.sd_contact_partners_workspace_bytes(), dtype=torch.uint8, device=dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
+    ws = D.scratch('sd_contact_partners_workspace_bytes', dev)
     if out.numel():
-        L.check(lib.sd_contact_partners(e.data_ptr(), seg.data_ptr(), X, Y, Z, *stencil, out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                        stream), 'sd_contact_partners')
+        D.call('sd_contact_partners', dev, e, seg, X, Y, Z, *stencil, out, ws, ws.numel())
     return out if return_device else out.cpu().numpy().view(np.uint64)
 
 
@@ -310,7 +280,7 @@ def detect_cs(arr, stencil=None, return_device: bool = False, device=None):
     if stencil is None:
         from .. import global_params
         stencil = global_params.config['cell_objects']['cs_filtersize']
-    dev = _cs_device(device)
+    dev = D.device(device)
     seg = _u32_volume(arr, dev)
     edges = detect_seg_boundaries(seg, return_device=True, device=dev)
     return process_block_nonzero(edges, seg, stencil, return_device=return_device, device=dev)
@@ -371,7 +341,7 @@ class CsSyntypeScan:
 
     def __init__(self, device=None, cap: Optional[int] = None):
         self.lib = L.load()
-        self.device = _cs_device(device)
+        self.device = D.device(device)
         self.cap = _pow2_at_least(cap) if cap else 0
         self.table = None
         self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
@@ -397,16 +367,12 @@ class CsSyntypeScan:
         if not self.cap:
             self.cap = _pow2_at_least(min(2 * max(nvox, 1), max(1 << 12, nvox // 256)))
         cores = [torch.empty(ext, dtype=c.dtype, device=dev) for _ in range(2)] if want_cores else [None, None]
-        stream = torch.cuda.current_stream(dev).cuda_stream
         self.passes = 0
         while True:
             nb = lib.sd_cs_syntype_table_bytes(self.cap)
             if self.table is None or self.table.numel() != nb:
                 self.table = torch.empty(nb, dtype=torch.uint8, device=dev)
-            L.check(lib.sd_cs_syntype_scan(c.data_ptr(), dtype, m[0].data_ptr(), m[1].data_ptr(), m[2].data_ptr(), *shape, *org, *ext,
-                                           self.table.data_ptr(), self.cap, cores[0].data_ptr() if want_cores else None,
-                                           cores[1].data_ptr() if want_cores else None, self.status.data_ptr(), stream),
-                    'sd_cs_syntype_scan')
+            D.call('sd_cs_syntype_scan', dev, c, dtype, *m, *shape, *org, *ext, self.table, self.cap, *cores, self.status)
             self.passes += 1
             if not int(self.status.item()):
                 break
@@ -414,24 +380,19 @@ class CsSyntypeScan:
                 raise RuntimeError('sd_cs_syntype_scan: table overflow at maximum capacity')
             self.cap *= 4
         cap = self.cap
-        cnt = torch.zeros(1, dtype=torch.int64, device=dev)
-        ids = torch.empty(cap, dtype=torch.int64, device=dev)
-        slots = torch.empty(cap, dtype=torch.int32, device=dev)
-        L.check(lib.sd_cs_syntype_compact(self.table.data_ptr(), cap, ids.data_ptr(), slots.data_ptr(), cap, cnt.data_ptr(), stream),
-                'sd_cs_syntype_compact')
+        cnt = D.counters(dev, 1)
+        ids, slots = D.empty(cap, D.i64, dev), D.empty(cap, D.i32, dev)
+        D.call('sd_cs_syntype_compact', dev, self.table, cap, ids, slots, cap, cnt)
         n = int(cnt.item())
         # ascending ids: the order is taken on the host from the n ids, as segstats does
-        order = np.argsort(ids[:n].cpu().numpy().view(np.uint64), kind='stable')
-        slots_sorted = slots[:n][torch.from_numpy(order).to(dev)].contiguous()
-        rec = torch.empty((max(n, 1), L.SD_CST_COLS), dtype=torch.int64, device=dev)
-        n_syn = torch.zeros(1, dtype=torch.int64, device=dev)
-        L.check(lib.sd_cs_syntype_records(self.table.data_ptr(), cap, slots_sorted.data_ptr() if n else None, n, *ext, rec.data_ptr(),
-                                          n_syn.data_ptr(), stream), 'sd_cs_syntype_records')
+        order = np.argsort(D.down(ids, n, np.uint64), kind='stable')
+        slots_sorted = slots[:n][D.up(order, dev)].contiguous()
+        rec = D.empty((n, L.SD_CST_COLS), D.i64, dev)
+        n_syn = D.counters(dev, 1)
+        D.call('sd_cs_syntype_records', dev, self.table, cap, slots_sorted if n else None, n, *ext, rec, n_syn)
         ns = int(n_syn.item())
-        vox = torch.empty((max(ns, 1), 3), dtype=torch.int64, device=dev)
-        offs = (C.c_int64 * 3)(*off.tolist())
-        L.check(lib.sd_cs_syntype_voxels(c.data_ptr(), dtype, m[0].data_ptr(), *shape, *org, rec.data_ptr(), n, ns, offs,
-                                         vox.data_ptr(), self.status.data_ptr(), stream), 'sd_cs_syntype_voxels')
+        vox = D.empty((ns, 3), D.i64, dev)
+        D.call('sd_cs_syntype_voxels', dev, c, dtype, m[0], *shape, *org, rec, n, ns, D.i64x3(off), vox, self.status)
         if ns and int(self.status.item()):
             raise RuntimeError('sd_cs_syntype_voxels: voxel counts disagree with the site records')
         return CsSyntype(rec[:n], vox[:ns], *cores)

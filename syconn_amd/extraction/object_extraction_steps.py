@@ -19,6 +19,7 @@ from typing import List, Optional, Sequence, Tuple, Union
 import numpy as np
 import torch
 
+from .. import _dev as D
 from .. import _lib as L
 
 _MOPS = {'binary_opening': L.SD_MOP_OPENING, 'binary_closing': L.SD_MOP_CLOSING, 'binary_dilation': L.SD_MOP_DILATION,
@@ -68,11 +69,7 @@ def object_segmentation_first_stage(prob, threshold: float, morph_ops: Sequence[
     tensors) does not need it on the host.  `return_distance` (watershed branch only, ``ValueError`` otherwise): the float32
     (x,y,z) distance transform of tmp_data (:349-350, of the WHOLE mask -- without it only the components the flood works on are
     transformed) is returned last."""
-    lib = L.load()
-    if not torch.cuda.is_available():
-        raise RuntimeError('syconn_amd: no MI355X visible to PyTorch-ROCm; this package has no CPU fallback')
-    device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
-    L.check(lib.sd_init(device.index or 0), 'sd_init')
+    device = D.device(device)
     morph_ops = list(morph_ops)
     for m in morph_ops:
         if m not in _MOPS:
@@ -87,7 +84,7 @@ def object_segmentation_first_stage(prob, threshold: float, morph_ops: Sequence[
     if isinstance(prob, np.ndarray):
         if prob.dtype != np.uint8:
             raise TypeError('probability maps are uint8 (KnossosDataset raw data)')
-        p = torch.from_numpy(np.ascontiguousarray(prob)).to(device)
+        p = D.up(prob, device)
     else:
         if prob.dtype != torch.uint8:
             raise TypeError('probability maps are uint8 (KnossosDataset raw data)')
@@ -105,26 +102,19 @@ def object_segmentation_first_stage(prob, threshold: float, morph_ops: Sequence[
     n = len(names)
     ops_a = (C.c_int32 * max(n, 1))(*[_MOPS[m] for m in names])
     it_a = (C.c_int32 * max(n, 1))(*counts)
-    stream = torch.cuda.current_stream(device).cuda_stream
+    st_p, st_shape = st.ctypes.data_as(C.c_void_p), [int(s) for s in st.shape]
     if watershed:
-        ws_bytes = lib.sd_objseg_watershed_workspace_bytes(X, Y, Z, pmax)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
+        ws = D.scratch('sd_objseg_watershed_workspace_bytes', device, X, Y, Z, pmax)
         ns = len(snames)
         sops_a = (C.c_int32 * ns)(*[_MOPS[m] for m in snames])
         sit_a = (C.c_int32 * ns)(*scounts)
-        pitch = (C.c_int32 * 3)(*[int(np.uint32(v)) for v in np.asarray(scaling)[:3]])          # scaling.astype(np.uint32), :350
-        L.check(lib.sd_object_segmentation_watershed(
-            p.data_ptr(), X, Y, Z, float(threshold), ops_a, it_a, n, sops_a, sit_a, ns, st.ctypes.data_as(C.c_void_p),
-            *[int(s) for s in st.shape], int(min_seed_vx), pitch, labels.data_ptr(), max_label.data_ptr(),
-            markers.data_ptr() if markers is not None else None, dist.data_ptr() if dist is not None else None,
-            mask.data_ptr() if mask is not None else None, ws.data_ptr(), ws_bytes, stream), 'sd_object_segmentation_watershed')
+        pitch = D.i32x3(np.uint32(v) for v in np.asarray(scaling)[:3])                          # scaling.astype(np.uint32), :350
+        D.call('sd_object_segmentation_watershed', device, p, X, Y, Z, float(threshold), ops_a, it_a, n, sops_a, sit_a, ns, st_p, *st_shape,
+               int(min_seed_vx), pitch, labels, max_label, markers, dist, mask, ws, ws.numel())
     else:
-        ws_bytes = lib.sd_objseg_workspace_bytes(X, Y, Z, pmax)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
-        L.check(lib.sd_object_segmentation(p.data_ptr(), X, Y, Z, float(threshold), ops_a, it_a, n,
-                                           st.ctypes.data_as(C.c_void_p), *[int(s) for s in st.shape], labels.data_ptr(),
-                                           max_label.data_ptr(), mask.data_ptr() if mask is not None else None, ws.data_ptr(),
-                                           ws_bytes, stream), 'sd_object_segmentation')
+        ws = D.scratch('sd_objseg_workspace_bytes', device, X, Y, Z, pmax)
+        D.call('sd_object_segmentation', device, p, X, Y, Z, float(threshold), ops_a, it_a, n, st_p, *st_shape, labels, max_label, mask,
+               ws, ws.numel())
     extra = ((mask,) if return_mask else ()) + ((markers,) if markers is not None else ()) + ((dist,) if dist is not None else ())
     if return_device:
         return (labels, max_label) + extra
@@ -135,11 +125,7 @@ def gaussian_threshold(prob, sigma, threshold: float, device=None, return_device
     """``gaussianSmoothing(tmp_data, sigma)`` followed by ``tmp_data > threshold`` (object_extraction_steps.py:296-297, 316-317)
     for one uint8 (x,y,z) probability map: `sigma` a number or one per axis (x,y,z) in voxels, `threshold` in uint8 units ->
     uint8 0/1 mask (x,y,z) [+ the float32 smoothed map].  vigra's algorithm restated (`sd_gaussian_threshold`, parity unpinned)."""
-    lib = L.load()
-    if not torch.cuda.is_available():
-        raise RuntimeError('syconn_amd: no MI355X visible to PyTorch-ROCm; this package has no CPU fallback')
-    device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
-    L.check(lib.sd_init(device.index or 0), 'sd_init')
+    device = D.device(device)
     p = torch.from_numpy(np.ascontiguousarray(prob)) if isinstance(prob, np.ndarray) else prob
     if p.dtype != torch.uint8:
         raise TypeError('probability maps are uint8 (KnossosDataset raw data)')
@@ -152,12 +138,8 @@ def gaussian_threshold(prob, sigma, threshold: float, device=None, return_device
     X, Y, Z = (int(v) for v in p.shape)
     mask = torch.empty((X, Y, Z), dtype=torch.uint8, device=device)
     sm = torch.empty((X, Y, Z), dtype=torch.float32, device=device) if return_smoothed else None
-    ws_bytes = lib.sd_gauss_workspace_bytes(X, Y, Z)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
-    sg_a = (C.c_double * 3)(*[float(v) for v in sg])
-    L.check(lib.sd_gaussian_threshold(p.data_ptr(), X, Y, Z, sg_a, float(threshold), mask.data_ptr(),
-                                      sm.data_ptr() if sm is not None else None, ws.data_ptr(), ws_bytes,
-                                      torch.cuda.current_stream(device).cuda_stream), 'sd_gaussian_threshold')
+    ws = D.scratch('sd_gauss_workspace_bytes', device, X, Y, Z)
+    D.call('sd_gaussian_threshold', device, p, X, Y, Z, D.f64x3(sg), float(threshold), mask, sm, ws, ws.numel())
     out = (mask,) + ((sm,) if sm is not None else ())
     if not return_device:
         out = tuple(o.cpu().numpy() for o in out)
@@ -168,11 +150,7 @@ def marker_flood(d2, markers, mask, device=None, return_device: bool = False):
     """``skimage.segmentation.watershed(-distance, markers, mask=mask)`` as `_object_segmentation_thread` calls it
     (object_extraction_steps.py:351) for ``distance ** 2 == d2`` (int32 >= 0): (x, y, z) arrays or device tensors -> int32 labels
     and the largest label (`sd_marker_flood`)."""
-    lib = L.load()
-    if not torch.cuda.is_available():
-        raise RuntimeError('syconn_amd: no MI355X visible to PyTorch-ROCm; this package has no CPU fallback')
-    device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
-    L.check(lib.sd_init(device.index or 0), 'sd_init')
+    device = D.device(device)
 
     def dev(a, dt):
         t = torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a
@@ -183,10 +161,8 @@ def marker_flood(d2, markers, mask, device=None, return_device: bool = False):
     X, Y, Z = (int(v) for v in g.shape)
     labels = torch.empty((X, Y, Z), dtype=torch.int32, device=device)
     max_label = torch.zeros(1, dtype=torch.int32, device=device)
-    ws_bytes = lib.sd_objseg_watershed_workspace_bytes(X, Y, Z, 0)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
-    L.check(lib.sd_marker_flood(g.data_ptr(), mk.data_ptr(), m.data_ptr(), X, Y, Z, labels.data_ptr(), max_label.data_ptr(),
-                                ws.data_ptr(), ws_bytes, torch.cuda.current_stream(device).cuda_stream), 'sd_marker_flood')
+    ws = D.scratch('sd_objseg_watershed_workspace_bytes', device, X, Y, Z, 0)
+    D.call('sd_marker_flood', device, g, mk, m, X, Y, Z, labels, max_label, ws, ws.numel())
     if return_device:
         return labels, max_label
     return labels.cpu().numpy(), int(max_label.item())
@@ -311,30 +287,25 @@ def label_offsets(n_components: Sequence[int]) -> Tuple[np.ndarray, int]:
 def make_unique_labels(labels: torch.Tensor, offset: int) -> torch.Tensor:
     """``_make_unique_labels_thread`` (object_extraction_steps.py:425-443) for one chunk: int32 (x,y,z) component labels on the
     device -> uint64 (stored as int64 bits) with `offset` added to every non-zero label (`sd_labels_make_unique`)."""
-    lib = L.load()
     if not (labels.is_cuda and labels.dtype == torch.int32 and labels.is_contiguous()):
         raise TypeError('expected a contiguous int32 device tensor (the labels of object_segmentation_first_stage(return_device=True))')
     out = torch.empty(labels.shape, dtype=torch.int64, device=labels.device)
     with torch.cuda.device(labels.device):
-        L.check(lib.sd_labels_make_unique(labels.data_ptr(), labels.numel(), int(offset), out.data_ptr(),
-                                          torch.cuda.current_stream(labels.device).cuda_stream), 'sd_labels_make_unique')
+        D.call('sd_labels_make_unique', labels.device, labels, labels.numel(), int(offset), out)
     return out
 
 
 def labels_box(vol: torch.Tensor, lo, size, lut: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Contiguous copy of the box ``vol[lo : lo + size]`` of a uint64 (int64 bits) (x,y,z) device volume, optionally mapped through a
     look-up table (`sd_labels_box_lut`); an id beyond the table raises."""
-    lib = L.load()
     if not (vol.is_cuda and vol.dtype == torch.int64 and vol.is_contiguous() and vol.dim() == 3):
         raise TypeError('expected a contiguous 3D int64 / uint64 device tensor')
     lo, size = [int(v) for v in lo], [int(v) for v in size]
     out = torch.empty(size, dtype=torch.int64, device=vol.device)
     status = torch.zeros(1, dtype=torch.int32, device=vol.device) if lut is not None else None
     with torch.cuda.device(vol.device):
-        L.check(lib.sd_labels_box_lut(vol.data_ptr(), *[int(v) for v in vol.shape], *lo, *size,
-                                      lut.data_ptr() if lut is not None else None, lut.numel() if lut is not None else 0,
-                                      out.data_ptr(), status.data_ptr() if status is not None else None,
-                                      torch.cuda.current_stream(vol.device).cuda_stream), 'sd_labels_box_lut')
+        D.call('sd_labels_box_lut', vol.device, vol, *[int(v) for v in vol.shape], *lo, *size, lut, lut.numel() if lut is not None else 0,
+               out, status)
     if status is not None and int(status.item()):
         raise ValueError('apply_merge_list: a label exceeds the merge list (max_label too small)')
     return out
@@ -477,5 +448,5 @@ def apply_merge_list(chunk_vol: torch.Tensor, chunk_size, merge_list) -> torch.T
     shape = np.asarray(chunk_vol.shape, dtype=np.int64)
     size = np.asarray(chunk_size, dtype=np.int64)
     off = (shape - size) // 2
-    lut = merge_list if isinstance(merge_list, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(merge_list).view(np.int64)).to(chunk_vol.device)
+    lut = merge_list if isinstance(merge_list, torch.Tensor) else D.up(merge_list, chunk_vol.device)
     return labels_box(chunk_vol, off, shape - 2 * off, lut)

@@ -8,11 +8,8 @@ the ``k`` nearest mesh vertices per maximum; the marker flood; the 6-connected `
 count.  Windows of a cell run in batches on one stream: the stages of every window are queued without reading anything back, the
 vertices in the boxes of the whole batch are compacted in one call (their total is the one value read per batch before the vote), one
 ``sd_syn_props_knn`` call votes for all maxima of the batch, and the per-window results come back in one copy.  No CPU fallback."""
-import ctypes as C
-
 import numpy as np
 
-from .. import _lib as L
 
 BATCH = 8                    # windows per batch (device buffers are sized for this many)
 REGION_VOX = 256             # windows read from a KnossosDataset are grouped into spatial buckets of this many voxels per axis: with the
@@ -63,21 +60,13 @@ def plan_regions(offsets, size, batch, bucket=None, max_bytes=None):
     return plan
 
 
-def _i64x3(v):
-    return (C.c_int64 * 3)(*[int(x) for x in v])
-
-
-def _f64x3(v):
-    return (C.c_double * 3)(*[float(x) for x in v])
-
-
 class WindowRunner:
     """Device buffers for batches of up to `batch` windows of `shape` zoomed voxels and the stage calls on the current stream."""
 
     def __init__(self, shape, batch: int = BATCH, max_peaks=None, device=None):
         import torch
-        from .find_object_properties import _cs_device
-        self.lib, self.dev = L.load(), _cs_device(device)
+        from .. import _dev as D
+        self.dev = D.device(device)
         self.X, self.Y, self.Z = (int(v) for v in shape)
         self.nvox = self.X * self.Y * self.Z
         if min(self.X, self.Y, self.Z) < 1 or self.nvox >= 2 ** 31 or max(self.X, self.Y, self.Z) > 18000:
@@ -86,9 +75,9 @@ class WindowRunner:
         self.cap = int(min(self.nvox, 1 << 20) if max_peaks is None else max_peaks)
         if self.batch < 1 or self.cap < 1 or self.batch * self.cap >= 2 ** 31:
             raise ValueError(f'batch = {batch}, max_peaks = {max_peaks}: need batch >= 1, max_peaks >= 1, batch * max_peaks < 2^31')
-        self.ws_bytes = int(self.lib.sd_spinehead_workspace_bytes(self.X, self.Y, self.Z))
         B, dev, sh = self.batch, self.dev, (self.X, self.Y, self.Z)
-        self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)
+        self.ws = D.scratch('sd_spinehead_workspace_bytes', dev, *sh)
+        self.ws_bytes = self.ws.numel()
         self.mask = torch.empty(sh, dtype=torch.uint8, device=dev)
         self.filled = torch.empty((B,) + sh, dtype=torch.uint8, device=dev)
         self.d2 = torch.empty((B,) + sh, dtype=torch.int32, device=dev)
@@ -103,64 +92,56 @@ class WindowRunner:
         self.knn_counts = self.buf[B * 4:]
         self.q_slots, self.q_cell, self.q_xyz, self.votes = 0, None, None, None      # sized by the peak counts of a batch (vote)
 
-    @property
-    def stream(self):
-        import torch
-        return torch.cuda.current_stream(self.dev).cuda_stream
-
-    def _res_ptr(self, w, field):
-        return self.res32[w, field:].data_ptr()
-
     # -- stages; every one only queues work ---------------------------------------------------------------------------------------------
     def window_mask(self, seg_d, origin, offset, tabs, sv_d, out=None):
+        from .. import _dev as D
         out = self.mask if out is None else out
         VX, VY, VZ = (int(v) for v in seg_d.shape)
-        L.check(self.lib.sd_spinehead_window_mask(seg_d.data_ptr(), VX, VY, VZ, _i64x3(origin), _i64x3(offset), tabs[0].data_ptr(), tabs[1].data_ptr(),
-                                                  tabs[2].data_ptr(), self.X, self.Y, self.Z, sv_d.data_ptr(), int(sv_d.numel()), out.data_ptr(),
-                                                  self.stream), 'sd_spinehead_window_mask')
+        D.call('sd_spinehead_window_mask', self.dev, seg_d, VX, VY, VZ, D.i64x3(origin), D.i64x3(offset), *tabs, self.X, self.Y, self.Z, sv_d,
+               int(sv_d.numel()), out)
         return out
 
     def fill_holes(self, mask, w):
-        L.check(self.lib.sd_spinehead_fill_holes(mask.data_ptr(), self.X, self.Y, self.Z, self.filled[w].data_ptr(), self._res_ptr(w, 0),
-                                                 self.ws.data_ptr(), self.ws_bytes, self.stream), 'sd_spinehead_fill_holes')
+        from .. import _dev as D
+        D.call('sd_spinehead_fill_holes', self.dev, mask, self.X, self.Y, self.Z, self.filled[w], self.res32[w, 0:], self.ws, self.ws_bytes)
         return self.filled[w]
 
     def edt(self, w):
-        L.check(self.lib.sd_edt_squared(self.filled[w].data_ptr(), self.X, self.Y, self.Z, self.d2[w].data_ptr(), self.ws.data_ptr(), self.ws_bytes,
-                                        self.stream), 'sd_edt_squared')
+        from .. import _dev as D
+        D.call('sd_edt_squared', self.dev, self.filled[w], self.X, self.Y, self.Z, self.d2[w], self.ws, self.ws_bytes)
         return self.d2[w]
 
     def find_peaks(self, w):
-        L.check(self.lib.sd_spinehead_peaks(self.filled[w].data_ptr(), self.d2[w].data_ptr(), self.X, self.Y, self.Z, self.peaks[w].data_ptr(),
-                                            self.cap, self._res_ptr(w, 1), self.ws.data_ptr(), self.ws_bytes, self.stream), 'sd_spinehead_peaks')
+        from .. import _dev as D
+        D.call('sd_spinehead_peaks', self.dev, self.filled[w], self.d2[w], self.X, self.Y, self.Z, self.peaks[w], self.cap, self.res32[w, 1:],
+               self.ws, self.ws_bytes)
 
     def box_vertices(self, verts_d, labels_d, offsets, size):
         """The vertices inside the boxes of the windows at `offsets` (n, 3): (points float64 (m, 3) relative to their window, labels
         int32 (m), begin (n + 2) as a host array).  Reads `begin` and, in the same copy, the peak counts of the windows (``self.n_peaks``)
         back: the one synchronisation of a batch before its results."""
         import torch
+        from .. import _dev as D
         n_win, n_verts = len(offsets), int(verts_d.shape[0])
-        begin_d = torch.zeros(n_win + 2, dtype=torch.int64, device=self.dev)
+        begin_d = D.counters(self.dev, n_win + 2)
         if n_verts == 0:
             self.n_peaks = np.zeros(n_win, np.int64)
             return torch.zeros((0, 3), dtype=torch.float64, device=self.dev), torch.zeros(0, dtype=torch.int32, device=self.dev), begin_d.cpu().numpy()
         if n_verts * n_win >= 2 ** 31:
             raise ValueError(f'{n_verts} vertices x {n_win} windows per batch: the product must stay below 2^31 (use a smaller batch)')
-        off_d = torch.from_numpy(np.ascontiguousarray(offsets, dtype=np.int64)).to(self.dev)
-        tmp = torch.empty(int(self.lib.sd_spinehead_box_vertices_temp_bytes(n_verts, n_win)), dtype=torch.uint8, device=self.dev)
-        size_c = (C.c_int32 * 3)(*[int(v) for v in size])
+        off_d = D.up(np.asarray(offsets, dtype=np.int64), self.dev)
+        tmp = D.scratch('sd_spinehead_box_vertices_temp_bytes', self.dev, n_verts, n_win)
+        size_c = D.i32x3(size)
         f32 = int(verts_d.dtype == torch.float32)
 
         def call(stages, pts, lab, cap):
-            L.check(self.lib.sd_spinehead_box_vertices(verts_d.data_ptr(), f32, labels_d.data_ptr(), n_verts, off_d.data_ptr(), n_win, size_c, stages,
-                                                       begin_d.data_ptr(), None if pts is None else pts.data_ptr(), None if lab is None else lab.data_ptr(),
-                                                       cap, tmp.data_ptr(), tmp.numel(), self.stream), 'sd_spinehead_box_vertices')
+            D.call('sd_spinehead_box_vertices', self.dev, verts_d, f32, labels_d, n_verts, off_d, n_win, size_c, stages, begin_d, pts, lab, cap,
+                   tmp, tmp.numel())
         call(1, None, None, 0)
         both = torch.cat([begin_d, self.res32[:n_win, 1].to(torch.int64)]).cpu().numpy()
         begin, self.n_peaks = both[:n_win + 2], both[n_win + 2:]
         total = int(begin[n_win])
-        pts = torch.empty((max(total, 1), 3), dtype=torch.float64, device=self.dev)
-        lab = torch.empty(max(total, 1), dtype=torch.int32, device=self.dev)
+        pts, lab = D.empty((total, 3), D.f64, self.dev), D.empty(total, D.i32, self.dev)
         if total:
             call(2, pts, lab, total)
         self._begin_d = begin_d
@@ -169,32 +150,29 @@ class WindowRunner:
     def vote(self, n_win, pts, lab, ds, k):
         """One ``sd_syn_props_knn`` call for the maxima of windows 0 .. n_win - 1 against the segmented vertex set of `box_vertices`;
         every window gets as many query slots as the largest peak count of the batch (read back with the vertex offsets)."""
-        import torch
+        from .. import _dev as D
         slots = int(max(1, min(self.cap, int(self.n_peaks[:n_win].max()))))
         if self.q_cell is None or self.q_cell.numel() < n_win * slots:
-            self.q_cell = torch.empty(n_win * slots, dtype=torch.int32, device=self.dev)
-            self.q_xyz = torch.empty((n_win * slots, 3), dtype=torch.float64, device=self.dev)
-            self.votes = torch.empty(n_win * slots, dtype=torch.int32, device=self.dev)
+            self.q_cell = D.empty(n_win * slots, D.i32, self.dev)
+            self.q_xyz = D.empty((n_win * slots, 3), D.f64, self.dev)
+            self.votes = D.empty(n_win * slots, D.i32, self.dev)
         self.q_slots = slots
         self._n_peaks_d = self.res32[:n_win, 1].contiguous()        # (a device-side copy: the counts of the batch as one array)
-        L.check(self.lib.sd_spinehead_queries(self.peaks.data_ptr(), self._n_peaks_d.data_ptr(), n_win, self.cap, slots, _f64x3(ds), self.q_cell.data_ptr(),
-                                              self.q_xyz.data_ptr(), self.stream), 'sd_spinehead_queries')
+        D.call('sd_spinehead_queries', self.dev, self.peaks, self._n_peaks_d, n_win, self.cap, slots, D.f64x3(ds), self.q_cell, self.q_xyz)
         n_pts = int(pts.shape[0])
-        tmp = torch.empty(int(self.lib.sd_syn_props_knn_temp_bytes(n_pts, n_win + 1)), dtype=torch.uint8, device=self.dev)
-        L.check(self.lib.sd_syn_props_knn(pts.data_ptr(), 0, self._begin_d.data_ptr(), n_win + 1, n_pts, lab.data_ptr(), self.q_cell.data_ptr(),
-                                          self.q_xyz.data_ptr(), n_win * slots, int(k), 3, self.votes.data_ptr(), None, None, self.knn_counts.data_ptr(),
-                                          tmp.data_ptr(), tmp.numel(), self.stream), 'sd_syn_props_knn')
+        tmp = D.scratch('sd_syn_props_knn_temp_bytes', self.dev, n_pts, n_win + 1)
+        D.call('sd_syn_props_knn', self.dev, pts, 0, self._begin_d, n_win + 1, n_pts, lab, self.q_cell, self.q_xyz, n_win * slots, int(k), 3,
+               self.votes, None, None, self.knn_counts, tmp, tmp.numel())
         self._knn_tmp = tmp
 
     def flood_select(self, w, c_rel, offset, scaling, objects=None):
+        from .. import _dev as D
         v = self.votes[w * self.q_slots:]                          # (a window with more peaks than max_peaks raises after the batch)
-        L.check(self.lib.sd_spinehead_markers(self.peaks[w].data_ptr(), self._res_ptr(w, 1), v.data_ptr(), self.q_slots, self.X, self.Y, self.Z,
-                                              self.markers.data_ptr(), self.stream), 'sd_spinehead_markers')
-        L.check(self.lib.sd_marker_flood(self.d2[w].data_ptr(), self.markers.data_ptr(), self.filled[w].data_ptr(), self.X, self.Y, self.Z,
-                                         self.flood.data_ptr(), self.max_label.data_ptr(), self.ws.data_ptr(), self.ws_bytes, self.stream), 'sd_marker_flood')
-        L.check(self.lib.sd_spinehead_select(self.flood.data_ptr(), self.X, self.Y, self.Z, _i64x3(c_rel), _i64x3(offset), _f64x3(scaling),
-                                             None if objects is None else objects.data_ptr(), self._res_ptr(w, 2), self.ws.data_ptr(),
-                                             self.ws_bytes, self.stream), 'sd_spinehead_select')
+        D.call('sd_spinehead_markers', self.dev, self.peaks[w], self.res32[w, 1:], v, self.q_slots, self.X, self.Y, self.Z, self.markers)
+        D.call('sd_marker_flood', self.dev, self.d2[w], self.markers, self.filled[w], self.X, self.Y, self.Z, self.flood, self.max_label,
+               self.ws, self.ws_bytes)
+        D.call('sd_spinehead_select', self.dev, self.flood, self.X, self.Y, self.Z, D.i64x3(c_rel), D.i64x3(offset), D.f64x3(scaling), objects,
+               self.res32[w, 2:], self.ws, self.ws_bytes)
 
     # -- one batch ----------------------------------------------------------------------------------------------------------------------
     def run_batch(self, seg_d, origin, offsets, tabs, sv_d, verts_d, labels_d, size, ds, k, c_rel, scaling, keep=None):
@@ -218,8 +196,7 @@ class WindowRunner:
         for w in range(n):
             if n_box[w] == 0:
                 continue
-            import torch
-            objects = torch.empty_like(self.flood) if keep is not None else None
+            objects = self.flood.new_empty(self.flood.shape) if keep is not None else None
             self.flood_select(w, c_rel[w], offsets[w], scaling, objects)
             if keep is not None:
                 keep[len(keep) - n + w].update(markers=self.markers.clone(), flood=self.flood.clone(), objects=objects)
@@ -259,8 +236,8 @@ def spinehead_windows(seg, sv_ids, rep_coords, verts_vox, vert_labels, scaling, 
     KnossosDataset is read region by region (``plan_regions``).  ValueError: a window whose filled mask is empty (the reference's
     message)."""
     import torch
-    from .find_object_properties import _cs_device
-    dev = _cs_device(device)
+    from .. import _dev as D
+    dev = D.device(device)
     sc, ds = check_scaling(scaling)
     ctx = np.array(ctx_vol)
     if ctx.shape != (3,) or ctx.dtype.kind not in 'iu' or np.any(ctx < 1):
@@ -277,11 +254,11 @@ def spinehead_windows(seg, sv_ids, rep_coords, verts_vox, vert_labels, scaling, 
     shape = [len(t) for t in tabs_h]
     if runner is None or [runner.X, runner.Y, runner.Z] != shape or runner.batch != int(batch) or runner.dev != dev:
         runner = WindowRunner(shape, batch, max_peaks, dev)
-    tabs = [torch.from_numpy(t).to(dev) for t in tabs_h]
-    sv_d = torch.from_numpy(sv.view(np.int64)).to(dev)
+    tabs = [D.up(t, dev) for t in tabs_h]
+    sv_d = D.up(sv, dev)
     verts_vox = np.asarray(verts_vox)
-    verts_d = torch.from_numpy(np.ascontiguousarray(verts_vox, dtype=np.float32 if verts_vox.dtype == np.float32 else np.float64).reshape(-1, 3)).to(dev)
-    labels_d = torch.from_numpy(np.ascontiguousarray(vert_labels, dtype=np.int32).reshape(-1)).to(dev)
+    verts_d = D.up(np.asarray(verts_vox, dtype=np.float32 if verts_vox.dtype == np.float32 else np.float64).reshape(-1, 3), dev)
+    labels_d = D.up(np.asarray(vert_labels, dtype=np.int32).reshape(-1), dev)
     offsets = np.maximum(rep - ctx, 0)                             # offset[offset < 0] = 0 (:2131-2132)
     c_rel = rep - offsets
     out = np.zeros((n, 6), np.int64)
@@ -300,7 +277,7 @@ def spinehead_windows(seg, sv_ids, rep_coords, verts_vox, vert_labels, scaling, 
     for ix, lo, hi in plan:
         if lo is not None:
             region = seg.load_seg(size=hi - lo, offset=lo, mag=1)  # (z, y, x), zeros outside the dataset
-            seg_d = torch.from_numpy(np.ascontiguousarray(region.swapaxes(2, 0)).astype(np.uint64, copy=False).view(np.int64)).to(dev)
+            seg_d = D.up(region.swapaxes(2, 0).astype(np.uint64, copy=False), dev)
             origin = lo
         out[ix] = runner.run_batch(seg_d, origin, offsets[ix], tabs, sv_d, verts_d, labels_d, size, ds.astype(np.float64), k, c_rel[ix],
                                    sc.astype(np.float64), keeps)

@@ -3,9 +3,8 @@ exec_init.py:299-367), the ``apply_ssv_size_threshold`` branch of ``run_create_n
 (/root/reference/syconn/proc/graphs.py:220-249) do with networkx, node by node, as one device call over tables in memory
 (``sd_svgraph_components``).  No CPU fallback; no edge-list files: edges arrive as an ``(e, 2)`` uint64 array."""
 import numpy as np
-import torch
 
-from .. import _lib as L
+from .. import _dev as D
 
 INT32_MAX = 2 ** 31 - 1
 
@@ -49,9 +48,8 @@ class SvTable:
             raise ValueError(f'{n} supervoxel ids, but {len(sizes)} sizes, {len(rep)} representative coordinates and {len(box_begin)} box offsets')
         if box_begin[0] != 0 or box_begin[-1] != len(boxes) or (np.diff(box_begin) < 0).any():
             raise ValueError('box_begin must ascend from 0 to the number of boxes')
-        up = lambda a: torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).to(device)
         self.n, self.n_boxes, self.ids_host, self.sizes_host = n, len(boxes), ids, sizes
-        self.ids, self.sizes, self.rep, self.box_begin, self.boxes = up(ids), up(sizes), up(rep), up(box_begin), up(boxes)
+        self.ids, self.sizes, self.rep, self.box_begin, self.boxes = (D.up(a, device) for a in (ids, sizes, rep, box_begin, boxes))
 
 
 class SvGraphComponents:
@@ -74,7 +72,6 @@ def svgraph_components(edges, sv_props, scaling, min_cc_size, strict: bool = Tru
     of all boxes of its supervoxels, in the reference's float64 arithmetic) and the filter: components with ``size <= min_cc_size``
     are dropped (``strict=False``: with ``size < min_cc_size``).  A component none of whose supervoxels is in the table raises
     ``ValueError`` as ``create_ccsize_dict`` does.  `sv_props`: a ``PropTable``."""
-    from ..extraction.find_object_properties import _cs_device
     what = 'svgraph_components'
     e = _u64(f'{what}: edges', edges, cols=2)
     scaling = np.ascontiguousarray(np.asarray(scaling, dtype=np.float64).reshape(-1))
@@ -82,29 +79,25 @@ def svgraph_components(edges, sv_props, scaling, min_cc_size, strict: bool = Tru
         raise ValueError(f'{what}: scaling must hold three positive numbers')
     if isinstance(min_cc_size, bool) or not np.isscalar(min_cc_size) or np.isnan(float(min_cc_size)):
         raise ValueError(f'{what}: min_cc_size must be a number, got {min_cc_size!r}')
-    lib, dev = L.load(), _cs_device(device)
+    dev = D.device(device)
     tab = sv_props if isinstance(sv_props, SvTable) else SvTable(sv_props, dev)
     n_e, m = len(e), tab.n + 2 * len(e)
-    u64 = lambda n: torch.empty(max(n, 1), dtype=torch.int64, device=dev)
-    e_d = torch.from_numpy(e.view(np.int64)).to(dev)
-    node_ids, node_comp, ssv_ids, sv_begin, sv_ids, edges_out = u64(m), u64(m), u64(m), u64(m + 1), u64(m), u64(2 * n_e)
-    node_size = torch.empty(max(m, 1), dtype=torch.float64, device=dev)
-    counts_d = torch.zeros(8, dtype=torch.int64, device=dev)
-    tmp = torch.empty(lib.sd_svgraph_components_temp_bytes(tab.n, n_e), dtype=torch.uint8, device=dev)
-    L.check(lib.sd_svgraph_components(e_d.data_ptr(), n_e, tab.ids.data_ptr(), tab.sizes.data_ptr(), tab.box_begin.data_ptr(), tab.boxes.data_ptr(), tab.n,
-                                      tab.n_boxes, scaling.ctypes.data_as(L.C.POINTER(L.C.c_double)), float(min_cc_size), int(bool(strict)),
-                                      node_ids.data_ptr(), node_comp.data_ptr(), node_size.data_ptr(), ssv_ids.data_ptr(), sv_begin.data_ptr(),
-                                      sv_ids.data_ptr(), edges_out.data_ptr(), counts_d.data_ptr(), tmp.data_ptr(), tmp.numel(),
-                                      torch.cuda.current_stream(dev).cuda_stream), 'sd_svgraph_components')
-    counts = counts_d.cpu().numpy()
+    e_d = D.up(e, dev)
+    node_ids, node_comp, ssv_ids, sv_begin, sv_ids, edges_out = (D.empty(k, D.i64, dev) for k in (m, m, m, m + 1, m, 2 * n_e))
+    node_size = D.empty(m, D.f64, dev)
+    counts_d = D.counters(dev)
+    tmp = D.scratch('sd_svgraph_components_temp_bytes', dev, tab.n, n_e)
+    D.call('sd_svgraph_components', dev, e_d, n_e, tab.ids, tab.sizes, tab.box_begin, tab.boxes, tab.n, tab.n_boxes, D.f64x3(scaling),
+           float(min_cc_size), int(bool(strict)), node_ids, node_comp, node_size, ssv_ids, sv_begin, sv_ids, edges_out, counts_d, tmp, tmp.numel())
+    counts = D.down(counts_d)
     if int(counts[7]):
         raise ValueError(f'{what}: the supervoxel table is inconsistent (ids or box offsets do not ascend)')
     if int(counts[6]):
         raise ValueError(f'Could not find a single bounding box for connected component with IDs: {{{int(counts.view(np.uint64)[5])}, ...}}.')
     n, n_cells, n_sv, n_kept = (int(counts[i]) for i in range(4))
-    host = lambda t, k: t[:k].cpu().numpy().view(np.uint64)
-    out = SvGraphComponents(node_ids=host(node_ids, n), node_comp=host(node_comp, n), node_size=node_size[:n].cpu().numpy(), ssv_ids=host(ssv_ids, n_cells),
-                            sv_begin=sv_begin[:n_cells + 1].cpu().numpy(), sv_ids=host(sv_ids, n_sv), edges=host(edges_out, 2 * n_kept).reshape(-1, 2),
+    host = lambda t, k: D.down(t, k, np.uint64)
+    out = SvGraphComponents(node_ids=host(node_ids, n), node_comp=host(node_comp, n), node_size=D.down(node_size, n), ssv_ids=host(ssv_ids, n_cells),
+                            sv_begin=D.down(sv_begin, n_cells + 1), sv_ids=host(sv_ids, n_sv), edges=host(edges_out, 2 * n_kept).reshape(-1, 2),
                             total_size=int(counts[4]))
     out.cc_sizes = out.node_size[np.searchsorted(out.node_ids, out.ssv_ids)] if n_cells else np.zeros(0, np.float64)
     return out

@@ -12,17 +12,17 @@ class Records:
 
     def __init__(self, device, fields, capacity: int, cursor):
         import torch
-        self.torch, self.device = torch, device
+        self.device, self.cursor = device, cursor
         self.fields = [(n, getattr(torch, dt), w) for n, dt, w in fields]
         self.capacity = int(capacity)
-        self.cursor = cursor
         self.arrays = {n: self._new(dt, w, self.capacity) for n, dt, w in self.fields}
 
     def _new(self, dtype, width, n):
-        return self.torch.empty((n, width) if width > 1 else (n,), dtype=dtype, device=self.device)
+        from .. import _dev as D
+        return D.empty((n, width) if width > 1 else n, dtype, self.device)
 
     def ptrs(self):
-        return [self.arrays[n].data_ptr() for n, _, _ in self.fields]
+        return [self.arrays[n] for n, _, _ in self.fields]
 
     def room_for(self, stored: int, n_more: int):
         """`stored` records are known to be in the arrays; make sure `n_more` further ones fit."""

@@ -110,14 +110,13 @@ class ChunkMerger:
 
     def __init__(self, names: Sequence[str], min_obj_vx: dict, device, n_chunks: int, capacity: int = 1 << 16):
         import torch
-        from .. import _lib as L
-        self.L, self.lib, self.torch = L, L.load(), torch
+        from .. import _dev as D
         self.device = torch.device(device)
         self.names = list(names)
         self.min_vx = {k: int(min_obj_vx.get(k, 1)) for k in ['sv'] + self.names}
         obj, pair = OBJECT_FIELDS, [('sub', 'int64', 1), ('cell', 'int64', 1), ('cnt', 'int64', 1)]
         n = len(self.names)
-        self.counters = torch.zeros(1 + 2 * n, dtype=torch.int64, device=self.device)          # cursors: cell, subs, pairs
+        self.counters = D.counters(self.device, 1 + 2 * n)                                      # cursors: cell, subs, pairs
         self.status = torch.zeros((max(int(n_chunks), 1), 2), dtype=torch.int32, device=self.device)      # overflow flags of every chunk's scan
         self.cell = Records(self.device, obj, capacity, self.counters[0:1])
         self.sub = [Records(self.device, obj, capacity, self.counters[1 + i:2 + i]) for i in range(n)]
@@ -136,9 +135,10 @@ class ChunkMerger:
         return self.status[self.n_chunks]
 
     def _post(self, k: int):
+        import torch
         r = k % (self.LAG + 1)
-        ev = self.torch.cuda.current_stream(self.device).record_event()
-        with self.torch.cuda.stream(self._side):
+        ev = torch.cuda.current_stream(self.device).record_event()
+        with torch.cuda.stream(self._side):
             self._side.wait_event(ev)
             self._host_counts[r].copy_(self.counters, non_blocking=True)
             self._host_status[r].copy_(self.status, non_blocking=True)
@@ -159,11 +159,10 @@ class ChunkMerger:
     def add_chunk(self, scan, origin):
         """`scan`: a ``DeviceScan`` after ``scan(cell, subs, status_out=self.status_slot())`` over one chunk whose (x, y, z) origin in
         the dataset is `origin`."""
-        lib, L = self.lib, self.L
-        k = self.n_chunks
+        from .. import _dev as D
+        k, dev = self.n_chunks, self.device
         X, Y, Z = scan.shape
         ox, oy, oz = (int(v) for v in origin)
-        stream = self.torch.cuda.current_stream(self.device).cuda_stream
         cap_o, cap_p = scan.cap_obj, scan.cap_pair
         upper_o, upper_p = min(cap_o, X * Y * Z), min(cap_p, X * Y * Z)
         self._read(k - self.LAG)
@@ -173,68 +172,58 @@ class ChunkMerger:
         def settle(rec, idx, upper):
             rec.room_for(int(self._known[idx]) + behind * upper, upper)
         settle(self.cell, 0, upper_o)
-        ids, rc, bb, sz = self.cell.ptrs()
-        L.check(lib.sd_chunkprops_append(scan.cell_table.data_ptr(), cap_o, X, Y, Z, ox, oy, oz, self.min_vx['sv'], ids, rc, bb, sz,
-                                         self.cell.capacity, self.cell.cursor.data_ptr(), stream), 'sd_chunkprops_append')
+        D.call('sd_chunkprops_append', dev, scan.cell_table, cap_o, X, Y, Z, ox, oy, oz, self.min_vx['sv'], *self.cell.ptrs(), self.cell.capacity,
+               self.cell.cursor)
         for i, name in enumerate(self.names):
             tab = scan.sub_tables[i]
             settle(self.sub[i], 1 + i, upper_o)
-            ids, rc, bb, sz = self.sub[i].ptrs()
-            L.check(lib.sd_chunkprops_append(tab.data_ptr(), cap_o, X, Y, Z, ox, oy, oz, self.min_vx[name], ids, rc, bb, sz,
-                                             self.sub[i].capacity, self.sub[i].cursor.data_ptr(), stream), 'sd_chunkprops_append')
+            D.call('sd_chunkprops_append', dev, tab, cap_o, X, Y, Z, ox, oy, oz, self.min_vx[name], *self.sub[i].ptrs(), self.sub[i].capacity,
+                   self.sub[i].cursor)
             settle(self.pairs[i], 1 + n + i, upper_p)
-            a, b, c = self.pairs[i].ptrs()
-            L.check(lib.sd_chunkpairs_append(scan.ptabs[i].data_ptr(), cap_p, tab.data_ptr(), scan.cell_table.data_ptr(), cap_o, X, Y, Z,
-                                             self.min_vx[name], a, b, c, self.pairs[i].capacity, self.pairs[i].cursor.data_ptr(), stream),
-                    'sd_chunkpairs_append')
+            D.call('sd_chunkpairs_append', dev, scan.ptabs[i], cap_p, tab, scan.cell_table, cap_o, X, Y, Z, self.min_vx[name],
+                   *self.pairs[i].ptrs(), self.pairs[i].capacity, self.pairs[i].cursor)
         self._post(k)
         self.n_chunks += 1
 
     # -- end of the dataset ------------------------------------------------------------------------------------------------------
     def _scratch(self, n: int):
         """One scratch buffer for all merges of `finish` (sized for the largest record count)."""
-        need = self.lib.sd_propmerge_temp_bytes(max(int(n), 1))
+        from .. import _dev as D, _lib as L
+        need = L.load().sd_propmerge_temp_bytes(max(int(n), 1))
         if getattr(self, '_tmp', None) is None or self._tmp.numel() < need:
-            self._tmp = self.torch.empty(need, dtype=self.torch.uint8, device=self.device)
+            self._tmp = D.empty(need, D.u8, self.device)
         return self._tmp
 
     def _merge_objects(self, rec: Records, n: int) -> PropTable:
-        torch, lib = self.torch, self.lib
+        from .. import _dev as D
         assert n <= rec.capacity, 'record arrays overran (internal error: capacity bound)'
         if n == 0:
             return PropTable(np.zeros(0, np.uint64), np.zeros(0, np.int64), np.zeros((0, 3), np.int64), np.zeros((0, 2, 3), np.int64),
                              np.zeros(1, np.int64))
-        dev, stream = self.device, torch.cuda.current_stream(self.device).cuda_stream
-        uniq = torch.empty(n, dtype=torch.int64, device=dev)
-        tot = torch.empty(n, dtype=torch.int64, device=dev)
-        rc = torch.empty((n, 3), dtype=torch.int32, device=dev)
-        beg = torch.empty(n, dtype=torch.int32, device=dev)
-        bbs = torch.empty((n, 6), dtype=torch.int32, device=dev)
-        cnt = torch.zeros(1, dtype=torch.int64, device=dev)
+        dev = self.device
+        uniq, tot, rc = D.empty(n, D.i64, dev), D.empty(n, D.i64, dev), D.empty((n, 3), D.i32, dev)
+        beg, bbs = D.empty(n, D.i32, dev), D.empty((n, 6), D.i32, dev)
+        cnt = D.counters(dev, 1)
         tmp = self._scratch(n)
         a = rec.arrays
-        self.L.check(lib.sd_propmerge_objects(a['ids'].data_ptr(), a['sizes'].data_ptr(), a['rc'].data_ptr(), a['bb'].data_ptr(), n,
-                                              uniq.data_ptr(), tot.data_ptr(), rc.data_ptr(), beg.data_ptr(), bbs.data_ptr(),
-                                              cnt.data_ptr(), tmp.data_ptr(), tmp.numel(), stream), 'sd_propmerge_objects')
+        D.call('sd_propmerge_objects', dev, a['ids'], a['sizes'], a['rc'], a['bb'], n, uniq, tot, rc, beg, bbs, cnt, tmp, tmp.numel())
         u = int(cnt.item())
-        return PropTable(uniq[:u].cpu().numpy().view(np.uint64), tot[:u].cpu().numpy(), rc[:u].cpu().numpy().astype(np.int64),
-                         bbs.cpu().numpy().astype(np.int64).reshape(n, 2, 3), segment_offsets(beg, u, n))
+        return PropTable(D.down(uniq, u, np.uint64), D.down(tot, u), D.down(rc, u).astype(np.int64),
+                         D.down(bbs).astype(np.int64).reshape(n, 2, 3), segment_offsets(beg, u, n))
 
     def _merge_pairs(self, rec: Records, n: int) -> MapTable:
-        torch, lib = self.torch, self.lib
+        from .. import _dev as D
         assert n <= rec.capacity, 'record arrays overran (internal error: capacity bound)'
         if n == 0:
             return MapTable(np.zeros(0, np.uint64), np.zeros(0, np.uint64), np.zeros(0, np.int64))
-        dev, stream = self.device, torch.cuda.current_stream(self.device).cuda_stream
-        o_s, o_c, o_n = (torch.empty(n, dtype=torch.int64, device=dev) for _ in range(3))
-        cnt = torch.zeros(1, dtype=torch.int64, device=dev)
+        dev = self.device
+        o_s, o_c, o_n = (D.empty(n, D.i64, dev) for _ in range(3))
+        cnt = D.counters(dev, 1)
         tmp = self._scratch(n)
         a = rec.arrays
-        self.L.check(lib.sd_propmerge_pairs(a['sub'].data_ptr(), a['cell'].data_ptr(), a['cnt'].data_ptr(), n, o_s.data_ptr(),
-                                            o_c.data_ptr(), o_n.data_ptr(), cnt.data_ptr(), tmp.data_ptr(), tmp.numel(), stream),
-                     'sd_propmerge_pairs')
+        D.call('sd_propmerge_pairs', dev, a['sub'], a['cell'], a['cnt'], n, o_s, o_c, o_n, cnt, tmp, tmp.numel())
         u = int(cnt.item())
-        return MapTable(o_s[:u].cpu().numpy().view(np.uint64), o_c[:u].cpu().numpy().view(np.uint64), o_n[:u].cpu().numpy())
+        return MapTable(D.down(o_s, u, np.uint64), D.down(o_c, u, np.uint64), D.down(o_n, u))
 
     def finish(self):
         """-> (cell PropTable, {name: PropTable}, {name: MapTable})"""

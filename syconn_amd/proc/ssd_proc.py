@@ -12,20 +12,9 @@ supervoxel id of the list, :87); the order inside a list is kept, and it decides
 from typing import Dict, Optional, Sequence
 
 import numpy as np
-import torch
 
-from .. import _lib as L
+from .. import _dev as D
 from .graphs import SvTable, _u64
-
-
-def _device(device):
-    from ..extraction.find_object_properties import _cs_device
-    return _cs_device(device)
-
-
-def _up(a, dev):
-    a = np.ascontiguousarray(a)
-    return torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).to(dev)
 
 
 class CellLists:
@@ -95,23 +84,20 @@ def cell_properties(cells: CellLists, sv_props, allow_missing: bool = False, dev
     max of the upper corners (``calculate_bounding_box``, :1154-1168), ``rep_coord`` = that of the first supervoxel in the cell's
     order (:713-727).  A supervoxel that is not in `sv_props` (a ``PropTable``) raises ``ValueError`` unless `allow_missing`: then it
     contributes nothing, and a cell without any known supervoxel gets size 0 and the zero box."""
-    lib, dev = L.load(), _device(device)
+    dev = D.device(device)
     tab = sv_props if isinstance(sv_props, SvTable) else SvTable(sv_props, dev)
     n = len(cells)
-    size = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
-    box = torch.empty((max(n, 1), 6), dtype=torch.int32, device=dev)
-    rep = torch.empty((max(n, 1), 3), dtype=torch.int32, device=dev)
-    counts_d = torch.zeros(8, dtype=torch.int64, device=dev)
-    sb, sv = _up(cells.sv_begin, dev), _up(cells.sv_ids, dev)
-    L.check(lib.sd_cell_props(sb.data_ptr(), sv.data_ptr(), n, len(cells.sv_ids), tab.ids.data_ptr(), tab.sizes.data_ptr(), tab.rep.data_ptr(),
-                              tab.box_begin.data_ptr(), tab.boxes.data_ptr(), tab.n, tab.n_boxes, size.data_ptr(), box.data_ptr(), rep.data_ptr(),
-                              counts_d.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), 'sd_cell_props')
-    counts = counts_d.cpu().numpy()
+    size, box, rep = D.empty(n, D.i64, dev), D.empty((n, 6), D.i32, dev), D.empty((n, 3), D.i32, dev)
+    counts_d = D.counters(dev)
+    sb, sv = D.up(cells.sv_begin, dev), D.up(cells.sv_ids, dev)
+    D.call('sd_cell_props', dev, sb, sv, n, len(cells.sv_ids), tab.ids, tab.sizes, tab.rep, tab.box_begin, tab.boxes, tab.n, tab.n_boxes, size, box,
+           rep, counts_d)
+    counts = D.down(counts_d)
     if int(counts[7]):
         raise ValueError('cell_properties: the cell lists or the supervoxel table are inconsistent')
     if int(counts[0]) and not allow_missing:
         raise ValueError(f'cell_properties: {int(counts[0])} supervoxels are not in the table, e.g. {int(counts.view(np.uint64)[5])}')
-    return CellProps(size[:n].cpu().numpy(), box[:n].cpu().numpy().reshape(n, 2, 3), rep[:n].cpu().numpy())
+    return CellProps(D.down(size, n), D.down(box, n).reshape(n, 2, 3), D.down(rep, n))
 
 
 class CellMapping:
@@ -156,7 +142,7 @@ def map_organelle(cells: CellLists, map_table, organelle_props, lower_ratio: flo
     """``sd_cell_mapping`` for one organelle kind: `map_table` a ``MapTable`` (organelle id, supervoxel id, voxels), `organelle_props` its
     ``PropTable`` (ids ascending, sizes).  See ``CellMapping``."""
     what = 'map_organelle'
-    lib, dev = L.load(), _device(device)
+    dev = D.device(device)
     sub, sv = _u64(f'{what}: organelle ids of the records', map_table.sub_ids), _u64(f'{what}: supervoxel ids of the records', map_table.cell_ids)
     cnt = np.ascontiguousarray(np.asarray(map_table.counts).reshape(-1), dtype=np.int64)
     org_ids = _u64(f'{what}: organelle ids', organelle_props.ids)
@@ -171,31 +157,27 @@ def map_organelle(cells: CellLists, map_table, organelle_props, lower_ratio: flo
         if np.isnan(float(v)):
             raise ValueError(f'{what}: {name} is NaN')
     r, o, n, s = len(sub), len(org_ids), len(cells), len(cells.sv_ids)
-    i64 = lambda k: torch.empty(max(k, 1), dtype=torch.int64, device=dev)
-    cell_begin, pair_org, acc_begin, acc_org = i64(n + 1), i64(r), i64(n + 1), i64(r)
-    ratio = torch.empty(max(r, 1), dtype=torch.float64, device=dev)
-    accepted = torch.empty(max(r, 1), dtype=torch.uint8, device=dev)
-    org_n, org_first = (torch.empty(max(o, 1), dtype=torch.int32, device=dev) for _ in range(2))
-    counts_d = torch.zeros(8, dtype=torch.int64, device=dev)
-    tmp = torch.empty(max(lib.sd_cell_mapping_temp_bytes(r, s), 1), dtype=torch.uint8, device=dev)
-    d = [_up(a, dev) for a in (sub, sv, cnt, org_ids, org_sizes, cells.sv_begin, cells.sv_ids)]
-    L.check(lib.sd_cell_mapping(d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), r, d[3].data_ptr(), d[4].data_ptr(), o, d[5].data_ptr(), d[6].data_ptr(), n, s,
-                                float(lower_ratio), float(upper_ratio), float(sizethreshold), cell_begin.data_ptr(), pair_org.data_ptr(), ratio.data_ptr(),
-                                accepted.data_ptr(), acc_begin.data_ptr(), acc_org.data_ptr(), org_n.data_ptr(), org_first.data_ptr(), counts_d.data_ptr(),
-                                tmp.data_ptr(), tmp.numel(), torch.cuda.current_stream(dev).cuda_stream), 'sd_cell_mapping')
-    counts = counts_d.cpu().numpy()
+    cell_begin, pair_org, acc_begin, acc_org = (D.empty(k, D.i64, dev) for k in (n + 1, r, n + 1, r))
+    ratio, accepted = D.empty(r, D.f64, dev), D.empty(r, D.u8, dev)
+    org_n, org_first = D.empty(o, D.i32, dev), D.empty(o, D.i32, dev)
+    counts_d = D.counters(dev)
+    tmp = D.scratch('sd_cell_mapping_temp_bytes', dev, r, s)
+    d = [D.up(a, dev) for a in (sub, sv, cnt, org_ids, org_sizes, cells.sv_begin, cells.sv_ids)]
+    D.call('sd_cell_mapping', dev, d[0], d[1], d[2], r, d[3], d[4], o, d[5], d[6], n, s, float(lower_ratio), float(upper_ratio), float(sizethreshold),
+           cell_begin, pair_org, ratio, accepted, acc_begin, acc_org, org_n, org_first, counts_d, tmp, tmp.numel())
+    counts = D.down(counts_d)
     if int(counts[6]):
         raise ValueError(f'{what}: a supervoxel is in two cells, or 0 is in one')
     if int(counts[7]):
         raise ValueError(f'{what}: the cell lists or the organelle table are inconsistent')
     n_pairs, n_acc = int(counts[1]), int(counts[2])
-    first = org_first[:o].cpu().numpy().view(np.uint32)
+    first = D.down(org_first, o, np.uint32)
     first_id = np.zeros(o, np.uint64)
     has = first != 0xffffffff
     first_id[has] = cells.ssv_ids[first[has]]
-    return CellMapping(ssv_ids=cells.ssv_ids, org_ids=org_ids, cell_begin=cell_begin[:n + 1].cpu().numpy(), ids=pair_org[:n_pairs].cpu().numpy().view(np.uint64),
-                       ratios=ratio[:n_pairs].cpu().numpy(), accepted=accepted[:n_pairs].cpu().numpy().astype(bool), acc_begin=acc_begin[:n + 1].cpu().numpy(),
-                       acc_ids=acc_org[:n_acc].cpu().numpy().view(np.uint64), org_n_cells=org_n[:o].cpu().numpy().view(np.uint32).astype(np.int64),
+    return CellMapping(ssv_ids=cells.ssv_ids, org_ids=org_ids, cell_begin=D.down(cell_begin, n + 1), ids=D.down(pair_org, n_pairs, np.uint64),
+                       ratios=D.down(ratio, n_pairs), accepted=D.down(accepted, n_pairs).astype(bool), acc_begin=D.down(acc_begin, n + 1),
+                       acc_ids=D.down(acc_org, n_acc, np.uint64), org_n_cells=D.down(org_n, o, np.uint32).astype(np.int64),
                        org_first_cell=first_id, n_records=int(counts[0]))
 
 
@@ -246,16 +228,14 @@ def map_synssv_objects(cells: CellLists, neuron_partners, syn_prob, syn_ids, syn
     if not (len(partners) == len(ids) == len(prob)):
         raise ValueError(f'{what}: {len(partners)} partner rows, {len(ids)} ids, {len(prob)} probabilities')
     keep = np.ascontiguousarray(prob > syn_threshold, dtype=np.uint8)
-    lib, dev = L.load(), _device(device)
+    dev = D.device(device)
     n, n_cells = len(ids), len(cells)
-    begin = torch.empty(n_cells + 1, dtype=torch.int64, device=dev)
-    out = torch.empty(max(2 * n, 1), dtype=torch.int64, device=dev)
-    counts_d = torch.zeros(8, dtype=torch.int64, device=dev)
-    tmp = torch.empty(lib.sd_cell_synapses_temp_bytes(n), dtype=torch.uint8, device=dev)
-    d = [_up(a, dev) for a in (partners, keep, ids, cells.ssv_ids)]
-    L.check(lib.sd_cell_synapses(d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), n, d[3].data_ptr(), n_cells, begin.data_ptr(), out.data_ptr(),
-                                 counts_d.data_ptr(), tmp.data_ptr(), tmp.numel(), torch.cuda.current_stream(dev).cuda_stream), 'sd_cell_synapses')
-    counts = counts_d.cpu().numpy()
+    begin, out = D.empty(n_cells + 1, D.i64, dev), D.empty(2 * n, D.i64, dev)
+    counts_d = D.counters(dev)
+    tmp = D.scratch('sd_cell_synapses_temp_bytes', dev, n)
+    d = [D.up(a, dev) for a in (partners, keep, ids, cells.ssv_ids)]
+    D.call('sd_cell_synapses', dev, d[0], d[1], d[2], n, d[3], n_cells, begin, out, counts_d, tmp, tmp.numel())
+    counts = D.down(counts_d)
     if int(counts[7]):
         raise ValueError(f'{what}: the cell ids do not ascend')
-    return CellSynapses(begin.cpu().numpy(), out[:int(counts[0])].cpu().numpy().view(np.uint64))
+    return CellSynapses(D.down(begin), D.down(out, int(counts[0]), np.uint64))

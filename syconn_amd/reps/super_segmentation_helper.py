@@ -11,6 +11,7 @@ import os
 import numpy as np
 import torch
 
+from .. import _dev as D
 from .. import _lib as L
 from .. import global_params
 from ..handler.basics import kd_factory
@@ -22,17 +23,16 @@ def box_majority_device(vol: torch.Tensor, origins_zyx: torch.Tensor, edge_zyx, 
                         thresh_majority: float) -> torch.Tensor:
     """out[i] = (count(vol[box_i] > thresh_proba) / prod(edge) > thresh_majority) on the device; boxes may leave the
     volume (zeros outside).  vol: (D,H,W) uint8, origins_zyx: (n,3) int32, both on the same ROCm device."""
-    lib = L.load()
+    L.load()                                   # (a library that was not built is reported first)
     if not (vol.is_cuda and origins_zyx.is_cuda):
         raise RuntimeError('box_majority_device needs device tensors (there is no CPU fallback)')
     assert vol.dtype == torch.uint8 and vol.dim() == 3 and vol.is_contiguous()
     origins_zyx = origins_zyx.to(torch.int32).contiguous()
     n = int(origins_zyx.shape[0])
     out = torch.empty((n,), dtype=torch.uint8, device=vol.device)
-    D, H, W = (int(v) for v in vol.shape)
-    L.check(lib.sd_box_majority(vol.data_ptr(), D, H, W, origins_zyx.data_ptr(), n, int(edge_zyx[0]), int(edge_zyx[1]),
-                                int(edge_zyx[2]), float(thresh_proba), float(thresh_majority), out.data_ptr(),
-                                torch.cuda.current_stream().cuda_stream), 'sd_box_majority')
+    # (dev None: the current stream of the current device)
+    D.call('sd_box_majority', None, vol, *(int(v) for v in vol.shape), origins_zyx, n, int(edge_zyx[0]), int(edge_zyx[1]), int(edge_zyx[2]),
+           float(thresh_proba), float(thresh_majority), out)
     return out
 
 
@@ -63,8 +63,8 @@ def map_myelin2coords(coords: np.ndarray, cube_edge_avg: np.ndarray = np.array([
         lo = off[ix].min(axis=0)
         hi = off[ix].max(axis=0) + edge
         vol = kd.load_raw(size=(hi - lo) * mag, offset=lo * mag, mag=mag)              # (z,y,x) uint8, zeros outside
-        vol_dev = torch.from_numpy(np.ascontiguousarray(vol)).to(dev)
-        org = torch.from_numpy(np.ascontiguousarray((off[ix] - lo)[:, ::-1]).astype(np.int32)).to(dev)
+        vol_dev = D.up(vol, dev)
+        org = D.up((off[ix] - lo)[:, ::-1].astype(np.int32), dev)
         res = box_majority_device(vol_dev, org, edge[::-1], thresh_proba, thresh_majority)
         preds[ix] = res.cpu().numpy()
     return preds
@@ -161,7 +161,7 @@ def skeleton_edge_weights(nodes, node_begin, edges, edge_begin, scaling) -> np.n
 
 
 def _skel_counts(name, counts_d):
-    counts = counts_d.cpu().numpy()
+    counts = D.down(counts_d)
     if int(counts[7]):
         raise RuntimeError(f'{name}: an offset, an edge or a weight was out of range')
     return counts
@@ -199,31 +199,24 @@ def skeleton_majority_vote(nodes, node_begin, edges, edge_begin, labels, scaling
     if n == 0:
         out = [lab.copy(), np.zeros(0, np.uint32), dict(sources_redone=0, steps_lds=0, steps_redo=0)]
         return out[0] if not (return_reached or return_counts) else tuple(o for o, f in zip(out, (True, return_reached, return_counts)) if f)
-    from ..extraction.find_object_properties import _cs_device
-    lib, dev = L.load(), _cs_device(device)
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    dev = D.device(device)
     n_cells, n_e = len(node_begin) - 1, len(e)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    nb_d, eb_d, e_d, w_d, cls_d = up(node_begin), up(edge_begin), up(e), up(weights), up(classes)
-    adj_begin = torch.empty(n + 1, dtype=torch.int64, device=dev)
-    adj_nbr = torch.empty(max(2 * n_e, 1), dtype=torch.int32, device=dev)
-    adj_w = torch.empty(max(2 * n_e, 1), dtype=torch.float64, device=dev)
-    counts_d = torch.zeros(8, dtype=torch.int64, device=dev)
-    tmp = torch.empty(lib.sd_skel_csr_temp_bytes(n_e), dtype=torch.uint8, device=dev)
-    L.check(lib.sd_skel_csr(e_d.data_ptr(), eb_d.data_ptr(), nb_d.data_ptr(), n_cells, n, n_e, w_d.data_ptr(), adj_begin.data_ptr(), adj_nbr.data_ptr(),
-                            adj_w.data_ptr(), counts_d.data_ptr(), tmp.data_ptr(), tmp.numel(), stream), 'sd_skel_csr')
+    nb_d, eb_d, e_d, w_d, cls_d = (D.up(a, dev) for a in (node_begin, edge_begin, e, weights, classes))
+    adj_begin, adj_nbr, adj_w = D.empty(n + 1, D.i64, dev), D.empty(2 * n_e, D.i32, dev), D.empty(2 * n_e, D.f64, dev)
+    counts_d = D.counters(dev)
+    tmp = D.scratch('sd_skel_csr_temp_bytes', dev, n_e)
+    D.call('sd_skel_csr', dev, e_d, eb_d, nb_d, n_cells, n, n_e, w_d, adj_begin, adj_nbr, adj_w, counts_d, tmp, tmp.numel())
     _skel_counts('sd_skel_csr', counts_d)
     max_cell = int(np.diff(node_begin).max())
-    vote_d = torch.empty(n, dtype=torch.uint8, device=dev)
-    reached_d = torch.empty(n, dtype=torch.int32, device=dev) if return_reached else None
-    tmp = torch.empty(lib.sd_skel_vote_temp_bytes(n, max_cell), dtype=torch.uint8, device=dev)
-    L.check(lib.sd_skel_vote(adj_begin.data_ptr(), adj_nbr.data_ptr(), adj_w.data_ptr(), 2 * n_e, nb_d.data_ptr(), n_cells, n, max_cell, cls_d.data_ptr(),
-                             len(values), float(max_dist), vote_d.data_ptr(), None if reached_d is None else reached_d.data_ptr(), counts_d.data_ptr(),
-                             tmp.data_ptr(), tmp.numel(), stream), 'sd_skel_vote')
+    vote_d = D.empty(n, D.u8, dev)
+    reached_d = D.empty(n, D.i32, dev) if return_reached else None
+    tmp = D.scratch('sd_skel_vote_temp_bytes', dev, n, max_cell)
+    D.call('sd_skel_vote', dev, adj_begin, adj_nbr, adj_w, 2 * n_e, nb_d, n_cells, n, max_cell, cls_d, len(values), float(max_dist), vote_d,
+           reached_d, counts_d, tmp, tmp.numel())
     counts = _skel_counts('sd_skel_vote', counts_d)
-    out = [values[vote_d.cpu().numpy()].astype(lab.dtype, copy=False)]
+    out = [values[D.down(vote_d)].astype(lab.dtype, copy=False)]
     if return_reached:
-        out.append(reached_d.cpu().numpy().view(np.uint32))
+        out.append(D.down(reached_d, view=np.uint32))
     if return_counts:
         out.append(dict(sources_redone=int(counts[0]), steps_lds=int(counts[1]), steps_redo=int(counts[2])))
     return out[0] if len(out) == 1 else tuple(out)
@@ -242,20 +235,17 @@ def skeleton_compartment_majority(node_begin, edges, edge_begin, labels, soma_la
     if n == 0:
         return lab.copy()
     find = lambda x: int(np.searchsorted(values, x)) if x in values else -1
-    from ..extraction.find_object_properties import _cs_device
-    lib, dev = L.load(), _cs_device(device)
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    nb_d, eb_d, e_d, cls_d = up(node_begin), up(edge_begin), up(e), up(classes)
-    out_d = torch.empty(n, dtype=torch.uint8, device=dev)
-    counts_d = torch.zeros(8, dtype=torch.int64, device=dev)
-    tmp = torch.empty(lib.sd_skel_components_temp_bytes(n), dtype=torch.uint8, device=dev)
-    L.check(lib.sd_skel_components(e_d.data_ptr(), eb_d.data_ptr(), nb_d.data_ptr(), len(node_begin) - 1, n, len(e), cls_d.data_ptr(), find(soma_label),
-                                   find(1), max(find(0), 0), out_d.data_ptr(), counts_d.data_ptr(), tmp.data_ptr(), tmp.numel(),
-                                   torch.cuda.current_stream(dev).cuda_stream), 'sd_skel_components')
+    dev = D.device(device)
+    nb_d, eb_d, e_d, cls_d = (D.up(a, dev) for a in (node_begin, edge_begin, e, classes))
+    out_d = D.empty(n, D.u8, dev)
+    counts_d = D.counters(dev)
+    tmp = D.scratch('sd_skel_components_temp_bytes', dev, n)
+    D.call('sd_skel_components', dev, e_d, eb_d, nb_d, len(node_begin) - 1, n, len(e), cls_d, find(soma_label), find(1), max(find(0), 0), out_d,
+           counts_d, tmp, tmp.numel())
     counts = _skel_counts('sd_skel_components', counts_d)
     if int(counts[6]):
         raise ValueError(f'{what}: a component of 2^24 nodes or more: the share of label 1 is not pinned there')
-    return values[out_d.cpu().numpy()].astype(lab.dtype, copy=False)
+    return values[D.down(out_d)].astype(lab.dtype, copy=False)
 
 
 def majorityvote_skeleton_property(sso, prop_key: str, max_dist: int = 10000, return_res: bool = False):
