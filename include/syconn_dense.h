@@ -778,6 +778,50 @@ size_t sd_cell_synapses_temp_bytes(size_t n_syn);
 int sd_cell_synapses(const uint64_t* partners_dev, const uint8_t* keep_dev, const uint64_t* syn_ids_dev, size_t n_syn, const uint64_t* ssv_ids_dev,
                      size_t n_cells, uint64_t* syn_begin_dev, uint64_t* out_ids_dev, uint64_t* counts_dev, void* temp_dev, size_t temp_bytes, void* stream);
 
+/* ---- surface meshes of labelled objects (csrc/sd_mesh.hip) -----------------------------------------------------------------
+ * The meshing of the reference's find_meshes (proc/meshes.py:937-994) for ALL non-zero labels of a chunk in one pass, and the merge of
+ * per-chunk meshes with the mesh_bb / mesh_area of proc/sd_proc.py:951-975 (merge_meshes_incl_norm, proc/meshes.py:483-519).  The
+ * surface is the UNSIMPLIFIED marching-cubes surface of every "label == id" volume over the triangle table of csrc/sd_mc_table.h
+ * (tools/gen_mc_table.py states the rule it is derived from); no normals.
+ * Input: labels_dev uint64 [X][Y][Z] and three int32 source-index tables tx_dev[NX], ty_dev[NY], tz_dev[NZ] that combine the
+ * reference's zoom (order 0) and edge pad: padded[i, j, k] = labels[tx[i], ty[j], tz[k]], an entry -1 reads as label 0 (scipy's
+ * constant).  No zoomed or padded copy is made.  ids_dev uint64[n_ids] strictly ascending, without 0: the objects, in output order (the
+ * caller has them from the label statistics; a label of the volume that is not listed has no mesh and raises counts[6]).
+ * Output, a CSR by object: vert_begin_dev / tri_begin_dev uint64[n_ids + 1]; verts_dev float32[vert_cap][3] in nm; tris_dev
+ * uint32[tri_cap][3], indices local to the object; mesh_bb_dev float32[n_ids][2][3] (min | max of the vertices, zeros without any);
+ * area_dev double[n_ids] in um^2 = (sum over triangles of |cross(v0 - v1, v0 - v2)|) / 2 / 1e6 in float64 over the float32 vertices.
+ * Order (part of the contract): one vertex per grid edge of the padded array whose two voxels differ in membership, ascending by the
+ * key ((x NY + y) NZ + z) * 3 + axis of the edge's lower voxel; triangles ascending by cube (x, y, z) in C order, then in table order,
+ * their three indices in the table's order.  Coordinates: v = float32(max(0, g * scale + offset)) per axis in float64, every product and
+ * sum rounded on its own, g the half-integer grid position in the padded array (voxel i at coordinate i); scale_xyz / offset_xyz
+ * HOST double[3] = scaling * ds and offset_vox * scaling - pad * scaling * ds.
+ * counts_dev uint64[8], zeroed by every call: [0] vertices, [1] triangles of the volume (sd_mesh_count: what sd_mesh_build needs as
+ * capacities), [2] != 0: a capacity was smaller and records were lost (nothing is written past a capacity; the outputs are then
+ * unusable), [5] != 0: a triangle without its vertex (only after [2]), [6] != 0: a label outside ids_dev, [7] != 0: a table entry
+ * outside [-1, extent) or ids not strictly ascending.  The padded volume holds at most 2^31 voxels and every count per call stays
+ * below 2^31 (SD_ERR_INVALID beyond).  Asynchronous on the stream; no float atomics; integer atomics only count.
+ *   sd_mesh_merge   pieces = the objects of several such tables, concatenated in the order of the tables: piece_ids_dev uint64[n_pieces]
+ *                   (any order, repeats = one object in several chunks), piece_vert_begin_dev / piece_tri_begin_dev uint64[n_pieces + 1]
+ *                   into verts_dev / tris_dev.  One stable sort by id, one scan, one gather: obj_ids_dev uint64[n_pieces] ascending
+ *                   (counts[0] objects), vert_begin_dev / tri_begin_dev [n_pieces + 1], the pieces of an object one after another in
+ *                   input order with their indices shifted (seam vertices stay twice, as in the reference), mesh_bb_dev / area_dev
+ *                   [n_pieces] recomputed.  counts[7] != 0: an offset table does not ascend from 0 to its total.
+ * One grid stride of every kernel is SD_MESH_GRID blocks of 256 threads (voxel kernels: 256 voxels per block and step; per-object
+ * kernel: 4 objects per block and step). */
+#define SD_MESH_GRID 256
+int sd_mesh_count(const uint64_t* labels_dev, int X, int Y, int Z, const int32_t* tx_dev, const int32_t* ty_dev, const int32_t* tz_dev, int NX, int NY,
+                  int NZ, const uint64_t* ids_dev, size_t n_ids, uint64_t* counts_dev, void* stream);
+size_t sd_mesh_build_temp_bytes(int NX, int NY, int NZ, size_t vert_cap, size_t tri_cap);
+int sd_mesh_build(const uint64_t* labels_dev, int X, int Y, int Z, const int32_t* tx_dev, const int32_t* ty_dev, const int32_t* tz_dev, int NX, int NY,
+                  int NZ, const uint64_t* ids_dev, size_t n_ids, const double* scale_xyz, const double* offset_xyz, size_t vert_cap, size_t tri_cap,
+                  uint64_t* vert_begin_dev, uint64_t* tri_begin_dev, float* verts_dev, uint32_t* tris_dev, float* mesh_bb_dev, double* area_dev,
+                  uint64_t* counts_dev, void* temp_dev, size_t temp_bytes, void* stream);
+size_t sd_mesh_merge_temp_bytes(size_t n_pieces);
+int sd_mesh_merge(const uint64_t* piece_ids_dev, const uint64_t* piece_vert_begin_dev, const uint64_t* piece_tri_begin_dev, size_t n_pieces,
+                  const float* verts_dev, size_t n_verts, const uint32_t* tris_dev, size_t n_tris, uint64_t* obj_ids_dev, uint64_t* vert_begin_dev,
+                  uint64_t* tri_begin_dev, float* verts_out_dev, uint32_t* tris_out_dev, float* mesh_bb_dev, double* area_dev, uint64_t* counts_dev,
+                  void* temp_dev, size_t temp_bytes, void* stream);
+
 /* ---- host-side helpers of the chunk pipeline (no GPU) -----------------------------------------------------------------
  * Multi-threaded strided copy of an (nz, ny, nx)-byte box between two uint8 host arrays whose x-rows are contiguous
  * (strides in bytes), and a multi-threaded memset: what numpy slicing does on one core when the reference cuts a chunk

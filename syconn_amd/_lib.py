@@ -18,6 +18,7 @@ SD_SPINEHEAD_VOX_GRID, SD_SPINEHEAD_VERT_GRID, SD_SPINEHEAD_ID_GRID = 8192, 1024
 SD_SYN_PROPS_MAX_K, SD_SYN_PROPS_CELL_GRID, SD_SYN_PROPS_POINT_GRID, SD_SYN_PROPS_QUERY_GRID, SD_SYN_PROPS_FOREST_GRID = 64, 4096, 1024, 8192, 1024
 SD_SKEL_MAX_CLASSES, SD_SKEL_LDS_NODES, SD_SKEL_VOTE_GRID, SD_SKEL_NODE_GRID, SD_SKEL_EDGE_GRID, SD_SKEL_REDO_GRID, SD_SKEL_REDO_BYTES = 64, 512, 2048, 1024, 1024, 1024, 1 << 28
 SD_CELLASM_GRID = 1024
+SD_MESH_GRID = 256
 
 LIB_NAME = 'libsyconn_dense_hip.so'
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), os.environ.get('SD_LIB_NAME', LIB_NAME))
@@ -42,7 +43,8 @@ EXPORTS = ['sd_init', 'sd_device_count', 'sd_model_create', 'sd_model_destroy', 
            'sd_spinehead_box_vertices', 'sd_spinehead_queries', 'sd_spinehead_markers', 'sd_spinehead_select', 'sd_skel_csr_temp_bytes', 'sd_skel_csr',
            'sd_skel_vote_temp_bytes', 'sd_skel_vote', 'sd_skel_components_temp_bytes', 'sd_skel_components',
            'sd_svgraph_components_temp_bytes', 'sd_svgraph_components', 'sd_cell_props', 'sd_cell_mapping_temp_bytes', 'sd_cell_mapping',
-           'sd_cell_synapses_temp_bytes', 'sd_cell_synapses']
+           'sd_cell_synapses_temp_bytes', 'sd_cell_synapses', 'sd_mesh_count', 'sd_mesh_build_temp_bytes', 'sd_mesh_build',
+           'sd_mesh_merge_temp_bytes', 'sd_mesh_merge']
 
 
 class OpDesc(C.Structure):
@@ -218,6 +220,13 @@ def load():
     lib.sd_cell_mapping.argtypes = [vp, vp, vp, sz, vp, vp, sz, vp, vp, sz, sz, f64, f64, f64] + [vp] * 9 + [vp, sz, vp]; lib.sd_cell_mapping.restype = i32
     lib.sd_cell_synapses_temp_bytes.argtypes = [sz]; lib.sd_cell_synapses_temp_bytes.restype = sz
     lib.sd_cell_synapses.argtypes = [vp, vp, vp, sz, vp, sz, vp, vp, vp, vp, sz, vp]; lib.sd_cell_synapses.restype = i32
+    # proc/meshes.py:937-994 (find_meshes, all labels of a chunk in one pass) and proc/sd_proc.py:951-975 (merge, mesh_bb, mesh_area)
+    lib.sd_mesh_count.argtypes = [vp, i32, i32, i32, vp, vp, vp, i32, i32, i32, vp, sz, vp, vp]; lib.sd_mesh_count.restype = i32
+    lib.sd_mesh_build_temp_bytes.argtypes = [i32, i32, i32, sz, sz]; lib.sd_mesh_build_temp_bytes.restype = sz
+    lib.sd_mesh_build.argtypes = [vp, i32, i32, i32, vp, vp, vp, i32, i32, i32, vp, sz, f64p, f64p, sz, sz] + [vp] * 7 + [vp, sz, vp]
+    lib.sd_mesh_build.restype = i32
+    lib.sd_mesh_merge_temp_bytes.argtypes = [sz]; lib.sd_mesh_merge_temp_bytes.restype = sz
+    lib.sd_mesh_merge.argtypes = [vp, vp, vp, sz, vp, sz, vp, sz] + [vp] * 8 + [vp, sz, vp]; lib.sd_mesh_merge.restype = i32
     _lib = lib
     return lib
 

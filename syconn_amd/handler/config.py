@@ -90,6 +90,16 @@ DEFAULTS = {
     'spines': {'semseg2coords_spines': {'k': 50, 'ds_vertices': 1, 'ignore_labels': [4, 5]}},
     'compartments': {'dist_axoness_averaging': 10000, 'view_properties_semsegax': {'semseg_key': 'axoness'}},
     'tcmn': {'ndim_embedding': 10},
+    # surface meshes (config.yml:169-189): the downsampling of every label volume before meshing, the size below which an object keeps
+    # an empty mesh, and the arguments of zmesh's get_mesh -- the two simplification keys are accepted and IGNORED (proc/meshes.py
+    # builds the unsimplified surface), normals: True is not built
+    'meshes': {
+        'allow_mesh_gen_cells': False,
+        'use_new_meshing': True,
+        'downsampling': {'sv': [4, 4, 2], 'sj': [2, 2, 1], 'vc': [4, 4, 2], 'mi': [4, 4, 2], 'er': [2, 2, 1], 'golgi': [2, 2, 1]},
+        'mesh_min_obj_vx': 100,
+        'meshing_props': {'normals': False, 'simplification_factor': 50, 'max_simplification_error': 40},
+    },
 }
 
 

@@ -304,6 +304,51 @@ def map_subcell_extract_props(kd_seg_path: str, kd_organelle_paths: Dict[str, st
     return cell_t.as_dicts(), {n: t.as_dicts() for n, t in sub_t.items()}, {n: t.as_dict() for n, t in map_t.items()}
 
 
+def mesh_objects(kd_seg_path: str, kd_organelle_paths: Dict[str, str], cube_of_interest_bb: Optional[Sequence] = None,
+                 chunk_size: Optional[Sequence[int]] = None, device=None, chunk_loader: Optional[Callable] = None,
+                 generate_sv_mesh: bool = False, scaling: Optional[Sequence[float]] = None):
+    """The meshing part of the reference's ``map_subcell_extract_props`` (sd_proc.py:687-770 per chunk, :957-964 over chunks) as a pass of
+    its own: over the chunk grid and with the loader convention of ``map_subcell_extract_props`` above, every organelle chunk (and the
+    cell chunk with `generate_sv_mesh`) is meshed by ``find_meshes_table(chunk, origin, pad=1, ds=config['meshes']['downsampling'][kind])``
+    and the per-chunk tables are merged in ASCENDING CHUNK ORDER (the reference merges in the order of a dictionary of workers).
+    Returns ``{kind: MeshTable}`` (the cell segmentation under ``'sv'``).  The size thresholds and the ``mesh_bb`` fallbacks of step 2
+    are ``proc.meshes.mesh_props`` over the merged ``PropTable``."""
+    import torch
+    from .. import global_params
+    from ..knossos import ChunkDataset
+    from .meshes import MeshTable, find_meshes_table
+    kinds = list(kd_organelle_paths.keys()) + (['sv'] if generate_sv_mesh else [])
+    kd = kd_factory(kd_seg_path)
+    if chunk_loader is None:
+        kds = {'sv': kd}
+        for name, path in kd_organelle_paths.items():
+            kds[name] = kd_factory(path)
+            if not np.array_equal(kds[name].boundary, kd.boundary):
+                raise ValueError("Data shape of subcellular structures '{}' differs from cell segmentation data. {} vs. {}".format(
+                    name, kds[name].boundary, kd.boundary))
+
+        def chunk_loader(name, offset, size):
+            return np.ascontiguousarray(kds[name].load_seg(size=size, offset=offset, mag=1).swapaxes(0, 2))
+    downsampling = global_params.config['meshes']['downsampling']
+    scaling = global_params.config['scaling'] if scaling is None else scaling
+    chunk_size = np.asarray([512, 512, 512] if chunk_size is None else chunk_size, dtype=np.int64)
+    lo = np.zeros(3, dtype=np.int64) if cube_of_interest_bb is None else np.asarray(cube_of_interest_bb[0], dtype=np.int64)
+    hi = np.asarray(kd.boundary, dtype=np.int64) if cube_of_interest_bb is None else np.asarray(cube_of_interest_bb[1], dtype=np.int64)
+    cd = ChunkDataset()
+    cd.initialize(kd, hi - lo, chunk_size, '', box_coords=lo, fit_box_size=True)
+    device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    pieces = {k: [] for k in kinds}
+    with torch.cuda.device(device):
+        for ch_id in sorted(cd.chunk_dict):
+            origin = np.asarray(cd.chunk_dict[ch_id].coordinates, dtype=np.int64)
+            for kind in kinds:
+                chunk = chunk_loader(kind, origin, chunk_size)
+                if isinstance(chunk, torch.Tensor) and chunk.dtype != torch.int64:
+                    chunk = chunk.to(torch.int64)
+                pieces[kind].append(find_meshes_table(chunk, origin, pad=1, ds=downsampling[kind], scaling=scaling, device=device))
+        return {kind: MeshTable.merge(pieces[kind], device=device) for kind in kinds}
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------
 # The reference's dictionary helpers, kept by name and contract for callers that hold dictionaries (the driver above works on
 # tables).  Each merges IN PLACE into the first element, as sd_proc.py:1248-1322 do.
