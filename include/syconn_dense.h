@@ -778,6 +778,59 @@ size_t sd_cell_synapses_temp_bytes(size_t n_syn);
 int sd_cell_synapses(const uint64_t* partners_dev, const uint8_t* keep_dev, const uint64_t* syn_ids_dev, size_t n_syn, const uint64_t* ssv_ids_dev,
                      size_t n_cells, uint64_t* syn_begin_dev, uint64_t* out_ids_dev, uint64_t* counts_dev, void* temp_dev, size_t temp_bytes, void* stream);
 
+/* ---- astrocyte splitting of the supervoxel graph (csrc/sd_glia.hip) --------------------------------------------------------
+ * The array form, for all cells of a dataset at once, of /root/reference/syconn/proc/graphs.py remove_glia_nodes (:278-360) with
+ * create_ccsize_dict (:220-249), of proc/glia_splitting.py collect_glia_sv (:37-63) and write_astrocyte_svgraph (:77-161), and of
+ * reps/segmentation_helper.py glia_pred_so / glia_proba_so (:32-78) with reps/segmentation.py glia_pred (:799-814).  Ids use all 64 bits
+ * and none is special.  Asynchronous on the stream; no float atomics; every count per call stays below 2^31 (SD_ERR_INVALID beyond).
+ *   sd_glia_split  edges_dev uint64[n_edges][2] (self loops and duplicates are legal: a single-supervoxel cell is a self loop),
+ *                  nodes_dev uint64[n_nodes] (optional: nodes without an edge; repeats of endpoints are legal).  The supervoxel table:
+ *                  ids_dev uint64[n_ids] strictly ascending, boxes_dev double[n_ids][2][3] in nm (finite; the supervoxel's mesh_bb),
+ *                  glia_dev uint8[n_ids] (0 neuron, else glia).  Nodes = the distinct endpoints and extra nodes, ascending; a cell = a
+ *                  component of the graph.  size(component) = sqrt(((dx dx) + dy dy) + dz dz) of d = max - min over BOTH corners of
+ *                  the boxes of its nodes, every product and sum rounded on its own, the root correctly rounded.  Per cell, with T =
+ *                  min_size: (1) no component of its neuron nodes has size > T: all of it is glia; (2) else no component of its glia
+ *                  nodes has size > T: all of it is neuron; (3) else glia nodes whose glia component has size < T are tiny fragments,
+ *                  nodes whose component among neuron nodes and tiny fragments has size < T leave, what stays is neuron and the rest
+ *                  glia.  Per node (node_cap entries each; counts[0] nodes): node_ids_dev, node_cell_dev (the smallest id of its
+ *                  cell), node_class_dev uint8 (final: 0 neuron, 1 glia), node_comp_dev (the smallest id of its component among the
+ *                  nodes of its final class), node_size1_dev (the size of its same-class component of steps 1 / 2), node_size2_dev
+ *                  (its size in step 3's neuron-or-tiny components, NaN where it took no part).  Per cell, ascending (node_cap
+ *                  entries; counts[1] cells): cell_ids_dev, cell_outcome_dev uint8 = 1, 2 or 3, the step that decided.  Two component
+ *                  tables in CSR form, neuron (ncc_, counts[2] components, counts[3] supervoxels) and glia (gcc_, counts[4],
+ *                  counts[5]): *_ids_dev ascending (node_cap entries), *_cell_dev, *_begin_dev uint64[node_cap + 1], *_sv_dev
+ *                  ascending inside a component (node_cap entries); for outcomes 1 and 2 the one component is the whole cell.
+ *                  neuron_edges_dev / astrocyte_edges_dev uint64[edge_cap][2] (counts[6] / counts[8]): the input edges with both
+ *                  endpoints neuron / glia, in input order, self loops included; a neuron node all of whose neighbours became glia
+ *                  is in the component table and, without a self loop, in no edge (the reference's lists and edge-list file differ
+ *                  in the same way).  cell_size_dev double[n_ids] (optional): a node with cell_size < min_cell_size (the size of its
+ *                  ORIGINAL cell, the caller's) is left out of both edge arrays, both component tables and counts[9] (:125-127,
+ *                  :147-149); its per-node outputs stay.  sv_sizes_dev int64[n_ids] (optional): counts[9] = the voxels of the glia
+ *                  nodes (total_size, :152-154).  counts_dev uint64[16], zeroed by every call: [7] != 0 ids_dev does not ascend
+ *                  strictly; [10] != 0 a node is not in the table (the reference raises KeyError) and [11] = the smallest such id
+ *                  (the outputs are then unusable); [12] != 0 node_cap or edge_cap was smaller than needed and records were lost
+ *                  (nothing is written past a capacity); [13], [14], [15] = cells of outcome 1, 2, 3.  node_cap = the distinct
+ *                  nodes (2 n_edges + n_nodes always suffices), edge_cap = n_edges always suffices.
+ *                  Scratch: sd_glia_split_temp_bytes(n_ids, n_edges, n_nodes).
+ *   sd_glia_pred   probas_dev float32 (is_f64 == 0) or float64 [n_views]: column 1 of every supervoxel's glia_probas, one after
+ *                  another; view_begin_dev uint64[n_sv + 1] ascending from 0 to n_views.  mean_dev double[n_sv] = the float64 sum in
+ *                  view order divided once by the number of views (NaN without views; numpy sums pairwise in the input dtype: equal
+ *                  whenever the sum is exact).  class_dev uint8[n_sv]: point_model == 0: mean > thresh and votes > (long long)
+ *                  ((double) views * 0.7) with votes = #(p > thresh); point_model != 0: mean >= thresh; no views: 0.
+ *                  counts_dev uint64[8]: [7] != 0 the offsets do not ascend from 0 to n_views.
+ * One grid stride of every kernel is SD_GLIA_GRID blocks of 256 items. */
+#define SD_GLIA_GRID 1024
+size_t sd_glia_split_temp_bytes(size_t n_ids, size_t n_edges, size_t n_nodes);
+int sd_glia_split(const uint64_t* edges_dev, size_t n_edges, const uint64_t* nodes_dev, size_t n_nodes, const uint64_t* ids_dev, const double* boxes_dev,
+                  const uint8_t* glia_dev, size_t n_ids, double min_size, const double* cell_size_dev, double min_cell_size, const int64_t* sv_sizes_dev,
+                  size_t node_cap, size_t edge_cap, uint64_t* node_ids_dev, uint64_t* node_cell_dev, uint8_t* node_class_dev, uint64_t* node_comp_dev,
+                  double* node_size1_dev, double* node_size2_dev, uint64_t* cell_ids_dev, uint8_t* cell_outcome_dev, uint64_t* ncc_ids_dev,
+                  uint64_t* ncc_cell_dev, uint64_t* ncc_begin_dev, uint64_t* ncc_sv_dev, uint64_t* gcc_ids_dev, uint64_t* gcc_cell_dev,
+                  uint64_t* gcc_begin_dev, uint64_t* gcc_sv_dev, uint64_t* neuron_edges_dev, uint64_t* astrocyte_edges_dev, uint64_t* counts_dev,
+                  void* temp_dev, size_t temp_bytes, void* stream);
+int sd_glia_pred(const void* probas_dev, int is_f64, const uint64_t* view_begin_dev, size_t n_sv, size_t n_views, double thresh, int point_model,
+                 uint8_t* class_dev, double* mean_dev, uint64_t* counts_dev, void* stream);
+
 /* ---- surface meshes of labelled objects (csrc/sd_mesh.hip) -----------------------------------------------------------------
  * The meshing of the reference's find_meshes (proc/meshes.py:937-994) for ALL non-zero labels of a chunk in one pass, and the merge of
  * per-chunk meshes with the mesh_bb / mesh_area of proc/sd_proc.py:951-975 (merge_meshes_incl_norm, proc/meshes.py:483-519).  The

@@ -19,6 +19,7 @@ SD_SYN_PROPS_MAX_K, SD_SYN_PROPS_CELL_GRID, SD_SYN_PROPS_POINT_GRID, SD_SYN_PROP
 SD_SKEL_MAX_CLASSES, SD_SKEL_LDS_NODES, SD_SKEL_VOTE_GRID, SD_SKEL_NODE_GRID, SD_SKEL_EDGE_GRID, SD_SKEL_REDO_GRID, SD_SKEL_REDO_BYTES = 64, 512, 2048, 1024, 1024, 1024, 1 << 28
 SD_CELLASM_GRID = 1024
 SD_MESH_GRID = 256
+SD_GLIA_GRID = 1024
 
 LIB_NAME = 'libsyconn_dense_hip.so'
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), os.environ.get('SD_LIB_NAME', LIB_NAME))
@@ -44,7 +45,7 @@ EXPORTS = ['sd_init', 'sd_device_count', 'sd_model_create', 'sd_model_destroy', 
            'sd_skel_vote_temp_bytes', 'sd_skel_vote', 'sd_skel_components_temp_bytes', 'sd_skel_components',
            'sd_svgraph_components_temp_bytes', 'sd_svgraph_components', 'sd_cell_props', 'sd_cell_mapping_temp_bytes', 'sd_cell_mapping',
            'sd_cell_synapses_temp_bytes', 'sd_cell_synapses', 'sd_mesh_count', 'sd_mesh_build_temp_bytes', 'sd_mesh_build',
-           'sd_mesh_merge_temp_bytes', 'sd_mesh_merge']
+           'sd_mesh_merge_temp_bytes', 'sd_mesh_merge', 'sd_glia_split_temp_bytes', 'sd_glia_split', 'sd_glia_pred']
 
 
 class OpDesc(C.Structure):
@@ -227,6 +228,10 @@ def load():
     lib.sd_mesh_build.restype = i32
     lib.sd_mesh_merge_temp_bytes.argtypes = [sz]; lib.sd_mesh_merge_temp_bytes.restype = sz
     lib.sd_mesh_merge.argtypes = [vp, vp, vp, sz, vp, sz, vp, sz] + [vp] * 8 + [vp, sz, vp]; lib.sd_mesh_merge.restype = i32
+    # proc/graphs.py:173-360 (remove_glia_nodes for all cells), proc/glia_splitting.py:37-161, reps/segmentation_helper.py:32-78 (glia_pred_so)
+    lib.sd_glia_split_temp_bytes.argtypes = [sz, sz, sz]; lib.sd_glia_split_temp_bytes.restype = sz
+    lib.sd_glia_split.argtypes = [vp, sz, vp, sz, vp, vp, vp, sz, f64, vp, f64, vp, sz, sz] + [vp] * 18 + [vp, vp, sz, vp]; lib.sd_glia_split.restype = i32
+    lib.sd_glia_pred.argtypes = [vp, i32, vp, sz, sz, f64, i32, vp, vp, vp, vp]; lib.sd_glia_pred.restype = i32
     _lib = lib
     return lib
 

@@ -1,0 +1,72 @@
+"""Astrocyte splitting between ``run_create_rag`` and ``run_create_neuron_ssd``: ``run_astrocyte_splitting`` of /root/reference/syconn/
+exec/exec_inference.py (:341-380) over the tables of ``exec_init``.  The reference reads the pruned graph from an edge-list file, splits
+cell by cell in batch jobs and writes the neuron graph to a file; here the pruned graph is the ``SvGraphComponents`` of
+``run_create_rag`` and the result's ``neuron_edges`` go straight into ``run_create_neuron_ssd(edges=...)``.  Not built: views, rendering
+and the glia model itself (``run_astrocyte_rendering`` / ``run_astrocyte_prediction``: the glia probabilities are an input), files."""
+import numpy as np
+
+from .. import global_params
+from ..proc import glia_splitting, graphs
+
+
+class AstrocyteSplitting:
+    """``split`` (``GliaSplit``), ``svs`` (``collect_glia_sv``: astrocyte_svs / neuron_svs / pruned_svs), ``graph`` (``AstrocyteSvGraph``),
+    ``glia`` (the class per table row) and ``glia_proba`` (the mean per table row, None where classes were given); ``neuron_edges`` is
+    ``graph.neuron_edges``."""
+
+    def __init__(self, split, svs, graph, glia, glia_proba):
+        self.split, self.svs, self.graph, self.glia, self.glia_proba = split, svs, graph, glia, glia_proba
+        self.neuron_edges = graph.neuron_edges
+
+
+def _boxes_nm(sv_props, mesh_bb, scaling):
+    """mesh_bb per table row: given (a ``MeshTable`` of ``mesh_props`` or an (n, 2, 3) array), or ``bounding_box * scaling`` for supervoxels
+    without a mesh (reps/segmentation.py:604-617)."""
+    n = len(sv_props.ids)
+    if mesh_bb is not None:
+        bb = np.asarray(mesh_bb.mesh_bb if hasattr(mesh_bb, 'mesh_bb') else mesh_bb)
+        if bb.size != 6 * n:
+            raise ValueError(f'run_astrocyte_splitting: mesh_bb must have the shape ({n}, 2, 3), got {bb.shape}')
+        return bb.reshape(n, 2, 3)
+    box_begin = np.asarray(sv_props.box_begin, np.int64)
+    boxes = np.asarray(sv_props.boxes, np.int64).reshape(-1, 2, 3)
+    if n and (np.diff(box_begin) < 1).any():
+        raise ValueError('run_astrocyte_splitting: a supervoxel without a bounding box')
+    lo = np.minimum.reduceat(boxes[:, 0], box_begin[:-1]) if n else np.zeros((0, 3), np.int64)
+    hi = np.maximum.reduceat(boxes[:, 1], box_begin[:-1]) if n else np.zeros((0, 3), np.int64)
+    return np.stack([lo, hi], 1) * scaling
+
+
+def run_astrocyte_splitting(components, sv_props, mesh_bb=None, glia_probas=None, view_begin=None, glia=None, thresh=None,
+                            use_point_models=None, scaling=None, min_cc_size=None, device=None) -> AstrocyteSplitting:
+    """``run_astrocyte_splitting`` (:341-380).  `components`: the ``SvGraphComponents`` of ``run_create_rag`` (its ``edges`` are the graph,
+    its ``sv_ids`` the nodes, its ``node_size`` the size of every supervoxel's original cell); `sv_props`: the cell ``PropTable``.  Boxes:
+    `mesh_bb` (the ``MeshTable`` of ``mesh_props`` over `sv_props`, or an (n, 2, 3) array in nm), without it ``bounding_box * scaling``.
+    The glia class per table row: `glia`, or ``glia_pred(glia_probas, view_begin, thresh, use_point_models)``.  `min_cc_size` (default
+    ``config['min_cc_size_ssv']``) is both the threshold of ``remove_glia_nodes`` and the ``min_ssv_size`` of
+    ``write_astrocyte_svgraph`` (:378)."""
+    what = 'run_astrocyte_splitting'
+    if (glia is None) == (glia_probas is None):
+        raise ValueError(f'{what}: pass either glia or glia_probas (with view_begin)')
+    if glia_probas is not None and view_begin is None:
+        raise ValueError(f'{what}: glia_probas needs view_begin')
+    scaling = np.asarray(global_params.config['scaling'] if scaling is None else scaling, dtype=np.float64)
+    if min_cc_size is None:
+        min_cc_size = global_params.config['min_cc_size_ssv']
+    ids = np.ascontiguousarray(np.asarray(sv_props.ids).reshape(-1), dtype=np.uint64)
+    boxes = _boxes_nm(sv_props, mesh_bb, scaling)
+    proba = None
+    if glia is None:
+        if len(np.asarray(view_begin).reshape(-1)) != len(ids) + 1:
+            raise ValueError(f'{what}: view_begin must have one entry per supervoxel and one more')
+        glia, proba = graphs.glia_pred(glia_probas, view_begin, thresh, use_point_models, device)
+    # the size of the original cell per table row: +inf for supervoxels outside the graph (they are no nodes)
+    cell_size = np.full(len(ids), np.inf)
+    row = np.searchsorted(ids, components.node_ids)
+    ok = row < len(ids)
+    ok[ok] = ids[row[ok]] == components.node_ids[ok]
+    cell_size[row[ok]] = components.node_size[ok]
+    split = glia_splitting.run_glia_splitting(components.edges, ids, boxes, glia, min_cc_size, components.sv_ids, cell_size, min_cc_size,
+                                              sv_props.sizes, device)
+    return AstrocyteSplitting(split, glia_splitting.collect_glia_sv(split, ids), glia_splitting.write_astrocyte_svgraph(split, scaling),
+                              np.asarray(glia), proba)

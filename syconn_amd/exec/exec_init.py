@@ -1,7 +1,8 @@
 """Cells from the supervoxel graph: ``run_create_rag`` and ``run_create_neuron_ssd`` of /root/reference/syconn/exec/exec_init.py
 (:299-367, :32-123) over the tables ``map_subcell_extract_props(as_tables=True)`` returns.  The reference reads edge-list files into
 networkx and writes ``SuperSegmentationDataset`` storages; here edges arrive as an ``(e, 2)`` uint64 array and everything stays in
-memory.  Not built: the files, the storages and their numpy caches, the per-cell ``edgelist`` files, astrocyte splitting, meshes."""
+memory.  Between the two runs ``exec_inference.run_astrocyte_splitting`` turns the pruned graph into the neuron graph.  Not built: the
+files, the storages and their numpy caches, the per-cell ``edgelist`` files, meshes."""
 from typing import Dict, Optional, Sequence
 
 import numpy as np

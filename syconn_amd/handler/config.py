@@ -100,6 +100,10 @@ DEFAULTS = {
         'mesh_min_obj_vx': 100,
         'meshing_props': {'normals': False, 'simplification_factor': 50, 'max_simplification_error': 40},
     },
+    # astrocyte splitting (config.yml:221, :243-247): run before the neuron cells are made; a supervoxel is glia when the mean of its
+    # views' glia probability is above glia_thresh and more than 70 % of the views are (point models: the mean at or above it)
+    'glia': {'prior_astrocyte_removal': True, 'glia_thresh': 0.161489},
+    'use_point_models': False,
 }
 
 
