@@ -831,6 +831,76 @@ int sd_glia_split(const uint64_t* edges_dev, size_t n_edges, const uint64_t* nod
 int sd_glia_pred(const void* probas_dev, int is_f64, const uint64_t* view_begin_dev, size_t n_sv, size_t n_views, double thresh, int point_model,
                  uint8_t* class_dev, double* mean_dev, uint64_t* counts_dev, void* stream);
 
+/* ---- multi-view depth and index images of a mesh, view rotations, pixel -> vertex vote (csrc/sd_views.hip) ----------------------
+ * The compute form of what the reference renders with OpenGL: proc/rendering_egl.py _render_mesh_coords (:611-681),
+ * multi_view_mesh_coords (:460-590), screen_shot (:130-174); proc/meshes.py MeshObject (:69-175), calc_rot_matrices (:236-329),
+ * flag_empty_spaces (:332-360) with extraction/in_bounding_boxC.pyx; proc/rendering.py render_sso_coords_index_views (:300-396);
+ * reps/super_segmentation_helper.py semseg2mesh_counter (:1527-1551) and the decision of semseg2mesh (:1603-1615).  The raster rule is
+ * this build's own and is stated in DESIGN.md section 7 (tests/_views_ref.py says the same in numpy).  Asynchronous on the stream; no
+ * float atomics; every count per call stays below 2^31 (SD_ERR_INVALID beyond).  counts_dev uint64[8], zeroed by every call.
+ * Common arguments: verts_dev float32[n_verts][3] and coords_dev float32[n_loc][3] are RAW; center3 (host, 3 floats) and max_dist > 0
+ * normalise both wherever they are read: vn = fl32(fl32(v - center) / max_dist) (center 0 and max_dist 1 leave them as they are).
+ * tris_dev uint32[n_tris][3].  edge3 (host, 3 doubles) = [cw, cw / 2, cw] / max_dist.
+ *   sd_views_rotations    rot_dev double[n_loc][16]: per location the PCA of the normalised vertices 0, stride, 2 stride, ... that lie
+ *                         inside the box of edge_length (normalised units) around it by in_bounding_box's float32 test (strict on both
+ *                         sides, half edge = fl32(edge_length / 2)): mean and covariance (divisor n - 1) in float64, rows = eigenvectors
+ *                         by descending eigenvalue, rot[i + 4 j] = row i, component j; rot[15] = 1; <= 2 inliers: 16 zeros.  The
+ *                         component of largest magnitude of every row is positive (lowest index on a tie).  empty_dev uint8[n_loc]
+ *                         (optional): 1 where no vertex is inside.  sd_views_flag_empty: only that.  Scratch:
+ *                         sd_views_rotations_temp_bytes(n_verts, stride).
+ *   sd_views_index        index_dev (sd_views_index_bytes(n_tris) bytes, opaque): a uniform grid over the normalised triangles keyed by
+ *                         centroid cell, the largest distance of a vertex to its triangle's centroid, and whether any normalised vertex
+ *                         is not 0.  counts[3] != 0: a triangle names a vertex >= n_verts (it is in no cell).  Scratch:
+ *                         sd_views_index_temp_bytes(n_tris).
+ *   sd_views_candidates   cand_begin_dev uint64[n_loc + 1], cand_dev uint32[cand_cap]: per location the triangles of the grid cells that
+ *                         meet the sphere of radius 0.5 |edge3| + that distance around it, a superset of what any view of the location
+ *                         shows.  counts[0] = their number; with cand_cap == 0 nothing is emitted (the sizing call); counts[1] != 0:
+ *                         cand_cap was too small, nothing is written past it; counts[6] != 0: 2^31 candidates or more (split the
+ *                         locations).  Scratch: sd_views_candidates_temp_bytes(n_loc).
+ *   sd_views_render       views_dev uint8[n_loc][n_views][H][W] (views_cap elements): view m of a location is its matrix rot_dev[loc]
+ *                         followed by the rotation about x with cos_v[m], sin_v[m] (host, n_views <= SD_VIEWS_MAX_VIEWS doubles each);
+ *                         weights7 (host) the 7 filter weights.  255 where nothing is drawn, for a location whose matrix is all zero
+ *                         and for a mesh whose normalised vertices are all zero.  counts[2] = triangles dropped because a snapped
+ *                         coordinate reached 2^22 (per location and view), counts[3] != 0: a bad triangle or vertex number.  A window
+ *                         of at most SD_VIEWS_TILE_PX pixels is one LDS tile; larger ones are cut into tiles of 250 x 122 (+ 3 halo).
+ *   sd_views_render_index views_dev uint32[n_loc][n_views][H][W]: the last vertex of the nearest triangle (lowest triangle number at equal
+ *                         depth), 2^32 - 2 where nothing is drawn.  One tile holds SD_VIEWS_TILE_PX / 2 pixels, larger windows are cut
+ *                         into tiles of 128 x 128.  Scratch of both: sd_views_render_temp_bytes(n_loc, n_views).
+ *   sd_views_vote         index_dev uint32[n_px], labels_dev uint8[n_px]: vertex_labels_dev uint8[n_verts] = the first label of the
+ *                         largest count among the pixels of the vertex, counts taken modulo 256; `unpredicted` where they sum to 0.
+ *                         Pixels equal to background_id are skipped.  table_dev uint8[n_verts][n_labels] (optional): the wrapped counts.
+ *                         counts[0] = predicted vertices, counts[3] != 0: a pixel names a vertex >= n_verts, counts[4] != 0: a label
+ *                         >= n_labels (both are skipped).  Scratch: sd_views_vote_temp_bytes(n_verts, n_labels).
+ * One grid stride of the 1D kernels is SD_VIEWS_GRID blocks of 256 threads, of the raster SD_VIEWS_RASTER_GRID workgroups. */
+#define SD_VIEWS_GRID 1024
+#define SD_VIEWS_RASTER_GRID 4096
+#define SD_VIEWS_MAX_VIEWS 16
+#define SD_VIEWS_TILE_PX 32768
+size_t sd_views_rotations_temp_bytes(size_t n_verts, size_t stride);
+int sd_views_rotations(const float* verts_dev, size_t n_verts, size_t stride, const float* coords_dev, size_t n_loc, const float* center3, float max_dist,
+                       float edge_length, double* rot_dev, uint8_t* empty_dev, uint64_t* counts_dev, void* temp_dev, size_t temp_bytes, void* stream);
+int sd_views_flag_empty(const float* verts_dev, size_t n_verts, size_t stride, const float* coords_dev, size_t n_loc, const float* center3, float max_dist,
+                        float edge_length, uint8_t* empty_dev, uint64_t* counts_dev, void* temp_dev, size_t temp_bytes, void* stream);
+size_t sd_views_index_bytes(size_t n_tris);
+size_t sd_views_index_temp_bytes(size_t n_tris);
+int sd_views_index(const float* verts_dev, size_t n_verts, const uint32_t* tris_dev, size_t n_tris, const float* center3, float max_dist, void* index_dev,
+                   size_t index_bytes, uint64_t* counts_dev, void* temp_dev, size_t temp_bytes, void* stream);
+size_t sd_views_candidates_temp_bytes(size_t n_loc);
+int sd_views_candidates(const void* index_dev, size_t n_tris, const float* coords_dev, size_t n_loc, const float* center3, float max_dist, const double* edge3,
+                        uint64_t* cand_begin_dev, uint32_t* cand_dev, size_t cand_cap, uint64_t* counts_dev, void* temp_dev, size_t temp_bytes, void* stream);
+size_t sd_views_render_temp_bytes(size_t n_loc, int n_views);
+int sd_views_render(const float* verts_dev, size_t n_verts, const uint32_t* tris_dev, size_t n_tris, const void* index_dev, const float* coords_dev,
+                    size_t n_loc, const double* rot_dev, const float* center3, float max_dist, const double* edge3, const double* cos_v, const double* sin_v,
+                    int n_views, int W, int H, const double* weights7, const uint64_t* cand_begin_dev, const uint32_t* cand_dev, size_t cand_n,
+                    uint8_t* views_dev, size_t views_cap, uint64_t* counts_dev, void* temp_dev, size_t temp_bytes, void* stream);
+int sd_views_render_index(const float* verts_dev, size_t n_verts, const uint32_t* tris_dev, size_t n_tris, const void* index_dev, const float* coords_dev,
+                          size_t n_loc, const double* rot_dev, const float* center3, float max_dist, const double* edge3, const double* cos_v,
+                          const double* sin_v, int n_views, int W, int H, const uint64_t* cand_begin_dev, const uint32_t* cand_dev, size_t cand_n,
+                          uint32_t* views_dev, size_t views_cap, uint64_t* counts_dev, void* temp_dev, size_t temp_bytes, void* stream);
+size_t sd_views_vote_temp_bytes(size_t n_verts, int n_labels);
+int sd_views_vote(const uint32_t* index_dev, const uint8_t* labels_dev, size_t n_px, uint32_t background_id, size_t n_verts, int n_labels, int unpredicted,
+                  uint8_t* vertex_labels_dev, uint8_t* table_dev, uint64_t* counts_dev, void* temp_dev, size_t temp_bytes, void* stream);
+
 /* ---- surface meshes of labelled objects (csrc/sd_mesh.hip) -----------------------------------------------------------------
  * The meshing of the reference's find_meshes (proc/meshes.py:937-994) for ALL non-zero labels of a chunk in one pass, and the merge of
  * per-chunk meshes with the mesh_bb / mesh_area of proc/sd_proc.py:951-975 (merge_meshes_incl_norm, proc/meshes.py:483-519).  The

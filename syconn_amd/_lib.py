@@ -20,6 +20,7 @@ SD_SKEL_MAX_CLASSES, SD_SKEL_LDS_NODES, SD_SKEL_VOTE_GRID, SD_SKEL_NODE_GRID, SD
 SD_CELLASM_GRID = 1024
 SD_MESH_GRID = 256
 SD_GLIA_GRID = 1024
+SD_VIEWS_GRID, SD_VIEWS_RASTER_GRID, SD_VIEWS_MAX_VIEWS, SD_VIEWS_TILE_PX = 1024, 4096, 16, 32768
 
 LIB_NAME = 'libsyconn_dense_hip.so'
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), os.environ.get('SD_LIB_NAME', LIB_NAME))
@@ -45,7 +46,10 @@ EXPORTS = ['sd_init', 'sd_device_count', 'sd_model_create', 'sd_model_destroy', 
            'sd_skel_vote_temp_bytes', 'sd_skel_vote', 'sd_skel_components_temp_bytes', 'sd_skel_components',
            'sd_svgraph_components_temp_bytes', 'sd_svgraph_components', 'sd_cell_props', 'sd_cell_mapping_temp_bytes', 'sd_cell_mapping',
            'sd_cell_synapses_temp_bytes', 'sd_cell_synapses', 'sd_mesh_count', 'sd_mesh_build_temp_bytes', 'sd_mesh_build',
-           'sd_mesh_merge_temp_bytes', 'sd_mesh_merge', 'sd_glia_split_temp_bytes', 'sd_glia_split', 'sd_glia_pred']
+           'sd_mesh_merge_temp_bytes', 'sd_mesh_merge', 'sd_glia_split_temp_bytes', 'sd_glia_split', 'sd_glia_pred',
+           'sd_views_rotations_temp_bytes', 'sd_views_rotations', 'sd_views_flag_empty', 'sd_views_index_bytes', 'sd_views_index_temp_bytes', 'sd_views_index',
+           'sd_views_candidates_temp_bytes', 'sd_views_candidates', 'sd_views_render_temp_bytes', 'sd_views_render', 'sd_views_render_index',
+           'sd_views_vote_temp_bytes', 'sd_views_vote']
 
 
 class OpDesc(C.Structure):
@@ -232,6 +236,24 @@ def load():
     lib.sd_glia_split_temp_bytes.argtypes = [sz, sz, sz]; lib.sd_glia_split_temp_bytes.restype = sz
     lib.sd_glia_split.argtypes = [vp, sz, vp, sz, vp, vp, vp, sz, f64, vp, f64, vp, sz, sz] + [vp] * 18 + [vp, vp, sz, vp]; lib.sd_glia_split.restype = i32
     lib.sd_glia_pred.argtypes = [vp, i32, vp, sz, sz, f64, i32, vp, vp, vp, vp]; lib.sd_glia_pred.restype = i32
+    # proc/rendering_egl.py:130-174, :460-681 (the views), proc/meshes.py:69-175, :236-360 (normalisation, rotations),
+    # reps/super_segmentation_helper.py:1527-1551, :1603-1615 (the pixel -> vertex vote)
+    f32, f32p = C.c_float, C.POINTER(C.c_float)
+    lib.sd_views_rotations_temp_bytes.argtypes = [sz, sz]; lib.sd_views_rotations_temp_bytes.restype = sz
+    lib.sd_views_rotations.argtypes = [vp, sz, sz, vp, sz, f32p, f32, f32, vp, vp, vp, vp, sz, vp]; lib.sd_views_rotations.restype = i32
+    lib.sd_views_flag_empty.argtypes = [vp, sz, sz, vp, sz, f32p, f32, f32, vp, vp, vp, sz, vp]; lib.sd_views_flag_empty.restype = i32
+    lib.sd_views_index_bytes.argtypes = [sz]; lib.sd_views_index_bytes.restype = sz
+    lib.sd_views_index_temp_bytes.argtypes = [sz]; lib.sd_views_index_temp_bytes.restype = sz
+    lib.sd_views_index.argtypes = [vp, sz, vp, sz, f32p, f32, vp, sz, vp, vp, sz, vp]; lib.sd_views_index.restype = i32
+    lib.sd_views_candidates_temp_bytes.argtypes = [sz]; lib.sd_views_candidates_temp_bytes.restype = sz
+    lib.sd_views_candidates.argtypes = [vp, sz, vp, sz, f32p, f32, f64p, vp, vp, sz, vp, vp, sz, vp]; lib.sd_views_candidates.restype = i32
+    lib.sd_views_render_temp_bytes.argtypes = [sz, i32]; lib.sd_views_render_temp_bytes.restype = sz
+    lib.sd_views_render.argtypes = [vp, sz, vp, sz, vp, vp, sz, vp, f32p, f32, f64p, f64p, f64p, i32, i32, i32, f64p, vp, vp, sz, vp, sz, vp, vp, sz, vp]
+    lib.sd_views_render.restype = i32
+    lib.sd_views_render_index.argtypes = [vp, sz, vp, sz, vp, vp, sz, vp, f32p, f32, f64p, f64p, f64p, i32, i32, i32, vp, vp, sz, vp, sz, vp, vp, sz, vp]
+    lib.sd_views_render_index.restype = i32
+    lib.sd_views_vote_temp_bytes.argtypes = [sz, i32]; lib.sd_views_vote_temp_bytes.restype = sz
+    lib.sd_views_vote.argtypes = [vp, vp, sz, C.c_uint32, sz, i32, i32, vp, vp, vp, vp, sz, vp]; lib.sd_views_vote.restype = i32
     _lib = lib
     return lib
 

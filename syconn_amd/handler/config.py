@@ -104,6 +104,13 @@ DEFAULTS = {
     # views' glia probability is above glia_thresh and more than 70 % of the views are (point models: the mean at or above it)
     'glia': {'prior_astrocyte_removal': True, 'glia_thresh': 0.161489},
     'use_point_models': False,
+    # views (config.yml:223-232): the organelle channels after the cell's ('sj' is rendered from 'syn_ssv' with on-the-fly views), the
+    # window edge in nm along the first principal axis, the window in pixels (x, y) and the views per location
+    'views': {
+        'use_onthefly_views': True,
+        'subcell_objects': ['mi', 'vc', 'sj'],
+        'view_properties': {'comp_window': 8000, 'ws': [256, 128], 'nb_views': 2},
+    },
 }
 
 

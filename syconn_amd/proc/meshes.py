@@ -68,6 +68,134 @@ def mesh_area_calc(mesh) -> float:
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
+# view normalisation and view rotations (proc/meshes.py:69-175, :236-360)
+class MeshObject(object):
+    """The normalisation members of the reference's ``MeshObject`` (proc/meshes.py:69-175): flat float32 ``vertices`` centred on
+    ``center`` and divided by ``max_dist`` (both float32), flat uint64 ``indices``, ``vert_resh``, ``transform_external_coords``,
+    ``retransform_external_coords``, ``bounding_box``, ``vertices_scaled``.  Normals, colours and the PCA members are not built."""
+
+    def __init__(self, object_type, indices, vertices, normals=None, color=None, bounding_box=None):
+        self.object_type = object_type
+        vertices, indices = np.asarray(vertices), np.asarray(indices)
+        if vertices.ndim == 2 and vertices.shape[1] == 3:
+            self.vertices = vertices.flatten()
+        else:
+            self.vertices = np.array(vertices, dtype=np.float32)
+        if indices.ndim == 2 and indices.shape[1] == 3:
+            self.indices = indices.flatten().astype(np.uint64)
+        else:
+            self.indices = np.array(indices, dtype=np.uint64)
+        if len(self.vertices) == 0:
+            self.center, self.max_dist = 0, 1
+            return
+        if bounding_box is None:
+            self.center, self.max_dist = get_bounding_box(self.vertices)
+        else:
+            self.center, self.max_dist = bounding_box[0], bounding_box[1]
+        self.center = np.asarray(self.center).astype(np.float32)
+        self.max_dist = np.asarray(self.max_dist).astype(np.float32)
+        vert_resh = np.array(self.vertices).reshape((len(self.vertices) // 3, 3))
+        vert_resh -= np.array(self.center, dtype=self.vertices.dtype)
+        vert_resh = vert_resh / np.array(self.max_dist)
+        self.vertices = vert_resh.reshape(len(self.vertices))
+
+    @property
+    def vert_resh(self):
+        return np.array(self.vertices).reshape(-1, 3)
+
+    def transform_external_coords(self, coords):
+        if len(coords) == 0:
+            return coords
+        coords = np.array(coords, dtype=np.float32)
+        coords = coords - self.center
+        coords /= self.max_dist
+        return coords
+
+    def retransform_external_coords(self, coords):
+        coords = np.array(coords, dtype=np.float32)
+        coords *= self.max_dist
+        coords += self.center
+        return coords.astype(np.int32)
+
+    @property
+    def bounding_box(self):
+        return [self.center, self.max_dist]
+
+    @property
+    def vertices_scaled(self):
+        return (self.vert_resh * self.max_dist + self.center).flatten()
+
+
+def _scalar_edge(name, edge_length):
+    if not np.isscalar(edge_length):
+        edge_length = np.min(edge_length)                                          # the reference warns and takes the smallest
+    edge_length = np.float32(edge_length)
+    if not np.isfinite(edge_length) or edge_length < 0:
+        raise ValueError(f'{name}: edge_length must be a finite, non-negative number')
+    return edge_length
+
+
+def rot_vertex_stride(n_vertices: int) -> int:
+    """``vertices[::8]`` above 1e5 vertices (proc/meshes.py:258-259)."""
+    return 8 if n_vertices > 1e5 else 1
+
+
+def calc_rot_matrices_device(verts_d, coords_d, center, max_dist, edge_length, dev, stride=None, flag_only=False):
+    """``sd_views_rotations`` / ``sd_views_flag_empty`` over device tensors: raw float32 vertices and locations with the normalisation
+    (`center`, `max_dist`) the kernels apply to both; `edge_length` in normalised units -> float64 (N, 16) on the device, or the
+    uint8 "no inlier" flags."""
+    import ctypes as C
+    from .. import _dev as D
+    n_verts, n = int(verts_d.shape[0]), int(coords_d.shape[0])
+    stride = rot_vertex_stride(n_verts) if stride is None else int(stride)
+    c3 = (C.c_float * 3)(*[float(v) for v in np.asarray(center, np.float32).reshape(3)])
+    cnt = D.counters(dev)
+    tmp = D.scratch('sd_views_rotations_temp_bytes', dev, n_verts, stride)
+    head = (verts_d if n_verts else None, n_verts, stride, coords_d, n, c3, float(max_dist), float(edge_length))
+    if flag_only:
+        out = D.empty(n, D.u8, dev)
+        D.call('sd_views_flag_empty', dev, *head, out, cnt, tmp, tmp.numel())
+    else:
+        out = D.empty((n, 16), D.f64, dev)
+        D.call('sd_views_rotations', dev, *head, out, None, cnt, tmp, tmp.numel())
+    return out[:n]
+
+
+def _rot_inputs(name, coords, vertices, edge_length, device):
+    from .. import _dev as D
+    edge_length = _scalar_edge(name, edge_length)
+    coords = np.array(coords, dtype=np.float32).reshape(-1, 3)
+    vertices = np.asarray(vertices).reshape(-1, 3).astype(np.float32)
+    if not (np.isfinite(coords).all() and np.isfinite(vertices).all()):
+        raise ValueError(f'{name}: coordinates and vertices must be finite')
+    dev = D.device(device)
+    return D.up(vertices, dev), D.up(coords, dev), edge_length, dev
+
+
+def calc_rot_matrices(coords: np.ndarray, vertices: np.ndarray, edge_length, nb_cpus: int = 1, device=None) -> np.ndarray:
+    """Drop-in of the reference's ``calc_rot_matrices`` (proc/meshes.py:236-329): per location the flat (Fortran order) 4 x 4 matrix
+    whose rows are the principal axes of the vertices inside the box of `edge_length` around it, 16 zeros for <= 2 inliers; every 8th
+    vertex above 1e5.  `coords` and `vertices` are normalised already.  The sign of a row is this build's (the component of largest
+    magnitude is positive; ``np.linalg.eig`` leaves it to LAPACK)."""
+    from .. import _dev as D
+    verts_d, coords_d, edge_length, dev = _rot_inputs('calc_rot_matrices', coords, vertices, edge_length, device)
+    if coords_d.shape[0] == 0:
+        return np.zeros((0, 16))
+    return D.down(calc_rot_matrices_device(verts_d, coords_d, np.zeros(3, np.float32), 1.0, edge_length, dev))
+
+
+def flag_empty_spaces(coords: np.ndarray, vertices: np.ndarray, edge_length, device=None) -> np.ndarray:
+    """Drop-in of the reference's ``flag_empty_spaces`` (proc/meshes.py:332-360): True where no vertex lies inside the box; every 8th
+    vertex above 1e6."""
+    from .. import _dev as D
+    verts_d, coords_d, edge_length, dev = _rot_inputs('flag_empty_spaces', coords, vertices, edge_length, device)
+    if coords_d.shape[0] == 0:
+        return np.zeros(0, bool)
+    stride = 8 if verts_d.shape[0] > 1e6 else 1
+    return D.down(calc_rot_matrices_device(verts_d, coords_d, np.zeros(3, np.float32), 1.0, edge_length, dev, stride, True)).astype(bool)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
 class MeshTable:
     """Meshes of the objects of one label volume kind, plain numpy, a CSR by object: ``ids`` uint64 ascending, ``vert_begin`` /
     ``tri_begin`` uint64 (n + 1), ``vertices`` float32 (v, 3) in nm, ``indices`` uint32 (t, 3) local to the object, ``mesh_bb`` float32
@@ -100,6 +228,15 @@ class MeshTable:
         vb, tb = self.vert_begin.astype(np.int64), self.tri_begin.astype(np.int64)
         return {int(i): [self.indices[tb[k]:tb[k + 1]].reshape(-1), self.vertices[vb[k]:vb[k + 1]].reshape(-1), np.zeros((0,), np.float32)]
                 for k, i in enumerate(self.ids)}
+
+    def mesh_of(self, obj_id):
+        """``[indices flat uint32, vertices flat float32, empty float32 normals]`` of one object, the form ``sso.mesh`` and
+        ``sso.load_mesh`` have and the view functions of ``proc/rendering.py`` take; empty arrays for an id the table does not hold."""
+        k = int(np.searchsorted(self.ids, np.uint64(obj_id)))
+        if k >= len(self.ids) or self.ids[k] != np.uint64(obj_id):
+            return [np.zeros(0, np.uint32), np.zeros(0, np.float32), np.zeros(0, np.float32)]
+        vb, tb = self.vert_begin.astype(np.int64), self.tri_begin.astype(np.int64)
+        return [self.indices[tb[k]:tb[k + 1]].reshape(-1), self.vertices[vb[k]:vb[k + 1]].reshape(-1), np.zeros(0, np.float32)]
 
     def vertices_of(self, ids):
         """``(vertices, vert_begin)`` of the objects `ids` in their order, as ``OrganelleTable`` / ``CellTable`` take them: float32 (w, 3)

@@ -275,3 +275,103 @@ def majority_vote_compartments(sso, ax_pred_key: str = 'axoness'):
     new_axoness_arr[:] = res
     sso.skeleton[ax_pred_key + "_comp_maj"] = new_axoness_arr
     sso.save_skeleton()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# from pixels back to the mesh (reps/super_segmentation_helper.py:1527-1667)
+def _vote_device(index_arr, label_arr, bg_label, n_verts, n_labels, unpredicted, want_table, device=None):
+    """``sd_views_vote`` -> (vertex labels uint8, the wrapped count table uint8 or None)."""
+    index_arr = index_arr if isinstance(index_arr, torch.Tensor) else np.asarray(index_arr).reshape(-1)
+    label_arr = label_arr if isinstance(label_arr, torch.Tensor) else np.asarray(label_arr).reshape(-1)
+    dev = D.device(device)
+    if isinstance(index_arr, torch.Tensor):
+        idx_d = index_arr.to(dev).reshape(-1).to(torch.int32).contiguous()
+    else:
+        if len(index_arr) and (index_arr.min() < 0 or index_arr.max() >= 2 ** 32):
+            raise IndexError('semseg2mesh_counter: an index does not fit 32 bits')
+        idx_d = D.up(index_arr.astype(np.uint32), dev)
+    if isinstance(label_arr, torch.Tensor):
+        lab_d = label_arr.to(dev).reshape(-1).to(torch.uint8).contiguous()
+    else:
+        if len(label_arr) and (label_arr.min() < 0 or label_arr.max() > 255):
+            raise ValueError('semseg2mesh_counter: labels must fit uint8')
+        lab_d = D.up(label_arr.astype(np.uint8), dev)
+    n_px = int(idx_d.numel())
+    if int(lab_d.numel()) != n_px:
+        raise ValueError(f'semseg2mesh_counter: {n_px} indices, {int(lab_d.numel())} labels')
+    labels_d = D.empty(n_verts, D.u8, dev)
+    table_d = D.empty((n_verts, n_labels), D.u8, dev) if want_table else None
+    cnt = D.counters(dev)
+    tmp = D.scratch('sd_views_vote_temp_bytes', dev, n_verts, n_labels)
+    D.call('sd_views_vote', dev, idx_d if n_px else None, lab_d if n_px else None, n_px, int(bg_label) & 0xffffffff, n_verts, n_labels, unpredicted,
+           labels_d, table_d, cnt, tmp, tmp.numel())
+    c = D.down(cnt)
+    if c[3]:
+        raise IndexError('semseg2mesh_counter: a pixel names a vertex the mesh does not have')
+    if c[4]:
+        raise IndexError('semseg2mesh_counter: a label is outside the count table')
+    return D.down(labels_d, n_verts), (D.down(table_d, n_verts) if want_table else None)
+
+
+def semseg2mesh_counter(index_arr: np.ndarray, label_arr: np.ndarray, bg_label: int, count_arr: np.ndarray, device=None) -> np.ndarray:
+    """Drop-in of the reference's ``semseg2mesh_counter`` (:1527-1551): the per-vertex label counts of the pixels, added to `count_arr`
+    ((M, labels), zero-initialised by the caller) in ITS dtype, so a uint8 table wraps at 256 as the reference's does."""
+    count_arr = np.asarray(count_arr)
+    if count_arr.ndim != 2:
+        raise ValueError('semseg2mesh_counter: count_arr must have shape (vertices, labels)')
+    if count_arr.dtype != np.uint8:
+        raise NotImplementedError('semseg2mesh_counter: only the uint8 count table of semseg2mesh is built')
+    n_verts, n_labels = count_arr.shape
+    if n_verts == 0 or n_labels == 0:
+        if len(np.asarray(index_arr).reshape(-1)) and (np.asarray(index_arr).reshape(-1) != bg_label).any():
+            raise IndexError('semseg2mesh_counter: a pixel names a vertex the mesh does not have')
+        return count_arr
+    _, table = _vote_device(index_arr, label_arr, bg_label, n_verts, n_labels, 0, True, device)
+    count_arr += table.reshape(count_arr.shape)
+    return count_arr
+
+
+def semseg2mesh(sso, semseg_key=None, nb_views=None, dest_path=None, k=1, colors=None, force_recompute=False, index_view_key=None,
+                index_views=None, semseg_views=None, device=None):
+    """The reference's ``semseg2mesh`` (:1554-1667) on arrays in memory: `index_views` (the output of ``render_sso_coords_index_views``)
+    and `semseg_views` (pixel labels of the same shape) vote for the vertices of ``sso.mesh``; -> ``(indices, vertices, normals, col)``
+    with col the per-vertex label, or ``colors[label]``.  ``background_id = max(index_views)``, ``background_l = max(semseg_views)``,
+    unpredicted = background_l + 1.  k = 0 keeps unpredicted and background vertices; k > 0 spreads the labels of the predicted,
+    non-background vertices to all vertices by the majority of the k nearest (the device kNN vote of the spine head path).  The view
+    and label storages are not built: the views are arguments, `dest_path` raises ``NotImplementedError``."""
+    if dest_path is not None:
+        raise NotImplementedError('semseg2mesh: writing the coloured mesh to a k.zip is not built')
+    if index_views is None or semseg_views is None:
+        raise NotImplementedError('semseg2mesh: the view storage is not built; pass index_views and semseg_views')
+    from ..extraction.cs_processing_steps import segmented_knn
+    i_views, s_views = np.asarray(index_views).reshape(-1), np.asarray(semseg_views).reshape(-1)
+    if len(i_views) != len(s_views):
+        raise ValueError(f'semseg2mesh: {len(i_views)} index pixels, {len(s_views)} label pixels')
+    if len(i_views) == 0:
+        raise ValueError('semseg2mesh: no pixels')
+    mesh = sso.mesh
+    vertices = np.asarray(mesh[1]).reshape(-1, 3)
+    background_id, background_l = int(np.max(i_views)), int(np.max(s_views))
+    unpredicted_l = background_l + 1
+    if unpredicted_l > 255:
+        raise ValueError('Overflow in label view array.')
+    pp = len(vertices)
+    if pp:
+        vertex_labels, _ = _vote_device(i_views, s_views, background_id, pp, background_l + 1, unpredicted_l, False, device)
+    else:
+        if (i_views != background_id).any():
+            raise IndexError('semseg2mesh: a pixel names a vertex the mesh does not have')
+        vertex_labels = np.zeros(0, np.uint8)
+    if isinstance(k, bool) or int(k) != k or k < 0:
+        raise ValueError(f'semseg2mesh: k must be a non-negative integer, got {k!r}')
+    if k == 0:
+        maj_vote = vertex_labels
+    else:
+        keep = (vertex_labels != unpredicted_l) & (vertex_labels != background_l)
+        if not keep.any():
+            raise ValueError('semseg2mesh: no vertex has a prediction to spread (the reference fails in cKDTree.query here)')
+        pts = vertices[keep]
+        maj_vote = segmented_knn(pts, np.array([0, len(pts)]), vertex_labels[keep].astype(np.int32), np.zeros(pp, np.int64),
+                                 vertices.astype(np.float64), int(k), device).astype(np.int32)
+    col = maj_vote if colors is None else np.asarray(colors)[maj_vote].astype(np.uint8)
+    return mesh[0], mesh[1], (mesh[2] if len(mesh) > 2 else np.zeros(0, np.float32)), col
