@@ -945,6 +945,40 @@ int sd_mesh_merge(const uint64_t* piece_ids_dev, const uint64_t* piece_vert_begi
                   uint64_t* tri_begin_dev, float* verts_out_dev, uint32_t* tris_out_dev, float* mesh_bb_dev, double* area_dev, uint64_t* counts_dev,
                   void* temp_dev, size_t temp_bytes, void* stream);
 
+/* ---- rendering locations of all objects of a vertex table (csrc/sd_locations.hip) ------------------------------------------------
+ * What the reference computes per supervoxel in SegmentationObject.sample_locations (reps/segmentation.py:700-732; the batch job
+ * batchjob_sample_location_caching.py, SuperSegmentationObject.sample_locations on top of it), for ALL objects of a table in one call.
+ * Object s owns verts_dev[vert_begin_dev[s] : vert_begin_dev[s + 1]] (uint64[n_obj + 1] ascending from 0 to n_verts, the layout of
+ * sd_mesh_build's vert_begin_dev).  Output, a CSR by object: loc_begin_dev uint64[n_obj + 1], loc_dev [loc_cap][3].  An object without
+ * vertices has no location.  With loc_cap == 0 nothing is emitted (the sizing call: counts[0] is the capacity the emitting call needs).
+ *   sd_locations_voxel    generate_rendering_locs (handler/multiviews.py:339-355), open3d's voxel_down_sample as open3d publishes it:
+ *                         verts_dev float32 (verts_f32 != 0) or float64 [n_verts][3]; per object in float64 vmin = min - 0.5 ds, voxel
+ *                         floor((p - vmin) / ds) per axis, a location = the sum of the voxel's vertices in ascending vertex order
+ *                         divided by their number; loc_dev double, ascending by voxel (ix, iy, iz), x most significant (open3d: the
+ *                         order of a hash map).
+ *   sd_locations_surface  surface_samples (reps/rep_helper.py:376-417): verts_dev float32; bin_sizes3 (host, 3 floats), r the ball's
+ *                         radius; max_nb_samples has no effect in the reference and is no argument.  histogramdd's float32 edges,
+ *                         the centre (b + 0.5) bin_size of every occupied bin in C order, the nearest vertex in float64 (lowest index on
+ *                         a tie), the ball ((dx dx) + dy dy) + dz dz <= r r around it, the float32 sum of its members in ascending
+ *                         vertex order, one float32 division, + the object's minimum; loc_dev float.  csrc/sd_locations.hip states the
+ *                         rule in full, tests/_locations_ref.py in numpy.
+ * An object may span at most SD_LOCATIONS_MAX_CELLS voxels / bins per axis (3 x 21 key bits).  counts_dev uint64[8], zeroed by every
+ * call: [0] locations, [1] != 0: loc_cap was smaller, nothing is written past it, [2] / [3] tiles visited / skipped by the surface
+ * rule, [4] != 0: an object beyond SD_LOCATIONS_MAX_CELLS, [5] != 0: a vertex is NaN or infinite, [7] != 0: the offsets do not ascend
+ * from 0 to n_verts (after [4], [5] or [7] the outputs are unusable; nothing is written outside them).  Every count per call stays
+ * below 2^31 (SD_ERR_INVALID beyond).  Asynchronous on the stream; no float atomics.  One grid stride of the 1D kernels is
+ * SD_LOCATIONS_GRID blocks of 256 threads, of the kernels with one wave per object or location SD_LOCATIONS_WAVE_GRID blocks of 4
+ * waves; neither constant rests on a measurement. */
+#define SD_LOCATIONS_GRID 1024
+#define SD_LOCATIONS_WAVE_GRID 4096
+#define SD_LOCATIONS_MAX_CELLS 2097152
+size_t sd_locations_voxel_temp_bytes(size_t n_verts, size_t n_obj);
+int sd_locations_voxel(const void* verts_dev, int verts_f32, const uint64_t* vert_begin_dev, size_t n_obj, size_t n_verts, double ds,
+                       uint64_t* loc_begin_dev, double* loc_dev, size_t loc_cap, uint64_t* counts_dev, void* temp_dev, size_t temp_bytes, void* stream);
+size_t sd_locations_surface_temp_bytes(size_t n_verts, size_t n_obj);
+int sd_locations_surface(const float* verts_dev, const uint64_t* vert_begin_dev, size_t n_obj, size_t n_verts, const float* bin_sizes3, double r,
+                         uint64_t* loc_begin_dev, float* loc_dev, size_t loc_cap, uint64_t* counts_dev, void* temp_dev, size_t temp_bytes, void* stream);
+
 /* ---- host-side helpers of the chunk pipeline (no GPU) -----------------------------------------------------------------
  * Multi-threaded strided copy of an (nz, ny, nx)-byte box between two uint8 host arrays whose x-rows are contiguous
  * (strides in bytes), and a multi-threaded memset: what numpy slicing does on one core when the reference cuts a chunk

@@ -21,6 +21,7 @@ SD_CELLASM_GRID = 1024
 SD_MESH_GRID = 256
 SD_GLIA_GRID = 1024
 SD_VIEWS_GRID, SD_VIEWS_RASTER_GRID, SD_VIEWS_MAX_VIEWS, SD_VIEWS_TILE_PX = 1024, 4096, 16, 32768
+SD_LOCATIONS_GRID, SD_LOCATIONS_WAVE_GRID, SD_LOCATIONS_MAX_CELLS = 1024, 4096, 1 << 21
 
 LIB_NAME = 'libsyconn_dense_hip.so'
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), os.environ.get('SD_LIB_NAME', LIB_NAME))
@@ -49,7 +50,8 @@ EXPORTS = ['sd_init', 'sd_device_count', 'sd_model_create', 'sd_model_destroy', 
            'sd_mesh_merge_temp_bytes', 'sd_mesh_merge', 'sd_glia_split_temp_bytes', 'sd_glia_split', 'sd_glia_pred',
            'sd_views_rotations_temp_bytes', 'sd_views_rotations', 'sd_views_flag_empty', 'sd_views_index_bytes', 'sd_views_index_temp_bytes', 'sd_views_index',
            'sd_views_candidates_temp_bytes', 'sd_views_candidates', 'sd_views_render_temp_bytes', 'sd_views_render', 'sd_views_render_index',
-           'sd_views_vote_temp_bytes', 'sd_views_vote']
+           'sd_views_vote_temp_bytes', 'sd_views_vote', 'sd_locations_voxel_temp_bytes', 'sd_locations_voxel', 'sd_locations_surface_temp_bytes',
+           'sd_locations_surface']
 
 
 class OpDesc(C.Structure):
@@ -254,6 +256,12 @@ def load():
     lib.sd_views_render_index.restype = i32
     lib.sd_views_vote_temp_bytes.argtypes = [sz, i32]; lib.sd_views_vote_temp_bytes.restype = sz
     lib.sd_views_vote.argtypes = [vp, vp, sz, C.c_uint32, sz, i32, i32, vp, vp, vp, vp, sz, vp]; lib.sd_views_vote.restype = i32
+    # reps/segmentation.py:700-732 (sample_locations), handler/multiviews.py:339-355 (generate_rendering_locs), reps/rep_helper.py:376-417
+    # (surface_samples): the rendering locations of all objects of a table in one call
+    lib.sd_locations_voxel_temp_bytes.argtypes = [sz, sz]; lib.sd_locations_voxel_temp_bytes.restype = sz
+    lib.sd_locations_voxel.argtypes = [vp, i32, vp, sz, sz, f64, vp, vp, sz, vp, vp, sz, vp]; lib.sd_locations_voxel.restype = i32
+    lib.sd_locations_surface_temp_bytes.argtypes = [sz, sz]; lib.sd_locations_surface_temp_bytes.restype = sz
+    lib.sd_locations_surface.argtypes = [vp, vp, sz, sz, f32p, f64, vp, vp, sz, vp, vp, sz, vp]; lib.sd_locations_surface.restype = i32
     _lib = lib
     return lib
 

@@ -105,9 +105,11 @@ DEFAULTS = {
     'glia': {'prior_astrocyte_removal': True, 'glia_thresh': 0.161489},
     'use_point_models': False,
     # views (config.yml:223-232): the organelle channels after the cell's ('sj' is rendered from 'syn_ssv' with on-the-fly views), the
-    # window edge in nm along the first principal axis, the window in pixels (x, y) and the views per location
+    # window edge in nm along the first principal axis, the window in pixels (x, y) and the views per location; the rule of the rendering
+    # locations (config.yml:225): generate_rendering_locs, else the legacy surface_samples
     'views': {
         'use_onthefly_views': True,
+        'use_new_renderings_locs': True,
         'subcell_objects': ['mi', 'vc', 'sj'],
         'view_properties': {'comp_window': 8000, 'ws': [256, 128], 'nb_views': 2},
     },

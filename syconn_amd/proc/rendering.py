@@ -297,3 +297,15 @@ def render_sso_coords_index_views(sso, coords: np.ndarray, verbose: bool = False
     meshes = [(ind, vert)] if len(vert) else [None]
     views, rot = render_views_table(meshes, coords, rot_mat, ws, nb_views, comp_window, index_views=True, device=device)
     return (views, rot) if return_rot_matrices else views
+
+
+def render_sampled_views(sso, ds_factor=None, index_views: bool = False, return_locations: bool = False, **render_kw):
+    """Views of a cell at its own rendering locations: ``sample_locations_sso`` of the cell's supervoxels (``sso.svs``), concatenated,
+    into ``render_sso_coords`` -- ``render_sso_coords_index_views`` with `index_views` --, whose keyword arguments `render_kw` are; with
+    `return_locations` ``(views, locations)``.  Locations and views are computed on the device; the locations cross the host between
+    the two."""
+    from ..reps.super_segmentation_helper import sample_locations_sso
+    parts = sample_locations_sso(sso, ds_factor, device=render_kw.get('device'))
+    locs = np.concatenate(parts) if parts else np.zeros((0, 3), np.float32)
+    views = (render_sso_coords_index_views if index_views else render_sso_coords)(sso, locs, **render_kw)
+    return (views, locs) if return_locations else views

@@ -375,3 +375,21 @@ def semseg2mesh(sso, semseg_key=None, nb_views=None, dest_path=None, k=1, colors
                                  vertices.astype(np.float64), int(k), device).astype(np.int32)
     col = maj_vote if colors is None else np.asarray(colors)[maj_vote].astype(np.uint8)
     return mesh[0], mesh[1], (mesh[2] if len(mesh) > 2 else np.zeros(0, np.float32)), col
+
+
+def sample_locations_sso(sso, ds_factor=None, device=None):
+    """What ``SuperSegmentationObject.sample_locations`` returns (reps/super_segmentation_object.py, over
+    ``SegmentationObject.sample_locations``, reps/segmentation.py:700-732) without the storages: the list of one float32 (k, 3) array of
+    rendering locations per entry of ``sso.svs``, each anything with ``.mesh`` (``[indices, vertices, ...]``), ``.rep_coord`` and
+    ``.scaling``.  One device call for the whole cell."""
+    from ..proc.locations import sample_locations_table
+    svs = list(sso.svs)
+    verts = [np.asarray(sv.mesh[1], np.float32).reshape(-1, 3) for sv in svs]
+    begin = np.concatenate(([0], np.cumsum([len(v) for v in verts]))).astype(np.uint64)
+    if not svs:
+        return []
+    table = sample_locations_table((np.arange(len(svs), dtype=np.uint64), begin, np.concatenate(verts)), ds_factor,
+                                   rep_coords=np.array([np.asarray(sv.rep_coord).reshape(3) for sv in svs]),
+                                   scaling=np.array([np.asarray(sv.scaling).reshape(3) for sv in svs]), device=device)
+    lb = table.loc_begin.astype(np.int64)
+    return [table.locations[lb[k]:lb[k + 1]] for k in range(len(svs))]
