@@ -283,6 +283,9 @@ def test_ring_form_is_bit_identical(gpu, monkeypatch):
     from syconn_amd.engine import DenseModel
     shapes = ((2, 96, 160, 160), (3, 64, 150, 170))
     sd = random_state_dict('semseg_axon', seed=12, final_scale=6.0)
+    # (planar NT = 3 layers run as 4-wave workgroups at every size since round 5; the 8-wave forms -- the ring form among them --
+    # are reached under SD_PLANAR_NT3_BIG only: without it both models below would run the same 4-wave kernels)
+    monkeypatch.setenv('SD_PLANAR_NT3_BIG', '1')
     monkeypatch.setenv('SD_NO_RING', '1')
     plain = DenseModel(sd, act_dtype='bf16', device=gpu)
     a = [plain.forward_batch(_input(sh, 5).to(gpu), L.SD_OUT_LOGITS_F32).clone() for sh in shapes]
@@ -292,6 +295,7 @@ def test_ring_form_is_bit_identical(gpu, monkeypatch):
         b = ring.forward_batch(_input(sh, 5).to(gpu), L.SD_OUT_LOGITS_F32, slot=1)
         assert torch.isfinite(b).all()
         assert torch.equal(ref, b), sh
+        assert any('NSLOT=-3' in k for _, k in ring.op_kernels()) and not any('NSLOT=-3' in k for _, k in plain.op_kernels())
 
 
 @pytest.mark.gpu
@@ -366,8 +370,10 @@ def test_fused_first_conv_is_bit_identical(gpu, monkeypatch):
     from syconn_amd import _lib as L
     from syconn_amd.engine import DenseModel
     # (semseg_axon / er: the 48-filter family -- a two-tile first convolution into three resident halo slots, round 4)
+    # (the last two: extents one past a multiple of the 1 x 32 x 16 blocks; W < 16)
     for arch, shape in (('semseg_spine', (12, 150, 170)), ('myelin', (9, 131, 77)), ('syntype', (16, 128, 144)),
-                        ('semseg_axon', (10, 140, 150)), ('er', (12, 150, 170))):
+                        ('semseg_axon', (10, 140, 150)), ('er', (12, 150, 170)), ('semseg_spine', (8, 129, 145)),
+                        ('myelin', (40, 480, 15))):
         model = build_unet(arch, seed=31, final_scale=4.0)
         raw = _input((2, *shape), 8).to(gpu)
         monkeypatch.setenv('SD_NO_FIRST_FUSE', '1')
@@ -414,7 +420,7 @@ def test_deferred_groupnorm_apply_is_bit_identical(gpu, monkeypatch, act):
     monkeypatch.delenv('SD_NO_GN_DEFER')
     fused = DenseModel(sd, act_dtype=act, device=gpu)
     assert fused.workspace_bytes((32, 48, 48)) >= 0
-    for shape in ((2, 16, 32, 48), (3, 13, 37, 43), (1, 32, 112, 144)):
+    for shape in ((2, 16, 32, 48), (3, 13, 37, 43), (1, 32, 112, 144), (1, 9, 33, 49), (2, 12, 40, 13)):      # (... one past a block multiple; W < 16)
         x = _input(shape, 3).to(gpu)
         for kind in (L.SD_OUT_LOGITS_F32, L.SD_OUT_PROBS_U8):
             a = plain.forward_batch(x, kind)
@@ -534,7 +540,7 @@ def test_groupnorm_raw_pooling_in_conv_epilogue_is_bit_identical(gpu, monkeypatc
     nofuse = DenseModel(sd, act_dtype=act, device=gpu)
     monkeypatch.delenv('SD_NO_GN_POOL_RAW')
     fused = DenseModel(sd, act_dtype=act, device=gpu)
-    for shape in ((2, 16, 32, 48), (3, 13, 37, 43), (1, 32, 112, 144)):
+    for shape in ((2, 16, 32, 48), (3, 13, 37, 43), (1, 32, 112, 144), (1, 9, 33, 49), (2, 12, 40, 13)):      # (... one past a block multiple; W < 16)
         x = _input(shape, 5).to(gpu)
         for kind in (L.SD_OUT_LOGITS_F32, L.SD_OUT_PROBS_U8):
             a = plain.forward_batch(x, kind).clone()
