@@ -914,7 +914,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == 12 ? 3 : 2) void k_conv_mfma(c
                 const char* const bcur = ldsB + (WRES ? s : RING ? gs % NW : (gs & 1)) * B_BYTES + lane * 16;
                 // ZROLL: the three stages of a chunk are the three KY rows of the stencil (the loop variable keeps its name); inside a stage
                 // the taps run kx-major, kz-minor -- every output is summed in the order (chunk, ky, kx, kz) (the weight groups are packed in
-                // that order, sd_api.hip).  A wave's voxel tiles are z-neighbours, so tile i at kz reads the halo plane
+                // that order, pack_conv in sd_plan.cpp).  A wave's voxel tiles are z-neighbours, so tile i at kz reads the halo plane
                 // tile i + 1 reads at kz - 1: with kz innermost a fragment serves up to three MFMA rows (MT = 4 below).
                 // (ZROLL = 3x3x3 layers with NT <= 2.  The NT = 3 forms -- the 48-filter family, two voxel tiles per wave, nothing to share --
                 // keep kz stages and the order (chunk, kz, ky, kx): which order a LAYER is summed in depends on its channel count alone,
@@ -1474,7 +1474,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == 12 ? 3 : 2) void k_conv_mfma(c
 #endif
     // (the pooled tensor first: its window maxima read the packed values, the row stores below may then trade them in place)
     // ---- fused MaxPool(ceil_mode): (kz,2,2) window = {the wave's two tiles (3D)} x {lane^16 (y)} x {lane^1 (x)} ----
-    // Only planned behind a ReLU (sd_api.hip): all values are >= 0, so the packed integer max is the float max and
+    // Only planned behind a ReLU (sd_plan.cpp: pool_sign_ok): all values are >= 0, so the packed integer max is the float max and
     // voxels beyond the volume contribute 0.
     if (p.pool_dst) {
         T* const pdst = reinterpret_cast<T*>(reinterpret_cast<char*>(p.pool_dst) + (size_t)tn * p.tstride);

@@ -63,7 +63,7 @@ __device__ __forceinline__ unsigned pk_max16(unsigned a, unsigned b) {
     return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s2, a), __builtin_bit_cast(s2, b)));
 }
 
-// Planar first convolution (1 -> 32 channels) on UINT8 input as two bf16 MFMAs (weight layout: sd_api.hip, `w3_off`).  The input
+// Planar first convolution (1 -> 32 channels) on UINT8 input as two bf16 MFMAs (weight layout: pack_first_u8 in sd_plan.cpp, `w3_off`).  The input
 // patch holds every voxel as the dword (bf16(v), bf16(v)) -- a uint8 is exact in bf16 --, r[0..4] = this lane's five patch reads
 // (lanes 0-31: taps 0-4; lanes 32-63: taps 5-8 and the constant dword (1.0, 1.0), which meets the bias parts).  Products
 // v * weight part are exact in fp32, the accumulation is the matrix core's fp32: conv(float32(v) / 255) to fp32 rounding.

@@ -14,16 +14,15 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstring>
 #include <string>
 #include <vector>
 
 int sd_fail_msg(int code, const char* msg);
 
-namespace {
+using sdplan::Dims;
+using sdplan::rup_sz;
 
-struct Dims3 { int d = 0, h = 0, w = 0; };
-inline size_t rup_sz(size_t v, size_t m) { return (v + m - 1) / m * m; }
+namespace {
 
 struct FOp {
     sd_op_desc d{};
@@ -364,50 +363,20 @@ struct sd_f32_model {
     int nbuf = 0;
     std::vector<int> bufC;
     float* blob = nullptr;
-    std::vector<Dims3> dims;
+    std::vector<Dims> dims;
     std::vector<size_t> buf_off;
     int final_cout = 0;
 };
 
 namespace {
 
-int infer32(const sd_f32_model* m, int D, int H, int W, std::vector<Dims3>& dims) {
-    dims.assign(m->nbuf, Dims3{});
-    dims[0] = {D, H, W};
-    for (const FOp& op : m->ops) {
-        const sd_op_desc& d = op.d;
-        switch (d.kind) {
-        case SD_OP_CONV: {
-            const Dims3 a = dims[d.src0];
-            Dims3 o = a;
-            if (d.src1 >= 0) {
-                o = dims[d.src1];
-                if (a.d < o.d || a.h < o.h || a.w < o.w) return sd_fail_msg(SD_ERR_INVALID, "merge conv: src0 smaller than src1");
-            }
-            if (o.d <= 0) return sd_fail_msg(SD_ERR_INVALID, "conv input not produced yet");
-            dims[d.dst] = o;
-            break;
-        }
-        case SD_OP_POOL: {
-            const Dims3 a = dims[d.src0];
-            dims[d.dst] = {d.kz == 2 ? (a.d + 1) / 2 : a.d, (a.h + 1) / 2, (a.w + 1) / 2};
-            break;
-        }
-        case SD_OP_UPCONV: {
-            const Dims3 a = dims[d.src0];
-            dims[d.dst] = {a.d * d.kz, a.h * 2, a.w * 2};
-            break;
-        }
-        default: break;
-        }
-    }
-    return SD_OK;
-}
-
-// one range per buffer from its writer to its last reader; disjoint lifetimes share memory (first fit)
-size_t plan32(const sd_f32_model* m, const std::vector<Dims3>& dims, std::vector<size_t>& off) {
+// Shapes and workspace of one tile: one range per buffer from its writer to its last reader; disjoint lifetimes share memory
+// (sd_plan.h: place_buffers) unless SD_KEEP_ALL / SD_NO_WS_REUSE say that layer-wise debugging reads buffers back (read per call).
+int layout32(const sd_f32_model* m, int D, int H, int W, std::vector<Dims>& dims, std::vector<size_t>& off, size_t& tstride) {
+    std::string err;
+    const int rc = sdplan::infer_shapes(m->ops, m->nbuf, D, H, W, dims, err);
+    if (rc != SD_OK) return sd_fail_msg(rc, err.c_str());
     const int nb = m->nbuf, nops = (int)m->ops.size();
-    off.assign(nb, 0);
     std::vector<size_t> bytes(nb, 0);
     for (int b = 1; b < nb; ++b) bytes[b] = rup_sz((size_t)dims[b].d * dims[b].h * dims[b].w * m->bufC[b] * 4, 256);
     std::vector<int> first(nb, nops), last(nb, -1);
@@ -417,28 +386,9 @@ size_t plan32(const sd_f32_model* m, const std::vector<Dims3>& dims, std::vector
         rd(d.src0); rd(d.src1);
         if (d.kind != SD_OP_FINAL && d.kind != SD_OP_GROUPNORM && d.dst > 0) { first[d.dst] = std::min(first[d.dst], i); last[d.dst] = std::max(last[d.dst], i); }
     }
-    const bool no_reuse = getenv("SD_KEEP_ALL") || getenv("SD_NO_WS_REUSE");     // layer-wise debugging reads buffers back
-    std::vector<int> order;
-    for (int b = 1; b < nb; ++b)
-        if (last[b] >= 0 && bytes[b]) order.push_back(b);
-    std::sort(order.begin(), order.end(), [&](int a, int b) { return first[a] != first[b] ? first[a] < first[b] : a < b; });
-    std::vector<int> placed;
-    size_t top = F32_SCRATCH;
-    for (int b : order) {
-        std::vector<std::pair<size_t, size_t>> busy;
-        for (int q : placed)
-            if (no_reuse || (first[q] <= last[b] && first[b] <= last[q])) busy.push_back({off[q], off[q] + bytes[q]});
-        std::sort(busy.begin(), busy.end());
-        size_t cur = F32_SCRATCH;
-        for (const auto& r : busy) {
-            if (cur + bytes[b] <= r.first) break;
-            cur = std::max(cur, r.second);
-        }
-        off[b] = cur;
-        top = std::max(top, cur + bytes[b]);
-        placed.push_back(b);
-    }
-    return top;
+    const sdplan::PlanSwitches sw = sdplan::read_plan_switches();
+    tstride = rup_sz(sdplan::place_buffers(first, last, bytes, F32_SCRATCH, !sw.keep_all && !sw.no_ws_reuse, off), 256);
+    return SD_OK;
 }
 
 }  // namespace
@@ -567,17 +517,17 @@ int f32_final_cout(const sd_f32_model* m) { return m->final_cout; }
 int f32_buf_channels(const sd_f32_model* m, int b) { return (b >= 0 && b < m->nbuf) ? m->bufC[b] : 0; }
 
 size_t f32_workspace_bytes(sd_f32_model* m, int D, int H, int W) {
-    std::vector<Dims3> dims;
+    std::vector<Dims> dims;
     std::vector<size_t> off;
-    if (infer32(m, D, H, W, dims) != SD_OK) return 0;
-    return rup_sz(plan32(m, dims, off), 256);
+    size_t tstride = 0;
+    return layout32(m, D, H, W, dims, off, tstride) == SD_OK ? tstride : 0;
 }
 
 int f32_forward(sd_f32_model* m, const void* in_dev, int in_dtype, int N, int D, int H, int W, void* out_dev, int out_kind,
                 const LabelArgs* lab, void* ws, size_t ws_bytes, hipStream_t s, hipEvent_t* ev) {
-    int rc = infer32(m, D, H, W, m->dims);
+    size_t tstride = 0;
+    int rc = layout32(m, D, H, W, m->dims, m->buf_off, tstride);
     if (rc != SD_OK) return rc;
-    const size_t tstride = rup_sz(plan32(m, m->dims, m->buf_off), 256);
     if ((size_t)N * tstride > ws_bytes) return sd_fail_msg(SD_ERR_NOMEM, "workspace too small");
     const size_t in_tstride = (size_t)D * H * W * (in_dtype == SD_U8 ? 1 : 4);
     const size_t out_tstride = out_kind == SD_OUT_LABELS_U8 ? (size_t)D * H * W
@@ -591,12 +541,12 @@ int f32_forward(sd_f32_model* m, const void* in_dev, int in_dtype, int N, int D,
         if (ev && hipEventRecord(ev[i], s) != hipSuccess) return sd_fail_msg(SD_ERR_HIP, "hipEventRecord");
         switch (d.kind) {
         case SD_OP_CONV: {
-            const Dims3 o = m->dims[d.dst], a = m->dims[d.src0];
+            const Dims o = m->dims[d.dst], a = m->dims[d.src0];
             Conv32 p{};
             p.in0 = d.src0 == 0 ? in_dev : (const void*)bufp(d.src0);
             p.in0_is_input = d.src0 == 0; p.C0 = d.cin0; p.H0 = a.h; p.W0 = a.w; p.P0 = (size_t)a.d * a.h * a.w;
             if (d.src1 >= 0) {
-                const Dims3 b = m->dims[d.src1];
+                const Dims b = m->dims[d.src1];
                 p.in1 = bufp(d.src1); p.C1 = d.cin1; p.H1 = b.h; p.W1 = b.w; p.P1 = (size_t)b.d * b.h * b.w;
             }
             p.dst = bufp(d.dst); p.Cout = d.cout; p.D = o.d; p.H = o.h; p.W = o.w;
@@ -607,13 +557,13 @@ int f32_forward(sd_f32_model* m, const void* in_dev, int in_dtype, int N, int D,
             break;
         }
         case SD_OP_POOL: {
-            const Dims3 a = m->dims[d.src0], o = m->dims[d.dst];
+            const Dims a = m->dims[d.src0], o = m->dims[d.dst];
             Pool32 p{bufp(d.src0), bufp(d.dst), m->bufC[d.src0], a.d, a.h, a.w, o.d, o.h, o.w, d.kz, tstride};
             k32_pool<<<dim3(grid_for((size_t)p.C * o.d * o.h * o.w), 1, N), 256, 0, s>>>(p);
             break;
         }
         case SD_OP_UPCONV: {
-            const Dims3 a = m->dims[d.src0];
+            const Dims a = m->dims[d.src0];
             Up32 p{};
             p.src = bufp(d.src0); p.Cin = d.cin0; p.D = a.d; p.H = a.h; p.W = a.w; p.dst = bufp(d.dst); p.Cout = d.cout; p.kz = d.kz;
             p.w = fp(op.w_off); p.bias = fp(op.bias_off); p.alpha = fp(op.alpha_off); p.beta = fp(op.beta_off);
@@ -624,8 +574,8 @@ int f32_forward(sd_f32_model* m, const void* in_dev, int in_dtype, int N, int D,
             break;
         }
         case SD_OP_GROUPNORM: {
-            const Dims3 a = m->dims[d.src0];
-            const Dims3 r = d.src1 >= 0 ? m->dims[d.src1] : a;
+            const Dims a = m->dims[d.src0];
+            const Dims r = d.src1 >= 0 ? m->dims[d.src1] : a;
             Gn32 p{};
             p.buf = bufp(d.src0); p.C = m->bufC[d.src0]; p.groups = d.groups;
             p.D = r.d; p.H = r.h; p.W = r.w; p.Hs = a.h; p.Ws = a.w; p.P = (size_t)a.d * a.h * a.w;
@@ -640,7 +590,7 @@ int f32_forward(sd_f32_model* m, const void* in_dev, int in_dtype, int N, int D,
             break;
         }
         case SD_OP_FINAL: {
-            const Dims3 a = m->dims[d.src0];
+            const Dims a = m->dims[d.src0];
             if (a.d != D || a.h != H || a.w != W) return sd_fail_msg(SD_ERR_INVALID, "final layer shape != input shape");
             Final32 p{};
             p.src = bufp(d.src0); p.Cin = d.cin0; p.w = fp(op.w_off); p.bias = fp(op.bias_off); p.cout = d.cout;
@@ -659,7 +609,7 @@ int f32_forward(sd_f32_model* m, const void* in_dev, int in_dtype, int N, int D,
 
 int f32_read_buffer(sd_f32_model* m, int buf, const void* ws, float* out, int32_t* dims4, hipStream_t s) {
     if (buf <= 0 || buf >= m->nbuf || m->dims.empty()) return sd_fail_msg(SD_ERR_INVALID, "sd_debug_read_buffer: bad argument");
-    const Dims3 a = m->dims[buf];
+    const Dims a = m->dims[buf];
     if (dims4) { dims4[0] = m->bufC[buf]; dims4[1] = a.d; dims4[2] = a.h; dims4[3] = a.w; }
     if (!out) return SD_OK;
     const size_t n = (size_t)m->bufC[buf] * a.d * a.h * a.w * 4;

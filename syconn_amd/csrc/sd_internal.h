@@ -1,9 +1,11 @@
-// Internal interface between the host-side plan executor (sd_api.hip) and the gfx950 kernels (sd_kernels.hip).
+// Internal interface between the host-side plan executor (sd_api.hip; the plan itself: sd_plan.h) and the gfx950 kernels
+// (sd_kernels.hip).
 // Nothing here is part of the C ABI (include/syconn_dense.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/syconn_dense.h"
+#include "sd_plan.h"      // SD_CHUNK, SD_GN_SCALE_OFF, upconv_rows_kernel
 
 // Activation tensors are CHANNEL-BLOCKED: a "chunk" is 16 consecutive channels = one MFMA k-step, and element
 // (chunk k, z, y, x, c) sits at ((k*P + (z*H + y)*W + x)*16 + c) with P = D*H*W the voxels of the buffer's own
@@ -14,7 +16,6 @@
 // byte offset t*tstride (all tiles share one workspace layout, so the same offset applies to every activation
 // buffer and scratch pointer of a launch); the network input / final output of tile t sit t*in_tstride /
 // t*out_tstride bytes after tile 0's.
-constexpr int SD_CHUNK = 16;
 constexpr int SD_CONV_PARAM_BYTES = 512;     // k_conv_mfma LDS constants: folded bias (<= 96 floats) + 8 class biases
 
 // geometry of one workgroup of the first-layer convolution: 256 output voxels = 8 MFMA column tiles of
@@ -87,7 +88,7 @@ struct FirstParams {
     void* dst;
     int Cd;
     const float* wpack;  // [ntile][nstep][64 lanes] float
-    const void* wpack3;  // planar first conv on uint8 input, bf16 / fp16 plans: [ntile][2 MFMAs][64 lanes][8] bf16 (sd_api.hip), or nullptr
+    const void* wpack3;  // planar first conv on uint8 input, bf16 / fp16 plans: [ntile][2 MFMAs][64 lanes][8] bf16 (sd_plan.cpp), or nullptr
     const float* bias;   // padded to ntile*32
     int relu;
     int nbx, nby, nbz;
@@ -197,13 +198,9 @@ inline size_t conv_gn_lds_per_tile(int nchunks) { return (size_t)nchunks * 128; 
 bool conv_can_fuse_first(int KZ, int NT, int NB, long vox_all_tiles, int nstages, bool fused_final);
 int launch_first(const FirstParams& p, int act_dtype, int in_dtype, int KZ, hipStream_t s);
 int launch_upconv(const UpconvParams& p, int act_dtype, int NB, hipStream_t s);
-bool upconv_rows_kernel(int nchunk, int Cd);   // shapes served by k_upconv_rows (see sd_kernels.hip)
 int launch_pool(const PoolParams& p, int act_dtype, hipStream_t s);
 int launch_final(const FinalParams& p, int act_dtype, hipStream_t s);
 int launch_groupnorm(const GnParams& p, int act_dtype, hipStream_t s);
-// workspace scratch (first 64 KiB of a tile's workspace): [0, SD_GN_SCALE_OFF) GroupNorm sums (2 * C doubles, zero between ops),
-// [SD_GN_SCALE_OFF, 64 KiB) scale / shift of a GroupNorm whose apply is not deferred (2 * C floats)
-#define SD_GN_SCALE_OFF ((size_t)40960)
 int launch_zero_scratch(void* ws, size_t tstride, int nbytes, int batch, hipStream_t s);
 int launch_tile_gather(const void* vol, int esize, int VD, int VH, int VW, int oz, int oy, int ox, void* tile, int TD,
                        int TH, int TW, hipStream_t s);

@@ -1175,15 +1175,6 @@ static int launch_upconv_rows_wl_g(const UpconvParams& p, hipStream_t s) {
     hipLaunchKernelGGL(kern, grid, block, lds, s, p);
     return SD_LAUNCH_CHECK();
 }
-// true when launch_upconv runs this shape with the row-coalescing kernel (activations of all chunks in registers): the form
-// into which a deferred GroupNorm apply folds for less than the separate apply pass costs (the generic MFMA kernel pays
-// more for it than the pass it replaces: 192 -> 96 channels 80 -> 108 us vs a 10 us pass)
-bool upconv_rows_kernel(int nchunk, int Cd) {
-    static const bool no_wl = getenv("SD_NO_UPCONV_WL") != nullptr;
-    return (nchunk == 4 && Cd == 32) || (nchunk == 3 && Cd == 32) || (nchunk == 2 && Cd == 16) || (nchunk == 8 && Cd == 64 && !no_wl) ||
-           (nchunk == 6 && Cd == 48) || (nchunk == 12 && Cd == 96 && !no_wl);
-}
-
 template <typename T>
 static int launch_upconv_t(const UpconvParams& p, int NB, hipStream_t s) {
     SD_NOTE_KERNEL("k_upconv_mfma");      // (the row-kernel launchers below overwrite it)

@@ -10,27 +10,27 @@ What is restated, and from where
 --------------------------------
 * plan.py `plan_from_unet_state_dict` / `plan_from_sequential` (lines 58-180): an op is an `OpDesc` (kind, src0, src1, dst,
   cin0, cin1, cout, kz, relu, norm, groups, eps, offsets into the float32 blob).  A convolution with `src1 >= 0` reads the
-  concatenation (src0, src1) in that order (plan.py:130, weight input-channel axis: sd_api.hip:506-513); src0 (the
-  up-convolved tensor, 2x the level below) is cropped at the high end to src1's extent (sd_api.hip:148-153).  A GROUPNORM op
-  works in place on `src0`; its `src1`, if any, only lends the extent of the region (plan.py:81-83, sd_api.hip:1424-1427).
-* BatchNorm fold, sd_api.hip:367-380 (`fold_bn`), in float32 and in this order: ``s = gamma / sqrt(var + eps)``,
-  ``shift = beta - mean * s``; weights ``w * s`` (sd_api.hip:407-409, 569), bias ``b * s + shift`` (sd_api.hip:427, 521, 574).
+  concatenation (src0, src1) in that order (plan.py:130, weight input-channel axis: `pack_conv` in sd_plan.cpp); src0 (the
+  up-convolved tensor, 2x the level below) is cropped at the high end to src1's extent (`infer_shapes`, sd_plan.h).  A GROUPNORM op
+  works in place on `src0`; its `src1`, if any, only lends the extent of the region (plan.py:81-83, `launch_groupnorm_op` in sd_api.hip).
+* BatchNorm fold, `Builder::fold_bn` in sd_plan.cpp, in float32 and in this order: ``s = gamma / sqrt(var + eps)``,
+  ``shift = beta - mean * s``; weights ``w * s`` (`wat`, `add_upconv`), bias ``b * s + shift`` (`folded_bias`; all in sd_plan.cpp).
 * Weight rounding, what the packing was found to do:
   - convolutions that do not read the network input and up-convolutions: the folded float32 weight is rounded to the storage
-    type (round to nearest even, sd_api.hip:35-48, 518, 570); the bias stays float32.  The reference rounds the same float32
+    type (round to nearest even: `cvt` in `pack_conv` / `add_upconv`, sd_plan.cpp); the bias stays float32.  The reference rounds the same float32
     product with torch's conversion, so its weights are the device's bit for bit.
-  - the FIRST convolution keeps float32 weights (sd_api.hip:416-427): `k_conv_first<... f32 MFMA chain>` multiplies them with
+  - the FIRST convolution keeps float32 weights (`pack_first_f32`, sd_plan.cpp): `k_conv_first<... f32 MFMA chain>` multiplies them with
     ``float32(v) / 255`` (sd_kernels.hip:53) -- form ``'f32_chain'``, also the float32-input form.  A planar first
     convolution with uint8 input runs on the exact uint8 values with ``float32(float64(w) / 255)`` carried as three bf16
-    parts = all 24 mantissa bits (sd_api.hip:428-467) -- form ``'u8_mfma'``; the bias is float32 in both.
-  - the FINAL 1x1x1 layer: the matrix-core forms (`k_final_mfma`, sd_api.hip:602-621, and the final layer fused into the
-    last convolution's epilogue, sd_api.hip:835-854) carry each float32 weight as ``hi + lo`` with ``hi = round_s(w)``,
+    parts = all 24 mantissa bits (`pack_first_u8`, sd_plan.cpp) -- form ``'u8_mfma'``; the bias is float32 in both.
+  - the FINAL 1x1x1 layer: the matrix-core forms (`k_final_mfma`, `add_final`, and the final layer fused into the
+    last convolution's epilogue, `fuse_final`; both pack with `pack_hilo_frags`, sd_plan.cpp) carry each float32 weight as ``hi + lo`` with ``hi = round_s(w)``,
     ``lo = round_s(w - hi)`` in the storage type: 16 mantissa bits for bf16, 22 for f16, NOT the float32 weight -- form
     ``'hilo'``.  The scalar `k_final` (float32 weights, form ``'f32'``) only runs from 481 padded input channels on
-    (sd_kernels.hip:1311-1312), which no network of the path has.  The bias is float32.
-* Pooling: ceil-mode maximum over (kz, 2, 2) windows (sd_api.hip:156-159, sd_kernels.hip:490-530): exact.
-* Up-convolution: stride = kernel = (kz, 2, 2), weight layout [cin][cout][kz][2][2] (plan.py:118, sd_api.hip:565-569); the
-  buffer holds the uncropped 2x tensor (sd_api.hip:161-164).
+    (`launch_final`, sd_kernels.hip), which no network of the path has.  The bias is float32.
+* Pooling: ceil-mode maximum over (kz, 2, 2) windows (`infer_shapes` in sd_plan.h, sd_kernels.hip:490-530): exact.
+* Up-convolution: stride = kernel = (kz, 2, 2), weight layout [cin][cout][kz][2][2] (plan.py:118, `add_upconv` in sd_plan.cpp); the
+  buffer holds the uncropped 2x tensor (`infer_shapes`).
 * GroupNorm (sd_kernels.hip:724-913): the producer's output is rounded to storage, per-channel sums of the STORED values
   over the region become per-group mean / biased variance in double, ``scale = float32(rstd * gamma)``,
   ``shift = float32(beta - mean * rstd * gamma)``, ``y = relu(x * scale + shift)`` in fp32, rounded to storage; outside the
@@ -148,7 +148,7 @@ class StepRef:
         return self.blob[off:off + n]
 
     def _fold(self, d):
-        """(scale, shift) per output channel: sd_api.hip `fold_bn`, float32 in the device's order (float64 if exact)."""
+        """(scale, shift) per output channel: sd_plan.cpp `fold_bn`, float32 in the device's order (float64 if exact)."""
         ft = np.float64 if self.exact else np.float32
         if d.norm != 1:
             return np.ones(d.cout, ft), np.zeros(d.cout, ft)
