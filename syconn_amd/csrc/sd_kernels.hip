@@ -480,6 +480,211 @@ __global__ __launch_bounds__(256) void k_upconv_rows(const UpconvParams p) {
     sguard.flush(p.ovf);
 }
 
+__device__ __forceinline__ void ds_write8(uint32_t addr, __attribute__((ext_vector_type(2))) unsigned v) {      // 8 bytes per lane (lgkmcnt)
+    asm volatile("ds_write_b64 %0, %1" ::"v"(addr), "v"(v) : "memory");
+}
+template <typename V> __device__ __forceinline__ void gload16(V& r, const void* g) {      // 16 bytes per lane, completion via a hand-placed vmcnt wait
+    static_assert(sizeof(V) == 16, "global_load_dwordx4");
+    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(r) : "v"(g) : "memory");
+}
+// K5, one-pass form of the row kernel: the LDS-weight forms above read the input planes once per (z-tap, y-tap) pair and channel
+// group, because a workgroup keeps only its own pair's weights.  Here a workgroup of 8 waves is persistent over groups of 256 input
+// voxels, a wave's activation fragments xf[NCH] stay in registers across ALL pairs and channel groups of its 32 voxels (the input
+// is requested once; FETCH_SIZE says the repeated reads of the old forms hit in L2, so what is saved is L2 requests, not HBM
+// bytes), and the weights are what moves: one STEP = NT column tiles (NT / 2 tiles = 16 NT / 2 channels of
+// BOTH x-taps of one pair, the tile numbering of the G > 1 form above), NT * NCH KiB of fragments that LDS-DMA streams from L2
+// into one of two slots while the other slot computes.  Per step and wave, in issue order:
+//     MFMAs of step s (slot s & 1) | wait: own DMA pieces of step s+1 | barrier | DMA of step s+2 -> slot s & 1 |
+//     [step 0: the next voxel group's xf loads] | rows of step s through the wave's LDS tile -> global stores
+// One barrier per step: behind it every wave has finished reading slot s & 1 and every wave's pieces of step s+1 have landed.
+// The wait is counted: vmcnt completes in issue order, and behind the DMA of step s+1 a wave has issued only the next group's
+// loads and the NST row stores of step s-1, so `vmcnt(NST)` leaves exactly those stores in flight -- a drain there would empty
+// the store queues of the whole workgroup at every barrier.  That count holds only where all NST stores were issued, i.e. for a
+// wave whose 32 voxels all exist; any other wave waits for vmcnt(0).  More outstanding operations than counted make the wait
+// stricter, never weaker.  Invalid voxels load a clamped address and store nothing.
+// Arithmetic as above: bias (here from an LDS copy), then the input chunks in order, one rounding -- bit-identical rows.
+template <typename T, int NCH, int NTAB, int NT>
+__global__ __launch_bounds__(512) void k_upconv_rows1(const UpconvParams p) {
+    constexpr int WAVES = 8;
+    static_assert(NT % 2 == 0 && NTAB % NT == 0 && (NT * NCH) % WAVES == 0, "whole tiles of each x-tap per step, whole DMA rounds");
+    using v8 = typename Act<T>::v8;
+    using v4 = typename Act<T>::v4;
+    typedef __attribute__((ext_vector_type(4))) unsigned u4;
+    constexpr int NQ = NTAB / NT;            // steps (channel groups) per pair
+    constexpr int TPT = NT / 2;              // column tiles per x-tap in a step
+    constexpr int CD = NT * 16;              // channels a step computes
+    constexpr int ROW = 4 * CD;              // bytes per input voxel per step: 2 taps * CD * 2 B
+    constexpr int PPV = ROW / 16;
+    constexpr int SWM = 7;
+    static_assert(PPV % 8 == 0, "XOR mask must divide the row");
+    constexpr int NST = (32 * PPV) / 64;     // row stores per wave and step
+    constexpr int SLOT = NT * NCH * 1024;    // bytes of weight fragments per step
+    constexpr int KD = NT * NCH / WAVES;     // DMA instructions per wave and step
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, vl = lane & 31;
+    char* const tile = smem + wave * (32 * ROW);
+    char* const slots = smem + WAVES * 32 * ROW;
+    const float* const bl = reinterpret_cast<const float*>(slots + 2 * SLOT);
+    const long M = (long)p.D * p.H * p.W;
+    const T* const src = reinterpret_cast<const T*>(reinterpret_cast<const char*>(p.src) + blockIdx.z * p.tstride);
+    const char* const wp = reinterpret_cast<const char*>(p.wpack);
+    char* const dst = reinterpret_cast<char*>(p.dst) + blockIdx.z * p.tstride;
+    const int H2 = p.Hd, W2 = p.Wd;
+    const int NS = 2 * p.kz * NQ;            // steps per voxel group (even: the slot of step s is s & 1 in every group)
+    StoreGuard<T> sguard;
+
+    auto tile_of = [&](int ab, int q, int jl) { return ab * NTAB + (jl / TPT) * (NTAB / 2) + q * TPT + jl % TPT; };
+    // step st -> its slot: [local tile][chunk][64 lanes] x 16 bytes; in the packed image tile t is half (t & 1) of block t >> 1
+    auto dma_step = [&](int st) {
+        const int ab = st / NQ, q = st - ab * NQ;
+        char* const sl = slots + (st & 1) * SLOT;
+#pragma unroll
+        for (int k = 0; k < KD; ++k) {
+            const int i = wave + k * WAVES, jl = i / NCH, c = i - jl * NCH, tl = tile_of(ab, q, jl);
+            glds16(wp + ((((size_t)(tl >> 1) * NCH + c) * 2 + (tl & 1)) * 64 + lane) * 16, sl + i * 1024);
+        }
+    };
+    auto load_x = [&](v8 (&x)[NCH], long m0) {
+        const long mm = m0 + vl;
+        const size_t sidx = upconv_src_index(p, mm < M ? mm : M - 1);
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) gload16(x[c], src + ((size_t)c * p.Ps + sidx) * SD_CHUNK + half * 8);
+    };
+
+    for (int i = tid; i < NS * NT * 32; i += WAVES * 64) const_cast<float*>(bl)[i] = p.bias[i];
+    dma_step(0);
+    dma_step(1);
+    const long NG = (M + WAVES * 32 - 1) / (WAVES * 32);
+    v8 xf[NCH], xn[NCH];
+    load_x(xf, ((long)blockIdx.x * WAVES + wave) * 32);
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) tie(xf[c]);
+
+    for (long gi = blockIdx.x; gi < NG; gi += gridDim.x) {
+        const long m0 = (gi * WAVES + wave) * 32;
+        const bool full = __builtin_amdgcn_readfirstlane((int)(m0 + 32 <= M)) != 0;
+        // a lane stores pieces of only TWO input voxels (v = lane / 4 in even store iterations, 16 + lane / 4 in odd ones)
+        size_t ov0[2];
+        bool okv[2];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const long mm = m0 + (lane >> 2) + 16 * e;
+            okv[e] = mm < M;
+            const unsigned mu = (unsigned)(okv[e] ? mm : 0), xy = mu % (unsigned)(p.W * p.H), z = mu / (unsigned)(p.W * p.H);
+            const unsigned y = xy / (unsigned)p.W, x = xy - y * (unsigned)p.W;
+            ov0[e] = ((size_t)(z * p.kz) * H2 + 2 * y) * W2 + 2 * x;
+        }
+#pragma unroll 1
+        for (int st = 0; st < NS; ++st) {
+            const int ab = st / NQ, q = st - ab * NQ;
+            const char* const wl = slots + (st & 1) * SLOT;
+            // Every LDS access of the step loop is explicit (ds_read16 / ds_write8, completion via hand-placed lgkmcnt waits): before
+            // an LDS access it can see, the compiler waits for ALL LDS-DMA in flight (vmcnt(0): it cannot count the predicated row
+            // stores behind it), which would drain the store queues at every step.
+            f32x16 acc[NT];
+            {
+                f32x4 bq[NT][4];
+#pragma unroll
+                for (int j = 0; j < NT; ++j) {
+                    const uint32_t ba = lds_addr(bl) + (32 * tile_of(ab, q, j) + 4 * half) * 4;
+                    ds_read16<0>(bq[j][0], ba); ds_read16<32>(bq[j][1], ba); ds_read16<64>(bq[j][2], ba); ds_read16<96>(bq[j][3], ba);
+                }
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+                for (int j = 0; j < NT; ++j)
+#pragma unroll
+                    for (int qq = 0; qq < 4; ++qq) {
+                        tie(bq[j][qq]);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) acc[j][4 * qq + e] = bq[j][qq][e];
+                    }
+            }
+            // weight fragments one chunk ahead of the MFMAs that use them (LDS reads complete in order)
+            const uint32_t wa = lds_addr(wl) + lane * 16;
+            v8 wq[2][NT];
+            static_for<NT>([&](auto j) { ds_read16<decltype(j)::value * NCH * 1024>(wq[0][decltype(j)::value], wa); });
+            static_for<NCH>([&](auto cc) {
+                constexpr int c = decltype(cc)::value;
+                if constexpr (c + 1 < NCH) {
+                    static_for<NT>([&](auto j) { ds_read16<(decltype(j)::value * NCH + c + 1) * 1024>(wq[(c + 1) & 1][decltype(j)::value], wa); });
+                    asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(NT) : "memory");
+                } else {
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                }
+#pragma unroll
+                for (int j = 0; j < NT; ++j) {
+                    tie(wq[c & 1][j]);
+                    acc[j] = Act<T>::mfma(wq[c & 1][j], xf[c], acc[j]);
+                }
+            });
+            if (full) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(NST) : "memory");
+            else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            // the next group's fragments were requested in step 0 behind the DMA of step 2: the wait of step 1 has covered them.  (Loads
+            // the compiler can see would make it wait vmcnt(0) before the MFMAs of EVERY step: gload16.)
+            if (st == 1) {
+#pragma unroll
+                for (int c = 0; c < NCH; ++c) tie(xn[c]);
+            }
+            if (st == NS - 1) {
+#pragma unroll
+                for (int c = 0; c < NCH; ++c) xf[c] = xn[c];
+                asm volatile("" ::: "memory");
+            }
+            dma_step(st + 2 < NS ? st + 2 : st + 2 - NS);
+            asm volatile("" ::: "memory");
+            if (st == 0) {
+                load_x(xn, ((gi + gridDim.x) * WAVES + wave) * 32);
+                asm volatile("" ::: "memory");
+            }
+            // accumulators -> rounded rows in the wave's LDS tile: voxel vl, columns 32j + 8qq + 4*half + e
+#pragma unroll
+            for (int j = 0; j < NT; ++j)
+#pragma unroll
+                for (int qq = 0; qq < 4; ++qq) {
+                    v4 o;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        float v = acc[j][4 * qq + e];
+                        if (p.relu) v = fmaxf(v, 0.f);
+                        o[e] = (T)v;
+                    }
+                    typedef __attribute__((ext_vector_type(2))) unsigned u2g;
+                    const u2g ob = __builtin_bit_cast(u2g, o);
+                    sguard.see_signed(ob.x); sguard.see_signed(ob.y);
+                    const int pc = (4 * j + qq) ^ (vl & SWM);
+                    ds_write8(lds_addr(tile) + vl * ROW + pc * 16 + half * 8, ob);
+                }
+            // LDS -> global, chunk-major as above: consecutive lanes = (voxel, tap, half) of ONE 16-channel chunk = contiguous memory
+            const int a = (p.kz == 2) ? (ab >> 1) : 0, b = ab & 1;
+            const size_t oab = ((size_t)a * H2 + b) * W2;
+            u4 val[NST];
+#pragma unroll
+            for (int it = 0; it < NST; ++it) {
+                const int u = it * 64 + lane;
+                const int chunk = u >> 7, r = u & 127;
+                const int v = r >> 2, tap = (r >> 1) & 1, hf = r & 1;
+                const int piece = tap * (CD / 8) + chunk * 2 + hf;
+                ds_read16<0>(val[it], lds_addr(tile) + v * ROW + ((piece ^ (v & SWM)) * 16));
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+            for (int it = 0; it < NST; ++it) {
+                const int u = it * 64 + lane;
+                const int chunk = u >> 7, r = u & 127;
+                const int tap = (r >> 1) & 1, hf = r & 1;
+                tie(val[it]);
+                if (okv[it & 1]) {
+                    const size_t ov = ov0[it & 1] + oab + tap;
+                    *reinterpret_cast<u4*>(dst + (((size_t)(q * (CD / 16) + chunk) * p.Pd + ov) * SD_CHUNK + hf * 8) * sizeof(T)) = val[it];
+                }
+            }
+        }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the last two DMA steps land in this workgroup's LDS before it ends
+    sguard.flush(p.ovf);
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // element index -> coordinates with 32-bit arithmetic (the launchers reject tensors with >= 2^32 elements for these passes:
 // three 64-bit divisions per 16-byte access made the HBM-bound pooling / GroupNorm passes VALU-bound)
@@ -1175,6 +1380,40 @@ static int launch_upconv_rows_wl_g(const UpconvParams& p, hipStream_t s) {
     hipLaunchKernelGGL(kern, grid, block, lds, s, p);
     return SD_LAUNCH_CHECK();
 }
+// one-pass form (k_upconv_rows1): the input read once, the weights streamed through two LDS slots in steps of NT column tiles;
+// one workgroup of 8 waves per CU (2 * NT * NCH KiB of slots + 8 transpose tiles + the bias), one round of workgroups.
+// (16 waves per CU -- two workgroups with NT = 2 steps and no register set for a prefetch -- measured 17.7 against 17.6 us per
+// tile at 128 -> 64 channels and was not kept: tools/experiments/upconv_onepass_notes.md)
+template <typename T, int NCH, int NTAB, int NT>
+static int launch_upconv_rows1(const UpconvParams& p, hipStream_t s) {
+    { static const std::string name = "k_upconv_rows<NCH=" + std::to_string(NCH) + ",NTAB=" + std::to_string(NTAB) + ",one pass>"; SD_NOTE_KERNEL(name.c_str()); }
+    const long M = (long)p.D * p.H * p.W;
+    if (M >= (1l << 31) || M < 1 || p.gn || (p.kz != 1 && p.kz != 2)) return SD_ERR_INVALID;
+    const size_t lds = (size_t)8 * 32 * 64 * NT + (size_t)2 * NT * NCH * 1024 + (size_t)2 * p.kz * NTAB * 32 * sizeof(float);
+    if (lds > (size_t)SD_LDS_BYTES) return SD_ERR_INVALID;
+    auto kern = k_upconv_rows1<T, NCH, NTAB, NT>;
+    {
+        static std::mutex mu;
+        static LaunchCache cache[SD_MAX_DEVICES];
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= SD_MAX_DEVICES) return SD_ERR_HIP;
+        std::lock_guard<std::mutex> lock(mu);
+        LaunchCache& c = cache[dev];
+        if (lds > c.attr_set) {
+            if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
+                hipSuccess) return SD_ERR_HIP;
+            c.attr_set = lds;
+        }
+    }
+    const long groups = (M + 255) / 256;
+    long wgs = std::max(1L, (long)SD_NUM_CU / p.batch);
+    // SD_UPCONV_ONEPASS_WGS (read per launch): cap on the workgroups per tile, so that a small box runs several voxel groups per
+    // persistent workgroup (tests)
+    if (const char* const cap = getenv("SD_UPCONV_ONEPASS_WGS")) wgs = std::max(1L, std::min(wgs, atol(cap)));
+    dim3 grid((unsigned)std::min(groups, wgs), 1, p.batch), block(512);
+    hipLaunchKernelGGL(kern, grid, block, lds, s, p);
+    return SD_LAUNCH_CHECK();
+}
 template <typename T>
 static int launch_upconv_t(const UpconvParams& p, int NB, hipStream_t s) {
     SD_NOTE_KERNEL("k_upconv_mfma");      // (the row-kernel launchers below overwrite it)
@@ -1185,6 +1424,19 @@ static int launch_upconv_t(const UpconvParams& p, int NB, hipStream_t s) {
     if (p.nchunk == 4 && p.Cd == 32) return (no_wl || getenv("SD_UPCONV32_NO_WL")) ? launch_upconv_rows<T, 4, 2>(p, s) : launch_upconv_rows_wl<T, 4, 2>(p, s);
     if (p.nchunk == 3 && p.Cd == 32) return launch_upconv_rows<T, 3, 2>(p, s);
     if (p.nchunk == 2 && p.Cd == 16) return launch_upconv_rows<T, 2, 1>(p, s);
+    // One-pass forms (k_upconv_rows1) for the two shapes of the 32-filter nets whose LDS-weight forms read the input four times:
+    // 128 -> 64 (per pair) and 256 -> 128 (two pairs x two channel groups).  Selected from the launch-set size on at which they
+    // were measured against the forms below, 8 tiles of 128^3 (2^19 / 2^17 source voxels per launch); smaller launch sets keep
+    // the old forms.  SD_UPCONV_ONEPASS (read per launch): 0 = the old forms (A/B, identity tests), any other value = the one-pass
+    // form at every size.  The deferred-GroupNorm (p.gn) and split-fp16 launches and the 48-filter shapes (96 -> 48, 192 -> 96:
+    // not measured) stay on the old path.
+    if (!p.gn && !no_wl) {
+        const char* const op = getenv("SD_UPCONV_ONEPASS");
+        const bool off = op && op[0] == '0', force = op && !off;
+        const long mb = (long)p.D * p.H * p.W * p.batch;
+        if (!off && p.nchunk == 8 && p.Cd == 64 && (force || mb >= (1l << 19))) return launch_upconv_rows1<T, 8, 4, 4>(p, s);
+        if (!off && p.nchunk == 16 && p.Cd == 128 && (force || mb >= (1l << 17))) return launch_upconv_rows1<T, 16, 8, 2>(p, s);
+    }
     if (p.nchunk == 8 && p.Cd == 64 && !no_wl) return launch_upconv_rows_wl<T, 8, 4>(p, s);
     // (192 -> 96 channels: k_upconv_mfma 76 us, LDS-weight rows kernel 83 us per tile in the channel-blocked layout)
     if (p.nchunk == 6 && p.Cd == 48) return no_wl ? launch_upconv_rows<T, 6, 3>(p, s) : launch_upconv_rows_wl<T, 6, 3>(p, s);
