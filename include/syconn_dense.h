@@ -1000,6 +1000,55 @@ int sd_host_zero(uint8_t* dst, int64_t nbytes, int n_threads);
 int sd_plan_clip_window(const sd_op_desc* ops, int n_ops, int axis, int lo, int hi, int full, int multiple, int* start,
                         int* extent);
 
+/* ---- the multi-view network of the cell type step (csrc/sd_viewnet.hip; host-only plan: csrc/sd_viewnet.h) -----------------
+ * Replaces the network behind /root/reference/syconn/handler/prediction.py:985-1000 (get_celltype_model_e3 -> InferenceModel
+ * .predict_proba) for the architecture of /root/reference/syconn/cnn/cnn_celltype_cmn_j0251.py:22-60
+ * (StackedConv2ScalarWithLatentAdd): planar layers "valid k x k convolution, (1, p, p) floor max-pool, activation" and a chain
+ * of Linear layers over [flattened features, scalars].  elektronn3's Conv3DLayer is not part of the reference tree; DESIGN.md says
+ * what of it is pinned by the tree's text and what is a stated assumption.
+ *   sd_viewnet_create     layers[n_layers] = (cout, k, pool) with k in {1, 2, 4, 5}, pool in {1, 2}, cout <= 80; in_channels 1..4;
+ *                         fc[n_fc + 1] = (inputs of the first Linear = flattened features + n_scalar, outputs of every Linear),
+ *                         1 <= n_fc <= 4; act 0 = ReLU, 1 = LeakyReLU(0.01); weights = float32 in registration order: per layer
+ *                         w[cout][cin][k][k] then b[cout], per Linear w[out][in] then b[out]; act_dtype SD_F16 or SD_BF16 (storage of
+ *                         activations and convolution weights; accumulation, bias and the whole head are fp32).
+ *   sd_viewnet_forward    views_dev uint8[n_loc][in_channels][nb_views][H][W] as sd_views_render leaves them, n_planes_total =
+ *                         n_loc * nb_views; sample_table_dev int32[n_samples][D]: plane loc * nb_views + view of every slot of every
+ *                         sample (the input is never copied into sample order; the first layer computes conv(u / 255 - 0.5) from the
+ *                         integers u with the normalisation in its fp32 epilogue); scalars_dev float[n_samples][n_scalar] (may be
+ *                         null when n_scalar = 0); logits_dev float[n_samples][n_classes]; workspace of sd_viewnet_workspace_bytes;
+ *                         flags_dev int32[2], zeroed by the call: [0] != 0 an fp16 activation overflowed (results invalid),
+ *                         [1] != 0 a table entry outside [0, n_planes_total): that plane is not read and the results are invalid; its
+ *                         layer-1 output keeps what the workspace held, the later layers run over it, and flag 0 may then be set by
+ *                         those values too.  Both flags are plain stores of 1 by every thread that sees the condition.
+ *   sd_viewnet_forward_timed  sd_viewnet_forward with a HIP event behind every launch; waits for the stream; ms_out[n_layers + 1] =
+ *                         the time of every layer kernel and of the head kernel (tools/celltype_probe.py).
+ *   sd_viewnet_overflow   flags_out[2] = the two flags (waits for the stream).
+ *   sd_viewnet_read_buffer  after a forward, index i < n_layers: the stored output of layer i as float32
+ *                         [n_samples * D][Ho][Wo][cout]; n_layers <= i < sd_viewnet_num_ops: the output of Linear i - n_layers (behind
+ *                         its activation; the last one is the logits) as float32 [n_samples][out].  dims_out[4] = those extents
+ *                         (the head's as [n_samples][1][1][out]).  out_host may be null to query dims_out only.
+ *   sd_viewnet_num_ops    n_layers + n_fc.
+ * One grid stride of the layer kernel is SD_VIEWNET_GRID blocks (one block = 8 x 32 convolution outputs of one plane), of the head
+ * kernel SD_VIEWNET_HEAD_GRID blocks (one block = one sample); neither constant rests on a measurement. */
+#define SD_VIEWNET_GRID 2048
+#define SD_VIEWNET_HEAD_GRID 32
+typedef struct sd_viewnet_layer_desc { int32_t cout, k, pool; } sd_viewnet_layer_desc;
+typedef struct sd_viewnet sd_viewnet;
+int sd_viewnet_create(const sd_viewnet_layer_desc* layers, int n_layers, const int32_t* fc, int n_fc, int in_channels, int n_scalar, int act,
+                      const float* weights, size_t n_floats, int act_dtype, sd_viewnet** out);
+void sd_viewnet_destroy(sd_viewnet* m);
+size_t sd_viewnet_workspace_bytes(sd_viewnet* m, size_t n_samples, int D, int H, int W);
+int sd_viewnet_forward(sd_viewnet* m, const uint8_t* views_dev, size_t n_planes_total, int nb_views, int H, int W, const int32_t* sample_table_dev,
+                       size_t n_samples, int D, const float* scalars_dev, float* logits_dev, void* workspace_dev, size_t ws_bytes,
+                       int32_t* flags_dev, void* stream);
+int sd_viewnet_forward_timed(sd_viewnet* m, const uint8_t* views_dev, size_t n_planes_total, int nb_views, int H, int W,
+                             const int32_t* sample_table_dev, size_t n_samples, int D, const float* scalars_dev, float* logits_dev,
+                             void* workspace_dev, size_t ws_bytes, int32_t* flags_dev, void* stream, float* ms_out);
+int sd_viewnet_overflow(sd_viewnet* m, const int32_t* flags_dev, void* stream, int32_t* flags_out);
+int sd_viewnet_read_buffer(sd_viewnet* m, int index, const void* workspace_dev, const float* logits_dev, size_t n_samples, int D, int H, int W,
+                           float* out_host, int32_t* dims_out, void* stream);
+int sd_viewnet_num_ops(sd_viewnet* m);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,7 @@ SD_MESH_GRID = 256
 SD_GLIA_GRID = 1024
 SD_VIEWS_GRID, SD_VIEWS_RASTER_GRID, SD_VIEWS_MAX_VIEWS, SD_VIEWS_TILE_PX = 1024, 4096, 16, 32768
 SD_LOCATIONS_GRID, SD_LOCATIONS_WAVE_GRID, SD_LOCATIONS_MAX_CELLS = 1024, 4096, 1 << 21
+SD_VIEWNET_GRID, SD_VIEWNET_HEAD_GRID = 2048, 32
 
 LIB_NAME = 'libsyconn_dense_hip.so'
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), os.environ.get('SD_LIB_NAME', LIB_NAME))
@@ -51,7 +52,8 @@ EXPORTS = ['sd_init', 'sd_device_count', 'sd_model_create', 'sd_model_destroy', 
            'sd_views_rotations_temp_bytes', 'sd_views_rotations', 'sd_views_flag_empty', 'sd_views_index_bytes', 'sd_views_index_temp_bytes', 'sd_views_index',
            'sd_views_candidates_temp_bytes', 'sd_views_candidates', 'sd_views_render_temp_bytes', 'sd_views_render', 'sd_views_render_index',
            'sd_views_vote_temp_bytes', 'sd_views_vote', 'sd_locations_voxel_temp_bytes', 'sd_locations_voxel', 'sd_locations_surface_temp_bytes',
-           'sd_locations_surface']
+           'sd_locations_surface', 'sd_viewnet_create', 'sd_viewnet_destroy', 'sd_viewnet_workspace_bytes', 'sd_viewnet_forward', 'sd_viewnet_forward_timed',
+           'sd_viewnet_overflow', 'sd_viewnet_read_buffer', 'sd_viewnet_num_ops']
 
 
 class OpDesc(C.Structure):
@@ -62,6 +64,11 @@ class OpDesc(C.Structure):
                 ('relu', C.c_int32), ('norm', C.c_int32), ('groups', C.c_int32), ('eps', C.c_float),
                 ('w_off', C.c_int64), ('b_off', C.c_int64), ('gamma_off', C.c_int64), ('beta_off', C.c_int64),
                 ('mean_off', C.c_int64), ('var_off', C.c_int64)]
+
+
+class ViewNetLayerDesc(C.Structure):
+    """Mirror of ``sd_viewnet_layer_desc``."""
+    _fields_ = [('cout', C.c_int32), ('k', C.c_int32), ('pool', C.c_int32)]
 
 
 _lib = None
@@ -262,6 +269,16 @@ def load():
     lib.sd_locations_voxel.argtypes = [vp, i32, vp, sz, sz, f64, vp, vp, sz, vp, vp, sz, vp]; lib.sd_locations_voxel.restype = i32
     lib.sd_locations_surface_temp_bytes.argtypes = [sz, sz]; lib.sd_locations_surface_temp_bytes.restype = sz
     lib.sd_locations_surface.argtypes = [vp, vp, sz, sz, f32p, f64, vp, vp, sz, vp, vp, sz, vp]; lib.sd_locations_surface.restype = i32
+    # handler/prediction.py:985-1000 (get_celltype_model_e3 -> InferenceModel.predict_proba) for cnn/cnn_celltype_cmn_j0251.py:22-60
+    lib.sd_viewnet_create.argtypes = [C.POINTER(ViewNetLayerDesc), i32, i32p, i32, i32, i32, i32, f32p, sz, i32, C.POINTER(vp)]
+    lib.sd_viewnet_create.restype = i32
+    lib.sd_viewnet_destroy.argtypes = [vp]; lib.sd_viewnet_destroy.restype = None
+    lib.sd_viewnet_workspace_bytes.argtypes = [vp, sz, i32, i32, i32]; lib.sd_viewnet_workspace_bytes.restype = sz
+    lib.sd_viewnet_forward.argtypes = [vp, vp, sz, i32, i32, i32, vp, sz, i32, vp, vp, vp, sz, vp, vp]; lib.sd_viewnet_forward.restype = i32
+    lib.sd_viewnet_forward_timed.argtypes = lib.sd_viewnet_forward.argtypes + [f32p]; lib.sd_viewnet_forward_timed.restype = i32
+    lib.sd_viewnet_overflow.argtypes = [vp, vp, vp, i32p]; lib.sd_viewnet_overflow.restype = i32
+    lib.sd_viewnet_read_buffer.argtypes = [vp, i32, vp, vp, sz, i32, i32, i32, f32p, i32p, vp]; lib.sd_viewnet_read_buffer.restype = i32
+    lib.sd_viewnet_num_ops.argtypes = [vp]; lib.sd_viewnet_num_ops.restype = i32
     _lib = lib
     return lib
 

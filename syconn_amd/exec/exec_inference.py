@@ -70,3 +70,19 @@ def run_astrocyte_splitting(components, sv_props, mesh_bb=None, glia_probas=None
                                               sv_props.sizes, device)
     return AstrocyteSplitting(split, glia_splitting.collect_glia_sv(split, ids), glia_splitting.write_astrocyte_svgraph(split, scaling),
                               np.asarray(glia), proba)
+
+
+def run_celltype_prediction(cells, model=None, views=None, ids=None, nb_views_model=None, use_syntype=None, bs: int = 40, **vote_kw):
+    """exec/exec_inference.py:113-144 as a table form: the cell types of `cells` (objects with ``load_views()`` and ``syn_props``, or
+    `views` per cell) with one pass over the view network -> ``CellTypeTable``.  The reference spreads the cells over batch jobs that
+    each call ``predict_celltype_multiview``; the dataset and job layers are not built.  `model` defaults to
+    ``get_celltype_model_e3()``, `nb_views_model` to ``config['celltypes']['nb_views_model']``, `use_syntype` to
+    ``config.syntype_available`` (as ``predict_sso_celltype`` decides it)."""
+    from ..handler.prediction import get_celltype_model_e3
+    from ..reps.super_segmentation_helper import predict_celltypes_table
+    if global_params.config['use_point_models']:
+        raise NotImplementedError('run_celltype_prediction: the point models are not built')
+    model = get_celltype_model_e3() if model is None else model
+    nb = global_params.config['celltypes']['nb_views_model'] if nb_views_model is None else nb_views_model
+    syn = bool(global_params.config.syntype_available) if use_syntype is None else use_syntype
+    return predict_celltypes_table(cells, model, views=views, nb_views_model=nb, use_syntype=syn, bs=bs, ids=ids, **vote_kw)

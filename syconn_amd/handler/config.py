@@ -113,6 +113,8 @@ DEFAULTS = {
         'subcell_objects': ['mi', 'vc', 'sj'],
         'view_properties': {'comp_window': 8000, 'ws': [256, 128], 'nb_views': 2},
     },
+    # cell types from multi-views (config.yml:297-299): the views per sample of the view network
+    'celltypes': {'nb_views_model': 20},
 }
 
 
@@ -221,6 +223,11 @@ class DynConfig:
     @property
     def mpath_mivcsj(self) -> str:
         return self.model_dir + '/mivcsj/model.pt'
+
+    @property
+    def mpath_celltype_e3(self) -> str:
+        """config.py:565-570: the view network of the cell type step."""
+        return self.model_dir + '/celltype_e3/model.pts'
 
     @property
     def syntype_available(self) -> bool:

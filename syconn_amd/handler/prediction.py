@@ -730,3 +730,182 @@ def predict_dense_to_kd(kd_path: str, target_path: str, model_path: str, n_chann
 def get_myelin_cnn():
     """prediction.py:1047-1063: ``Predictor(torch.jit.load(mpath_myelin))`` with the default tiling of that loader."""
     return Predictor(global_params.config.mpath_myelin, strict_shapes=False, apply_softmax=True)
+
+
+# -- multi-view networks (cell types) ---------------------------------------------------------------------------------------------
+def naive_view_normalization_new(d):
+    """prediction.py:1096-1097."""
+    return d.astype(np.float32) / 255. - 0.5
+
+
+def certainty_estimate(inp: np.ndarray, is_logit: bool = False) -> float:
+    """prediction.py:1197-1227: one minus the entropy of the mean (pseudo-)probabilities over its maximum ln(C).  ``scipy.special
+    .softmax`` (exp(x - max) / sum) and ``scipy.stats.entropy`` (normalise, then -sum p ln p with 0 ln 0 = 0) are restated in numpy, in
+    the dtype of the input as there: scipy is no runtime dependency."""
+    if not inp.ndim == 2:
+        raise ValueError('Input is not two dimensional.')
+    if is_logit:
+        mx = np.max(inp, axis=1, keepdims=True)
+        e = np.exp(inp - np.where(np.isfinite(mx), mx, 0))
+        proba = e / np.sum(e, axis=1, keepdims=True)
+    else:
+        proba = inp
+    proba = np.mean(proba, axis=0)
+    entr_max = np.log(len(proba))
+    pk = 1.0 * proba / np.sum(proba, axis=0, keepdims=True)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        terms = np.where(pk > 0, -pk * np.log(pk), np.where(pk == 0, 0, -np.inf)).astype(pk.dtype)
+    entr_norm = np.sum(terms, axis=0) / entr_max
+    return 1 - entr_norm
+
+
+def views_to_uint8(x: np.ndarray) -> np.ndarray:
+    """Views that were normalised with ``naive_view_normalization_new`` back to the uint8 renderings they came from.  Only exact:
+    ``u = rint((x + 0.5) 255)`` must reproduce every element of `x` bit for bit (views are always uint8 renderings; the device
+    multiplies the integers and normalises in its epilogue), NotImplementedError otherwise."""
+    x = np.asarray(x)
+    if x.dtype != np.float32:
+        raise NotImplementedError(f'views must be uint8 or float32 normalised uint8, got {x.dtype}')
+    with np.errstate(invalid='ignore'):
+        u = np.rint((x.astype(np.float64) + 0.5) * 255.)
+    ok = np.isfinite(u).all() and u.min(initial=0) >= 0 and u.max(initial=0) <= 255
+    if ok:
+        u8 = u.astype(np.uint8)
+        ok = np.array_equal(naive_view_normalization_new(u8), x)
+    if not ok:
+        raise NotImplementedError('float32 views that are not naive_view_normalization_new(uint8 views): the view network reads the '
+                                  'uint8 renderings; pass those')
+    return u8
+
+
+class ViewSamples:
+    """The internal input form of ``ViewModel.predict_proba``: the renderer's tensor ``views`` uint8 (n_loc, C, nb_views, H, W) (device or
+    host) and ``table`` int32 (n_samples, D), the plane ``loc * nb_views + view`` of every slot of every sample."""
+
+    def __init__(self, views, table):
+        self.views, self.table = views, table
+
+
+class ViewModel:
+    """``InferenceModel`` of elektronn3 (prediction.py:999) for a view network given as a spec: ``predict_proba(inp, bs=None)`` with
+    ``inp = views`` or ``(views, scalars)`` returns the float32 logits (n_samples, n_classes) -- the cell type path passes no normalising
+    function, so "proba" are logits there too.  `weights`: a state dict, a module, or the path of a ``torch.jit`` file.  The views are
+    uint8 (n_samples, C, D, H, W), a ``ViewSamples``, or float32 that ``views_to_uint8`` takes.  Deviations: DESIGN.md."""
+
+    def __init__(self, spec, weights, act_dtype: str = 'f16', bs: int = 40, device=None):
+        from .. import _dev as dv
+        if act_dtype not in ('f16', 'bf16'):
+            raise ValueError("act_dtype must be 'f16' or 'bf16'")
+        if isinstance(weights, (str, os.PathLike)):
+            weights = torch.jit.load(os.fspath(weights), map_location='cpu')
+        if hasattr(weights, 'state_dict'):
+            weights = weights.state_dict()
+        arrs = spec.weights_from_state_dict(weights)
+        self.spec, self.act_dtype, self.bs = spec, act_dtype, int(bs)
+        if self.bs < 1:
+            raise ValueError('bs must be positive')
+        self.dev = dv.device(device)
+        import ctypes as C
+        lib = L.load()
+        blob = np.concatenate([a.ravel() for a in arrs]).astype(np.float32)
+        descs = (L.ViewNetLayerDesc * len(spec.layers))(*[L.ViewNetLayerDesc(*l) for l in spec.layers])
+        sizes = spec.linear_sizes
+        fc = (C.c_int32 * len(sizes))(*sizes)
+        h = C.c_void_p()
+        with torch.cuda.device(self.dev):
+            L.check(lib.sd_viewnet_create(descs, len(spec.layers), fc, len(sizes) - 1, spec.in_channels, spec.n_scalar,
+                                          0 if spec.act == 'relu' else 1, blob.ctypes.data_as(C.POINTER(C.c_float)), blob.size,
+                                          L.SD_F16 if act_dtype == 'f16' else L.SD_BF16, C.byref(h)), 'sd_viewnet_create')
+        self._h = h
+        self._last = None
+
+    def __del__(self):
+        h, self._h = getattr(self, '_h', None), None
+        if h:
+            L.load().sd_viewnet_destroy(h)
+
+    @property
+    def num_ops(self) -> int:
+        return L.load().sd_viewnet_num_ops(self._h)
+
+    def _samples(self, views) -> 'ViewSamples':
+        if isinstance(views, ViewSamples):
+            v, t = views.views, views.table
+        else:
+            if isinstance(views, np.ndarray) and views.dtype == np.float32:
+                views = views_to_uint8(views)
+            v = views
+            if getattr(v, 'ndim', 0) != 5:
+                raise ValueError('views must be (n_samples, C, D, H, W)')
+            t = np.arange(v.shape[0] * v.shape[2], dtype=np.int32).reshape(v.shape[0], v.shape[2])
+        v = torch.from_numpy(np.ascontiguousarray(v)) if isinstance(v, np.ndarray) else v
+        t = torch.from_numpy(np.ascontiguousarray(t)) if isinstance(t, np.ndarray) else t
+        if not isinstance(v, torch.Tensor) or v.dtype != torch.uint8 or v.dim() != 5:
+            raise ValueError('views must be a uint8 array / tensor (n_loc, C, nb_views, H, W)')
+        if v.shape[1] != self.spec.in_channels:
+            raise ValueError(f'views have {v.shape[1]} channels, the model takes {self.spec.in_channels}')
+        if v.numel() == 0:
+            raise ValueError('views are empty')
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+            raise ValueError('the sample table must be int32 (n_samples, D) with at least one sample')
+        return ViewSamples(v.to(self.dev).contiguous(), t.to(self.dev).contiguous())
+
+    def predict_proba(self, inp, bs: Optional[int] = None) -> np.ndarray:
+        from .. import _dev as dv
+        views, scal = inp if isinstance(inp, (tuple, list)) else (inp, None)
+        spec = self.spec
+        bs = self.bs if bs is None else int(bs)
+        if bs < 1:
+            raise ValueError('bs must be positive')
+        sm = self._samples(views)
+        n, D = int(sm.table.shape[0]), int(sm.table.shape[1])
+        n_loc, _, nb_views, H, W = (int(x) for x in sm.views.shape)
+        spec.check_geometry(D, H, W)
+        if spec.n_scalar:
+            if scal is None:
+                raise ValueError(f'the model takes {spec.n_scalar} scalars per sample')
+            scal = torch.as_tensor(np.asarray(scal, dtype=np.float32) if not isinstance(scal, torch.Tensor) else scal)
+            if tuple(scal.shape) != (n, spec.n_scalar):
+                raise ValueError(f'scalars must be ({n}, {spec.n_scalar}), got {tuple(scal.shape)}')
+            scal = scal.to(device=self.dev, dtype=torch.float32).contiguous()
+        elif scal is not None and np.asarray(scal.cpu() if isinstance(scal, torch.Tensor) else scal).size:
+            raise ValueError('the model takes no scalars')
+        nb = min(bs, n)
+        with torch.cuda.device(self.dev):
+            ws = dv.scratch('sd_viewnet_workspace_bytes', self.dev, self._h, nb, D, H, W)
+            logits = torch.empty((n, spec.n_classes), dtype=torch.float32, device=self.dev)
+            flags = torch.zeros((-(-n // nb), 2), dtype=torch.int32, device=self.dev)
+            for i, b in enumerate(range(0, n, nb)):
+                e = min(b + nb, n)
+                dv.call('sd_viewnet_forward', self.dev, self._h, sm.views, n_loc * nb_views, nb_views, H, W, sm.table[b:e], e - b, D,
+                        scal[b:e] if spec.n_scalar else None, logits[b:e], ws, ws.numel(), flags[i])
+            fl = flags.cpu().numpy()
+        self._last = (ws, logits[b:e], e - b, D, H, W)
+        if fl[:, 1].any():
+            raise IndexError(f'sample table: an entry is outside [0, {n_loc * nb_views}) (n_loc * nb_views planes)')
+        if fl[:, 0].any():
+            raise L.ActivationOverflowError("fp16 activation storage overflowed in the view network: its logits are invalid; use "
+                                            "act_dtype='bf16'")
+        return logits.cpu().numpy()
+
+    def read_buffer(self, index: int) -> np.ndarray:
+        """Debug: after ``predict_proba``, the stored output of layer `index` of the LAST launch set as float32 (planes, Ho, Wo, cout), or
+        for ``index >= len(spec.layers)`` the output of Linear ``index - len(spec.layers)`` as (n_samples, out)."""
+        from .. import _dev as dv
+        import ctypes as C
+        if self._last is None:
+            raise RuntimeError('read_buffer: no forward yet')
+        ws, logits, n, D, H, W = self._last
+        lib = L.load()
+        dims = (C.c_int32 * 4)()
+        args = (self._h, int(index), ws.data_ptr(), logits.data_ptr(), n, D, H, W)
+        L.check(lib.sd_viewnet_read_buffer(*args, None, dims, dv.stream(self.dev)), 'sd_viewnet_read_buffer')
+        out = np.empty(tuple(dims), dtype=np.float32)
+        L.check(lib.sd_viewnet_read_buffer(*args, out.ctypes.data_as(C.POINTER(C.c_float)), dims, dv.stream(self.dev)), 'sd_viewnet_read_buffer')
+        return out if index < len(self.spec.layers) else out.reshape(dims[0], dims[3])
+
+
+def get_celltype_model_e3(act_dtype: str = 'f16', n_classes: int = 7, n_scalar: int = 2):
+    """prediction.py:985-1000: ``torch.jit.load(mpath_celltype_e3)`` -> state dict -> the view network (bs=40 as there)."""
+    from ..cnn.viewnet_spec import CELLTYPE_CMN
+    return ViewModel(CELLTYPE_CMN(n_classes, n_scalar), global_params.config.mpath_celltype_e3, act_dtype=act_dtype, bs=40)

@@ -255,10 +255,12 @@ def _subcell_objects(add_cellobjects):
 
 def render_sso_coords(sso, coords: np.ndarray, add_cellobjects: Optional[Iterable[str]] = None, verbose: bool = False, clahe: bool = False,
                       ws=None, cellobjects_only: bool = False, wire_frame: bool = False, nb_views: Optional[int] = None,
-                      comp_window: Optional[float] = None, rot_mat: Optional[np.ndarray] = None, return_rot_mat: bool = False, device=None):
+                      comp_window: Optional[float] = None, rot_mat: Optional[np.ndarray] = None, return_rot_mat: bool = False, device=None,
+                      return_device: bool = False):
     """Views of a cell at `coords`: uint8 (N, channels, nb_views, ws[1], ws[0]), the cell's mesh first (left out with
     `cellobjects_only`), then one channel per entry of `add_cellobjects`; a missing or empty mesh gives 255.  `sso` is anything with
-    ``.mesh`` and ``.load_mesh(name)`` (``[indices, vertices, ...]``).  proc/rendering.py:204-297."""
+    ``.mesh`` and ``.load_mesh(name)`` (``[indices, vertices, ...]``).  proc/rendering.py:204-297.  With `return_device` the views (and
+    matrices) stay on the device as tensors (the view network reads them there)."""
     _not_built(clahe=clahe, wire_frame=wire_frame)
     add_cellobjects = _subcell_objects(add_cellobjects)
     names = list(add_cellobjects) if add_cellobjects is not False else []
@@ -278,7 +280,7 @@ def render_sso_coords(sso, coords: np.ndarray, add_cellobjects: Optional[Iterabl
     elif rot_mat is None:
         rot_mat = np.zeros((N, 16))
     meshes = ([] if cellobjects_only else [cell_vm]) + [pair(sso.load_mesh(name)) for name in names]
-    views, rot = render_views_table(meshes, coords_d, rot_mat, ws, nb_views, comp_window, device=dev)
+    views, rot = render_views_table(meshes, coords_d, rot_mat, ws, nb_views, comp_window, device=dev, return_device=return_device)
     return (views, rot) if return_rot_mat else views
 
 

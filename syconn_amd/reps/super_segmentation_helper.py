@@ -393,3 +393,190 @@ def sample_locations_sso(sso, ds_factor=None, device=None):
                                    scaling=np.array([np.asarray(sv.scaling).reshape(3) for sv in svs]), device=device)
     lb = table.loc_begin.astype(np.int64)
     return [table.locations[lb[k]:lb[k + 1]] for k in range(len(svs))]
+
+
+# -- cell types from multi-views (reps/super_segmentation_helper.py:180-213, :1670-1755, :1981-2065) -------------------------------
+def view_sample_table(n_loc: int, views_per_loc: int, nb_views: int) -> np.ndarray:
+    """The draws of ``sso_views_to_modelinput`` (:199-212) as a table over the UNSHUFFLED views (n_loc, C, views_per_loc, H, W): int32
+    (n_samples, nb_views), entry = plane ``loc * views_per_loc + view`` of that slot.  numpy's global generator is seeded and used exactly
+    as the reference uses it: ``seed(0)``, ``shuffle`` along axis 0 (for an array: ``n_loc - 1`` bounded draws, whatever it holds),
+    ``choice`` for the padding when there are fewer than `nb_views` planes."""
+    if n_loc < 1 or views_per_loc < 1 or nb_views < 1:
+        raise ValueError('view_sample_table: no views')
+    np.random.seed(0)
+    perm = np.arange(n_loc).reshape(n_loc, 1)      # shuffled as the 5-D view array is: rows along axis 0
+    np.random.shuffle(perm)
+    planes = (perm.astype(np.int64) * views_per_loc + np.arange(views_per_loc)[None]).reshape(-1)
+    if len(planes) < nb_views:
+        rand_ixs = np.random.choice(len(planes), nb_views - len(planes))
+        planes = np.append(planes, planes[rand_ixs])
+    nb_samples = int(np.floor(len(planes) / nb_views))
+    return planes[:nb_samples * nb_views].reshape(nb_samples, nb_views).astype(np.int32)
+
+
+def sso_views_to_modelinput(sso, nb_views: int, view_key=None, return_table: bool = False):
+    """:180-213: random subsets of `nb_views` views, (n_samples, C, nb_views, H, W).  `sso`: the view array (n_loc, C, views_per_loc, H,
+    W) itself -- numpy, or a device tensor --, or anything with ``load_views(view_key=...)``.  With `return_table` the views are not
+    moved: -> ``ViewSamples(views, table)`` (``handler.prediction``), the form the view network reads in place."""
+    views = sso if isinstance(sso, (np.ndarray, torch.Tensor)) else sso.load_views(view_key=view_key)
+    if views.ndim != 5 or views.shape[0] < 1 or views.shape[2] < 1:
+        raise ValueError('sso_views_to_modelinput: views must be (n_loc > 0, C, views_per_loc > 0, H, W)')
+    table = view_sample_table(int(views.shape[0]), int(views.shape[2]), int(nb_views))
+    if return_table:
+        from ..handler.prediction import ViewSamples
+        return ViewSamples(views, table)
+    v = views.cpu().numpy() if isinstance(views, torch.Tensor) else np.asarray(views)
+    n_loc, C, vpl, H, W = v.shape
+    planes = v.swapaxes(1, 0).reshape(C, n_loc * vpl, H, W)
+    return planes[:, table.reshape(-1)].reshape(C, table.shape[0], nb_views, H, W).swapaxes(1, 0)
+
+
+def syn_sign_ratio_celltype(syn_sign, mesh_area, syn_axs, weighted: bool = True, comp_types=None) -> float:
+    """:1981-2065 over arrays: `syn_sign` (+1 / -1), `mesh_area` and the compartment label at the synapse (``attr_for_coords`` of the
+    axoness key) of every ``syn_ssv`` object of the cell.  Boutons count as axon (3, 4 -> 1), the size is ``mesh_area / 2``; -> the
+    (area-weighted) share of symmetric synapses among those on `comp_types` (default [1]), -1 for no synapse or zero area."""
+    comp_types = [1] if comp_types is None else list(comp_types)
+    syn_sign, mesh_area, syn_axs = np.asarray(syn_sign), np.asarray(mesh_area, dtype=np.float64), np.array(syn_axs, copy=True)
+    if not (len(syn_sign) == len(mesh_area) == len(syn_axs)):
+        raise ValueError('syn_sign_ratio_celltype: arrays of different lengths')
+    if len(syn_sign) == 0:
+        return -1
+    syn_axs[syn_axs == 3] = 1
+    syn_axs[syn_axs == 4] = 1
+    keep = np.isin(syn_axs, comp_types)
+    syn_signs, syn_sizes = syn_sign[keep], mesh_area[keep] / 2
+    if len(syn_signs) == 0 or np.sum(syn_sizes) == 0:
+        return -1
+    if weighted:
+        return np.sum(syn_sizes[syn_signs == -1]) / float(np.sum(syn_sizes))
+    return np.sum(syn_signs == -1) / float(len(syn_signs))
+
+
+def celltype_vote(res: np.ndarray, da_equals_tan: bool = True, n_classes: int = 7):
+    """The vote block of ``celltype_of_sso_nocache`` (:1733-1753) on the logits of all samples of a cell: -> ``(pred, res, certainty)``
+    with `res` the (merged) float32 array the reference stores as ``_probas`` and the certainty of ``certainty_celltype`` (the entropy
+    certainty of the softmax of `res`)."""
+    from ..handler.prediction import certainty_estimate
+    res = np.array(res, copy=True)
+    if da_equals_tan:
+        assert n_classes == 7
+        res[:, 1] += res[:, 6]
+        res = np.delete(res, [6], axis=1)
+    clf = np.argmax(res, axis=1)
+    if np.max(clf) >= n_classes:
+        raise ValueError('Unknown cell type predicted.')
+    major_dec = np.zeros(n_classes)
+    for ii in range(len(major_dec)):
+        major_dec[ii] = np.sum(clf == ii)
+    major_dec /= np.sum(major_dec)
+    pred = np.argmax(major_dec)
+    return pred, res, certainty_estimate(res, is_logit=True)
+
+
+def _celltype_store(sso, pred_key, pred, res, cert, save_to_attr_dict):
+    sso.attr_dict[pred_key] = pred
+    sso.attr_dict[f'{pred_key}_probas'] = res
+    sso.attr_dict[f'{pred_key}_certainty'] = cert
+    if save_to_attr_dict and hasattr(sso, 'save_attributes'):
+        sso.save_attributes([pred_key, f'{pred_key}_probas', f'{pred_key}_certainty'], [pred, res, cert])
+
+
+def _celltype_scalars(sso, n_samples, syn_props):
+    """[[ratio on axon, ratio on dendrite]] * n_samples (:1726-1727); `syn_props` = (syn_sign, mesh_area, syn_axs), default
+    ``sso.syn_props``."""
+    props = sso.syn_props if syn_props is None else syn_props
+    return np.array([[syn_sign_ratio_celltype(*props, comp_types=[1, ]), syn_sign_ratio_celltype(*props, comp_types=[0, ])]] * n_samples)
+
+
+def _celltype_predict(sso, model, views, nb_views_model, use_syntype, pred_key, da_equals_tan, n_classes, save_to_attr_dict, syn_props):
+    inp = sso_views_to_modelinput(sso if views is None else views, nb_views_model, return_table=True)
+    n = len(inp.table)
+    res = model.predict_proba((inp, _celltype_scalars(sso, n, syn_props)) if use_syntype else inp, bs=40)
+    pred, res, cert = celltype_vote(res, da_equals_tan, n_classes)
+    _celltype_store(sso, pred_key, pred, res, cert, save_to_attr_dict)
+    return pred, res, cert
+
+
+def predict_sso_celltype(sso, model, nb_views_model: int = 20, use_syntype=True, overwrite: bool = False, pred_key_appendix='',
+                         da_equals_tan: bool = True, n_classes: int = 7, save_to_attr_dict: bool = True, views=None, syn_props=None):
+    """:114-177 with the views passed in (host array or device tensor, (n_loc, C, views_per_loc, H, W)) or from ``sso.load_views()``:
+    the samples are read in place through the sample table, the vote runs in numpy on the logits.  The ratios are used when
+    ``config.syntype_available and use_syntype``, as there.  Also returns ``(pred, probas, certainty)``."""
+    pred_key = 'celltype_cnn_e3' + pred_key_appendix
+    if not overwrite and pred_key in sso.attr_dict:
+        return
+    return _celltype_predict(sso, model, views, nb_views_model, bool(global_params.config.syntype_available and use_syntype), pred_key,
+                             da_equals_tan, n_classes, save_to_attr_dict, syn_props)
+
+
+def celltype_of_sso_nocache(sso, model, ws, nb_views, comp_window, nb_views_model: int = 20, pred_key_appendix: str = '', verbose: bool = False,
+                            overwrite: bool = True, use_syntype: bool = True, da_equals_tan: bool = True, n_classes: int = 7,
+                            save_to_attr_dict: bool = True, syn_props=None, device=None):
+    """:1670-1755: render the 4-channel views at ``generate_rendering_locs(verts, comp_window / 3)`` -- they stay on the device --, cut
+    them into the reference's random subsets, run the view network with the two synapse-sign ratios, add logit 6 onto logit 1, vote.
+    `sso`: anything with ``.mesh``, ``.load_mesh(name)``, ``.attr_dict`` and ``.syn_props`` (or `syn_props`)."""
+    from ..handler.multiviews import generate_rendering_locs
+    from ..proc.rendering import render_sso_coords
+    pred_key = 'celltype_cnn_e3' + pred_key_appendix
+    if not overwrite and pred_key in sso.attr_dict:
+        return
+    verts = np.asarray(sso.mesh[1]).reshape(-1, 3)
+    rendering_locs = generate_rendering_locs(verts, comp_window / 3, device=device)
+    sso._sample_locations = rendering_locs
+    views = render_sso_coords(sso, rendering_locs, ws=ws, comp_window=comp_window, nb_views=nb_views, verbose=verbose, add_cellobjects=True,
+                              return_rot_mat=False, device=device, return_device=True)
+    return _celltype_predict(sso, model, views, nb_views_model, use_syntype, pred_key, da_equals_tan, n_classes, save_to_attr_dict, syn_props)
+
+
+class CellTypeTable:
+    """Cell types of many cells: ``ids``, ``pred`` int64 (n,), ``certainty`` float64 (n,), and the (merged) logits of all samples as one
+    ragged array: ``probas`` float32 (n_samples_total, C) with the samples of cell k at ``sample_begin[k]:sample_begin[k + 1]``."""
+
+    def __init__(self, ids, pred, certainty, probas, sample_begin):
+        self.ids, self.pred, self.certainty, self.probas, self.sample_begin = ids, pred, certainty, probas, sample_begin
+
+    def __len__(self):
+        return len(self.ids)
+
+    def probas_of(self, k: int) -> np.ndarray:
+        return self.probas[self.sample_begin[k]:self.sample_begin[k + 1]]
+
+    def as_dict(self, pred_key: str = 'celltype_cnn_e3') -> dict:
+        """id -> the three attributes the reference stores per cell."""
+        return {i: {pred_key: self.pred[k], f'{pred_key}_probas': self.probas_of(k), f'{pred_key}_certainty': self.certainty[k]}
+                for k, i in enumerate(self.ids)}
+
+
+def predict_celltypes_table(cells, model, views=None, nb_views_model: int = 20, use_syntype: bool = True, da_equals_tan: bool = True,
+                            n_classes: int = 7, bs: int = 40, ids=None) -> CellTypeTable:
+    """The cell type step for many cells with ONE pass over the view network: the samples of all cells go through ``predict_proba`` in
+    launch sets of `bs`, whatever cell they belong to, and the votes are taken per cell afterwards.  `views[k]` (default
+    ``cells[k].load_views()``): the view array of cell k, host or device, (n_loc_k, C, views_per_loc, H, W) with the same
+    ``views_per_loc``, H, W for all; they are joined along the location axis and read through one sample table.  Every cell's draws are
+    those of ``sso_views_to_modelinput`` on its own views, so the result equals one ``predict_sso_celltype`` per cell."""
+    from ..handler.prediction import ViewSamples
+    cells = list(cells)
+    if not cells:
+        raise ValueError('predict_celltypes_table: no cells')
+    views = [c.load_views() for c in cells] if views is None else list(views)
+    if len(views) != len(cells):
+        raise ValueError('predict_celltypes_table: one view array per cell')
+    if len({tuple(v.shape[1:]) for v in views}) != 1:
+        raise ValueError('predict_celltypes_table: the view arrays differ in channels, views per location or window')
+    dev = model.dev
+    tens = [v.to(dev) if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v)).to(dev) for v in views]
+    vpl = int(tens[0].shape[2])
+    tables, scal, begin, plane0 = [], [], [0], 0
+    for c, v in zip(cells, tens):
+        t = view_sample_table(int(v.shape[0]), vpl, int(nb_views_model)) + np.int32(plane0)
+        tables.append(t)
+        if use_syntype:
+            scal.append(_celltype_scalars(c, len(t), None))
+        begin.append(begin[-1] + len(t))
+        plane0 += int(v.shape[0]) * vpl
+    inp = ViewSamples(tens[0] if len(tens) == 1 else torch.cat(tens, 0), np.concatenate(tables))
+    res = model.predict_proba((inp, np.concatenate(scal)) if use_syntype else inp, bs=bs)
+    votes = [celltype_vote(res[begin[k]:begin[k + 1]], da_equals_tan, n_classes) for k in range(len(cells))]
+    ids = np.arange(len(cells)) if ids is None else np.asarray(ids)
+    return CellTypeTable(ids, np.array([v[0] for v in votes], np.int64), np.array([v[2] for v in votes], np.float64),
+                         np.concatenate([v[1] for v in votes]), np.array(begin, np.int64))

@@ -86,3 +86,34 @@ def semsegaxoness2skel(sso, map_properties: dict, pred_key: str, max_dist: int):
     for key, val in res.items():
         sso.skeleton[key] = val
     sso.save_skeleton()
+
+
+# -- cell types (the methods of the reference's SuperSegmentationObject, as functions of the cell object) ------------------------------
+def predict_celltype_multiview(sso, model, pred_key_appendix: str = '', model_tnet=None, view_props=None, onthefly_views: bool = False,
+                               overwrite: bool = True, model_props=None, verbose: bool = False, save_to_attr_dict: bool = True, **kw):
+    """reps/super_segmentation_object.py:3125-3165: ``celltype_cnn_e3``, ``_probas`` and ``_certainty`` of `sso` from `model` (a
+    ``handler.prediction.ViewModel``), from the stored views (``sso.load_views()``, or ``views=`` in `kw`) or, with `onthefly_views`,
+    from views rendered with the view properties of the config (updated by `view_props`).  The morphology embedding (`model_tnet`, the
+    triplet net) is not built."""
+    from .. import global_params
+    from . import super_segmentation_helper as ssh
+    if model_tnet is not None:
+        raise NotImplementedError('predict_celltype_multiview: the morphology embedding (view_embedding_of_sso_nocache) is not built')
+    model_props = dict(model_props or {})
+    props = dict(global_params.config['views']['view_properties'])
+    props.update(view_props or {})
+    if not onthefly_views:
+        return ssh.predict_sso_celltype(sso, model, pred_key_appendix=pred_key_appendix, save_to_attr_dict=save_to_attr_dict,
+                                        overwrite=overwrite, **model_props, **kw)
+    return ssh.celltype_of_sso_nocache(sso, model, pred_key_appendix=pred_key_appendix, save_to_attr_dict=save_to_attr_dict,
+                                       overwrite=overwrite, verbose=verbose, **props, **model_props, **kw)
+
+
+def certainty_celltype(sso, pred_key=None) -> float:
+    """reps/super_segmentation_object.py:3193-3220: the stored certainty, else the entropy certainty of the stored logits."""
+    from ..handler.prediction import certainty_estimate
+    pred_key = 'celltype_cnn_e3' if pred_key is None else pred_key
+    cert = sso.attr_dict.get(pred_key + '_certainty')
+    if cert is not None:
+        return cert
+    return certainty_estimate(sso.attr_dict[pred_key + '_probas'], is_logit=True)
