@@ -1,14 +1,19 @@
 """GPU: csrc/sd_views.hip past one grid stride of its kernels -- more (location, view) items than SD_VIEWS_RASTER_GRID workgroups and
 more locations than the waves of one stride of the candidate kernels, more triangles than one stride of the index kernels, more pixels
-than one stride of the vote."""
+than one stride of the vote, more locations than the waves of one stride of the rotation solver and more vertices than one stride of
+the rotation's key and place kernels."""
+import os
+
 import numpy as np
 import pytest
 
 import _views_gpu as G
 import _views_ref as R
 from syconn_amd import _lib as L
+from test_gpu_views import ROT_BOUND
 
 pytestmark = pytest.mark.gpu
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'g27_views.npz')
 
 
 def test_locations_past_the_raster_stride(gpu):
@@ -56,6 +61,66 @@ def test_triangles_past_the_index_stride(gpu):
     corner = (cell_x[None, :] * (k + 1) + cell_y[:, None])
     last = ix[0, 0].astype(np.int64) - corner                                      # the last vertex of either triangle of that cell
     assert np.isin(last, (k + 2, 1)).all()
+
+
+@pytest.fixture(scope='module')
+def gold():
+    return dict(np.load(GOLD))
+
+
+@pytest.fixture(scope='module')
+def rot_small(gpu, gold):
+    """The 52 clouds of the golden, which test_rotations_against_golden compares with the reference."""
+    g = gold
+    rc, c, rot, empty = G.rotations(gpu, g['r_verts'], g['r_coords'], g['r_edge'])
+    assert rc == 0 and not c.any()
+    rot.setflags(write=False)
+    return rot, empty
+
+
+def test_rotation_locations_past_one_stride(gpu, gold, rot_small):
+    """4201 locations > the 4096 waves of one stride of k_vw_rot_solve: a location's result does not depend on the others (its sums go
+    through one fixed butterfly), so every repeat equals the 52-location call bit for bit."""
+    g = gold
+    n = L.SD_VIEWS_GRID * 4 + 105
+    rep = np.arange(n) % 52
+    rot, empty = rot_small
+    rc, c, big, empty_big = G.rotations(gpu, g['r_verts'], g['r_coords'][rep], g['r_edge'])
+    assert rc == 0 and not c.any()
+    assert np.array_equal(big, rot[rep]) and np.array_equal(empty_big, empty[rep])
+    assert big[-1].any() and big[L.SD_VIEWS_GRID * 4].any()                         # the second trip wrote matrices
+    rc, c, none, empty_flag = G.rotations(gpu, g['r_verts'], g['r_coords'][rep], g['r_edge'], flag_only=True)
+    assert rc == 0 and none is None and np.array_equal(empty_flag, empty[rep]) and empty[48] and not empty[49]
+
+
+@pytest.mark.parametrize('fill', [50.0, -50.0])
+def test_rotation_vertices_past_one_stride(gpu, gold, rot_small, fill):
+    """266,006 vertices > 262,144 = one stride of k_vw_rot_keys / k_vw_rot_place, the cloud across the stride's end behind a filler
+    that is no inlier anywhere: the inliers are the same, their order in the sums need not be.  The filler at 50 has the largest
+    Morton code and is sorted behind the cloud; the one at -50 has code 0 and is sorted in front of it, so the cloud lies across the
+    stride's end in the sorted order that k_vw_rot_place writes as well."""
+    g = gold
+    verts = np.concatenate([np.full((255000, 3), fill, np.float32), g['r_verts']])
+    assert len(verts) > L.SD_VIEWS_GRID * 256 > 255000
+    rot, empty = rot_small
+    rc, c, big, empty_big = G.rotations(gpu, verts, g['r_coords'], g['r_edge'])
+    assert rc == 0 and not c.any()
+    assert np.array_equal(empty_big, empty) and np.array_equal(big.any(1), rot.any(1))           # <= 2 inliers: 16 zeros
+    fixed = [3, 7, 11, 12, 13, 14, 15]                                              # the last row and column of every matrix
+    assert np.array_equal(big[:, fixed], rot[:, fixed])
+    ok = g['r_gap_ok']
+    worst = np.abs(big - rot)[ok].max()
+    print(f'rotations with 255,000 filler vertices at {fill}: largest |difference| of an entry = {worst:.3e} over {int(ok.sum())} clouds')
+    assert worst <= ROT_BOUND                                                       # sign included
+
+
+def test_rotation_stride_with_a_remainder(gpu, gold):
+    g = gold
+    v = g['m_vn'][:1021]
+    assert len(v) % 8 == 5
+    rc, c, rot8, empty8 = G.rotations(gpu, v, g['m_cn'], g['m_edge'], stride=8)
+    rc2, c2, sub, empty_sub = G.rotations(gpu, v[::8], g['m_cn'], g['m_edge'])
+    assert rc == rc2 == 0 and not c.any() and np.array_equal(rot8, sub) and np.array_equal(empty8, empty_sub) and rot8.any()
 
 
 def test_vote_past_one_stride(gpu):
