@@ -1049,6 +1049,50 @@ int sd_viewnet_read_buffer(sd_viewnet* m, int index, const void* workspace_dev, 
                            float* out_host, int32_t* dims_out, void* stream);
 int sd_viewnet_num_ops(sd_viewnet* m);
 
+/* ---- the FCN semantic-segmentation network of the compartment step (csrc/sd_fcn.hip; host-only plan: csrc/sd_fcn.h) ---------------
+ * Replaces the networks behind /root/reference/syconn/handler/prediction.py:1003-1030 (get_semseg_spiness_model,
+ * get_semseg_axon_model -> InferenceModel) as /root/reference/syconn/reps/super_segmentation_helper.py:1353-1392
+ * (predict_views_semseg) calls them: views / 255 -> FCNs(VGGNet) -> argmax over the classes.  elektronn3's fcn_2d is not part of the
+ * reference tree; the architecture is stated, not pinned (syconn_amd/cnn/fcn_spec.py): five encoder blocks of 1 to 3
+ * "3 x 3 convolution (padding 1) + ReLU" and a 2 x 2 max-pool each, five decoder steps "ConvTranspose2d(3, stride 2, padding 1,
+ * output_padding 1) -> ReLU -> eval BatchNorm (eps 1e-5) -> + skip" (no skip behind the fifth), a 1 x 1 classifier.
+ *   sd_fcn_create         blocks = output channels (1..512) of all encoder convolutions, block after block, block_len[5] = convolutions
+ *                         per block (1..3); dec_last 1..512; n_class 1..16; in_channels 1..4; weights = float32 in registration order:
+ *                         encoder w[cout][cin][3][3], b[cout]; per decoder step w[cin][cout][3][3], b, gamma, beta, running_mean,
+ *                         running_var [cout]; classifier w[n_class][dec_last], b; act_dtype SD_F16 or SD_BF16 (storage of activations
+ *                         and of the 3 x 3 weights; accumulation, bias, BatchNorm constants and the classifier are fp32).  A weight
+ *                         that rounds to infinity in the storage type is refused.
+ *   sd_fcn_forward        views_dev uint8[n_loc][in_channels][nb_views][H][W] as sd_views_render leaves them, n_planes_total =
+ *                         n_loc * nb_views, H and W multiples of 32; the planes [plane0, plane0 + n_planes) are computed (plane =
+ *                         loc * nb_views + view; the input is never copied into plane order; the first layer multiplies the integers u
+ *                         and applies 1 / 255 in its fp32 epilogue).  labels_dev uint8[n_planes][H][W]: the argmax, the lowest index
+ *                         wins exact ties -- for plane0 = 0 and all planes this is [n_loc][1][nb_views][H][W]; logits_dev
+ *                         float[n_planes][n_class][H][W] or null; workspace of sd_fcn_workspace_bytes(m, n_planes, H, W), 16-byte
+ *                         aligned; flags_dev int32[1], zeroed by the call: != 0 an fp16 activation reached 65520 before rounding
+ *                         (results invalid; a plain store of 1 by every thread that sees it).
+ *   sd_fcn_forward_timed  sd_fcn_forward with a HIP event behind the launches of every op; waits for the stream; ms_out[n_ops]
+ *                         (tools/semseg_probe.py).
+ *   sd_fcn_overflow       flags_out[1] = the flag (waits for the stream).
+ *   sd_fcn_read_buffer    after a forward, index i < n_ops - 1: the stored output of op i as float32 [n_planes][h][w][c]; i = n_ops - 1:
+ *                         the logits [n_planes][n_class][H][W] (needs logits_dev).  dims_out[4] = those extents; out_host may be null.
+ *   sd_fcn_num_ops        encoder convolutions (the pool is part of a block's last one) + 5 decoder steps + the classifier.
+ * A workgroup of the MFMA kernels computes 8 x 32 positions for at most 64 output channels; no grid is capped, a call whose launches
+ * would pass 2^31 - 1 blocks is refused. */
+typedef struct sd_fcn sd_fcn;
+int sd_fcn_create(int in_channels, const int32_t* blocks, const int32_t* block_len, int dec_last, int n_class, const float* weights, size_t n_floats,
+                  int act_dtype, sd_fcn** out);
+void sd_fcn_destroy(sd_fcn* m);
+size_t sd_fcn_workspace_bytes(sd_fcn* m, size_t n_planes, int H, int W);
+int sd_fcn_forward(sd_fcn* m, const uint8_t* views_dev, size_t n_planes_total, int nb_views, int H, int W, size_t plane0, size_t n_planes,
+                   uint8_t* labels_dev, float* logits_dev, void* workspace_dev, size_t ws_bytes, int32_t* flags_dev, void* stream);
+int sd_fcn_forward_timed(sd_fcn* m, const uint8_t* views_dev, size_t n_planes_total, int nb_views, int H, int W, size_t plane0, size_t n_planes,
+                         uint8_t* labels_dev, float* logits_dev, void* workspace_dev, size_t ws_bytes, int32_t* flags_dev, void* stream,
+                         float* ms_out);
+int sd_fcn_overflow(sd_fcn* m, const int32_t* flags_dev, void* stream, int32_t* flags_out);
+int sd_fcn_read_buffer(sd_fcn* m, int index, const void* workspace_dev, const float* logits_dev, size_t n_planes, int H, int W, float* out_host,
+                       int32_t* dims_out, void* stream);
+int sd_fcn_num_ops(sd_fcn* m);
+
 #ifdef __cplusplus
 }
 #endif

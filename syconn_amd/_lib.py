@@ -53,7 +53,8 @@ EXPORTS = ['sd_init', 'sd_device_count', 'sd_model_create', 'sd_model_destroy', 
            'sd_views_candidates_temp_bytes', 'sd_views_candidates', 'sd_views_render_temp_bytes', 'sd_views_render', 'sd_views_render_index',
            'sd_views_vote_temp_bytes', 'sd_views_vote', 'sd_locations_voxel_temp_bytes', 'sd_locations_voxel', 'sd_locations_surface_temp_bytes',
            'sd_locations_surface', 'sd_viewnet_create', 'sd_viewnet_destroy', 'sd_viewnet_workspace_bytes', 'sd_viewnet_forward', 'sd_viewnet_forward_timed',
-           'sd_viewnet_overflow', 'sd_viewnet_read_buffer', 'sd_viewnet_num_ops']
+           'sd_viewnet_overflow', 'sd_viewnet_read_buffer', 'sd_viewnet_num_ops', 'sd_fcn_create', 'sd_fcn_destroy', 'sd_fcn_workspace_bytes',
+           'sd_fcn_forward', 'sd_fcn_forward_timed', 'sd_fcn_overflow', 'sd_fcn_read_buffer', 'sd_fcn_num_ops']
 
 
 class OpDesc(C.Structure):
@@ -279,6 +280,16 @@ def load():
     lib.sd_viewnet_overflow.argtypes = [vp, vp, vp, i32p]; lib.sd_viewnet_overflow.restype = i32
     lib.sd_viewnet_read_buffer.argtypes = [vp, i32, vp, vp, sz, i32, i32, i32, f32p, i32p, vp]; lib.sd_viewnet_read_buffer.restype = i32
     lib.sd_viewnet_num_ops.argtypes = [vp]; lib.sd_viewnet_num_ops.restype = i32
+    # handler/prediction.py:1003-1030 (get_semseg_spiness_model, get_semseg_axon_model) as reps/super_segmentation_helper.py:1353-1392
+    # (predict_views_semseg) calls them
+    lib.sd_fcn_create.argtypes = [i32, i32p, i32p, i32, i32, f32p, sz, i32, C.POINTER(vp)]; lib.sd_fcn_create.restype = i32
+    lib.sd_fcn_destroy.argtypes = [vp]; lib.sd_fcn_destroy.restype = None
+    lib.sd_fcn_workspace_bytes.argtypes = [vp, sz, i32, i32]; lib.sd_fcn_workspace_bytes.restype = sz
+    lib.sd_fcn_forward.argtypes = [vp, vp, sz, i32, i32, i32, sz, sz, vp, vp, vp, sz, vp, vp]; lib.sd_fcn_forward.restype = i32
+    lib.sd_fcn_forward_timed.argtypes = lib.sd_fcn_forward.argtypes + [f32p]; lib.sd_fcn_forward_timed.restype = i32
+    lib.sd_fcn_overflow.argtypes = [vp, vp, vp, i32p]; lib.sd_fcn_overflow.restype = i32
+    lib.sd_fcn_read_buffer.argtypes = [vp, i32, vp, vp, sz, i32, i32, f32p, i32p, vp]; lib.sd_fcn_read_buffer.restype = i32
+    lib.sd_fcn_num_ops.argtypes = [vp]; lib.sd_fcn_num_ops.restype = i32
     _lib = lib
     return lib
 

@@ -86,3 +86,66 @@ def run_celltype_prediction(cells, model=None, views=None, ids=None, nb_views_mo
     nb = global_params.config['celltypes']['nb_views_model'] if nb_views_model is None else nb_views_model
     syn = bool(global_params.config.syntype_available) if use_syntype is None else use_syntype
     return predict_celltypes_table(cells, model, views=views, nb_views_model=nb, use_syntype=syn, bs=bs, ids=ids, **vote_kw)
+
+
+def run_semsegaxoness_prediction(cells, model=None, view_props=None, map_properties=None, pred_key=None, max_dist=None, bs: int = 5, device=None):
+    """exec/exec_inference.py:147-186 over cells in memory, each handled as ``semsegaxoness_predictor`` does
+    (reps/super_segmentation_object.py:3468-3494): ``semseg_of_sso_nocache`` with ``config['compartments']['view_properties_semsegax']``
+    (updated by `view_props`), then ``semsegaxoness2skel`` with ``map_properties_semsegax``, the views' ``semseg_key`` and
+    ``dist_axoness_averaging``.  -> the ids of the cells that raised a ``RuntimeError`` (the reference's "missing" list).  The dataset,
+    job and point-model layers are not built.  `model` defaults to ``get_semseg_axon_model()``; bs = 5 as in the batch job script."""
+    import logging
+    from ..handler.prediction import get_semseg_axon_model
+    from ..reps.super_segmentation_helper import semseg_of_sso_nocache
+    from ..reps.super_segmentation_object import semsegaxoness2skel
+    if global_params.config['use_point_models']:
+        raise NotImplementedError('run_semsegaxoness_prediction: the point models are not built')
+    comp = global_params.config['compartments']
+    props = dict(comp['view_properties_semsegax'])
+    props.update(view_props or {})
+    map_properties = dict(comp['map_properties_semsegax'] if map_properties is None else map_properties)
+    pred_key = props['semseg_key'] if pred_key is None else pred_key
+    max_dist = comp['dist_axoness_averaging'] if max_dist is None else max_dist
+    model = get_semseg_axon_model() if model is None else model
+    missing = []
+    for sso in cells:
+        try:
+            semseg_of_sso_nocache(sso, model, bs=bs, device=device, **props)
+            semsegaxoness2skel(sso, map_properties, pred_key, max_dist)
+        except RuntimeError as e:
+            missing.append(sso.id)
+            logging.getLogger('syconn_amd.reps').error('Error during sem. seg. prediction of SSV {}. {}'.format(sso.id, repr(e)))
+    return missing
+
+
+def run_semsegspiness_prediction(cells, model=None, view_props=None, kwargs_semseg2mesh=None, kwargs_semsegforcoords=None, device=None):
+    """exec/exec_inference.py:189-214 over cells in memory, each handled as ``semsegspiness_predictor`` does (:3560-3597):
+    ``semseg_of_sso_nocache`` with ``config['views']['view_properties']`` (updated by `view_props`) and
+    ``config['spines']['semseg2mesh_spines']``, then the vertex labels at the skeleton nodes (``semseg_for_coords`` with
+    ``semseg2coords_spines``) into ``sso.skeleton[semseg_key]`` and ``sso.save_skeleton()``.  -> the ids of the cells that raised a
+    ``RuntimeError``.  `model` defaults to ``get_semseg_spiness_model()``."""
+    import logging
+    from ..handler.prediction import get_semseg_spiness_model
+    from ..reps.super_segmentation_helper import semseg_of_sso_nocache
+    from ..reps.super_segmentation_object import semseg_for_coords
+    props = dict(global_params.config['views']['view_properties'])
+    props.update(view_props or {})
+    s2m = dict(global_params.config['spines']['semseg2mesh_spines'] if kwargs_semseg2mesh is None else kwargs_semseg2mesh)
+    s2c = dict(global_params.config['spines']['semseg2coords_spines'] if kwargs_semsegforcoords is None else kwargs_semsegforcoords)
+    model = get_semseg_spiness_model() if model is None else model
+    missing = []
+    for sso in cells:
+        try:
+            semseg_of_sso_nocache(sso, model, device=device, **props, **s2m)
+            sso.load_skeleton()
+            if sso.skeleton is None or len(sso.skeleton['nodes']) == 0:
+                logging.getLogger('syconn_amd.reps').warning(f'Skeleton of SSV {sso.id} has zero nodes.')
+                node_preds = np.zeros((0,), dtype=np.int32)
+            else:
+                node_preds = semseg_for_coords(sso, sso.skeleton['nodes'], s2m['semseg_key'], device=device, **s2c)
+            sso.skeleton[s2m['semseg_key']] = node_preds
+            sso.save_skeleton()
+        except RuntimeError as e:
+            missing.append(sso.id)
+            logging.getLogger('syconn_amd.reps').error('Error during sem. seg. prediction of SSV {}. {}'.format(sso.id, repr(e)))
+    return missing

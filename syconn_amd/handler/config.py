@@ -87,8 +87,14 @@ DEFAULTS = {
     },
     # partner properties of the cell-level synapses (config.yml:271-274, :278, :288, :303): the vote over the k nearest mesh vertices
     # (every ds_vertices-th one, without the ignored labels), the skeleton key of the compartment, the length of the embedding
-    'spines': {'semseg2coords_spines': {'k': 50, 'ds_vertices': 1, 'ignore_labels': [4, 5]}},
-    'compartments': {'dist_axoness_averaging': 10000, 'view_properties_semsegax': {'semseg_key': 'axoness'}},
+    'spines': {'semseg2coords_spines': {'k': 50, 'ds_vertices': 1, 'ignore_labels': [4, 5]},
+               # semseg2mesh of the spine labels (config.yml:265-267): k = 0 keeps unpredicted vertices as their own class
+               'semseg2mesh_spines': {'semseg_key': 'spiness', 'k': 0}},
+    # compartment views and the mapping of their vertex labels to skeleton nodes (config.yml:283-295)
+    'compartments': {'dist_axoness_averaging': 10000,
+                     'view_properties_semsegax': {'verbose': False, 'ws': [1024, 512], 'nb_views': 3, 'comp_window': 40960, 'semseg_key': 'axoness',
+                                                  'k': 0},
+                     'map_properties_semsegax': {'k': 50, 'ds_vertices': 1, 'ignore_labels': [5, 6]}},
     'tcmn': {'ndim_embedding': 10},
     # surface meshes (config.yml:169-189): the downsampling of every label volume before meshing, the size below which an object keeps
     # an empty mesh, and the arguments of zmesh's get_mesh -- the two simplification keys are accepted and IGNORED (proc/meshes.py
@@ -228,6 +234,16 @@ class DynConfig:
     def mpath_celltype_e3(self) -> str:
         """config.py:565-570: the view network of the cell type step."""
         return self.model_dir + '/celltype_e3/model.pts'
+
+    @property
+    def mpath_spiness(self) -> str:
+        """config.py:537-544: the 2D semantic-segmentation model of spine head, neck, shaft and other."""
+        return self.model_dir + '/spiness/model.pts'
+
+    @property
+    def mpath_axonsem(self) -> str:
+        """config.py:546-553: the 2D semantic-segmentation model of axon, boutons, dendrite and soma."""
+        return self.model_dir + '/axoness_semseg/model.pts'
 
     @property
     def syntype_available(self) -> bool:

@@ -909,3 +909,146 @@ def get_celltype_model_e3(act_dtype: str = 'f16', n_classes: int = 7, n_scalar: 
     """prediction.py:985-1000: ``torch.jit.load(mpath_celltype_e3)`` -> state dict -> the view network (bs=40 as there)."""
     from ..cnn.viewnet_spec import CELLTYPE_CMN
     return ViewModel(CELLTYPE_CMN(n_classes, n_scalar), global_params.config.mpath_celltype_e3, act_dtype=act_dtype, bs=40)
+
+
+# -- 2D semantic segmentation of multi-views (compartments) -------------------------------------------------------------------------
+def semseg_views_to_uint8(x: np.ndarray) -> np.ndarray:
+    """float32 views that are exactly ``u.astype(np.float32) / 255.`` of uint8 renderings `u` (what ``predict_views_semseg`` hands to
+    the model, reps/super_segmentation_helper.py:1372) back to `u`; anything else is a NotImplementedError: the network reads the uint8
+    renderings and applies 1 / 255 in its first epilogue."""
+    x = np.asarray(x)
+    if x.dtype != np.float32:
+        raise NotImplementedError(f'views must be uint8 or float32 uint8 / 255, got {x.dtype}')
+    with np.errstate(invalid='ignore'):
+        u = np.rint(x.astype(np.float64) * 255.)
+    ok = np.isfinite(u).all() and u.min(initial=0) >= 0 and u.max(initial=0) <= 255
+    if ok:
+        u8 = u.astype(np.uint8)
+        ok = np.array_equal(u8.astype(np.float32) / 255., x)
+    if not ok:
+        raise NotImplementedError('float32 views that are not uint8 views / 255: the semantic-segmentation network reads the uint8 '
+                                  'renderings; pass those')
+    return u8
+
+
+class SemsegViewModel:
+    """``InferenceModel`` of elektronn3 (prediction.py:1003-1030) for an FCN given as a spec (syconn_amd/cnn/fcn_spec.py).
+    ``predict_proba(views (N, C, H, W))`` returns the float32 logits (N, n_class, H, W) -- the reference passes no normalising
+    function and takes the argmax, which a softmax would not change --; ``predict_labels(views (n_loc, C, nb_views, H, W))`` reads
+    the renderer's tensor in place, host or device, and returns the uint8 labels (n_loc, 1, nb_views, H, W) of
+    ``predict_views_semseg`` as the same kind (array or device tensor).  `weights`: a state dict, a module, or the path of a
+    ``torch.jit`` file.  Views are uint8, or float32 that ``semseg_views_to_uint8`` takes.  A launch set holds at most `bs` planes and
+    at most ``max_workspace_bytes`` of workspace."""
+
+    max_workspace_bytes = 4 << 30
+
+    def __init__(self, spec, weights, act_dtype: str = 'f16', bs: int = 10, device=None):
+        from .. import _dev as dv
+        import ctypes as C
+        if act_dtype not in ('f16', 'bf16'):
+            raise ValueError("act_dtype must be 'f16' or 'bf16'")
+        if isinstance(weights, (str, os.PathLike)):
+            weights = torch.jit.load(os.fspath(weights), map_location='cpu')
+        if hasattr(weights, 'state_dict'):
+            weights = weights.state_dict()
+        arrs = spec.weights_from_state_dict(weights)
+        self.spec, self.act_dtype, self.bs = spec, act_dtype, int(bs)
+        if self.bs < 1:
+            raise ValueError('bs must be positive')
+        self.dev = dv.device(device)
+        lib = L.load()
+        blob = np.concatenate([a.ravel() for a in arrs]).astype(np.float32)
+        flat = [c for b in spec.blocks for c in b]
+        blocks, lens = (C.c_int32 * len(flat))(*flat), (C.c_int32 * 5)(*[len(b) for b in spec.blocks])
+        h = C.c_void_p()
+        with torch.cuda.device(self.dev):
+            L.check(lib.sd_fcn_create(spec.in_channels, blocks, lens, spec.dec_last, spec.n_class, blob.ctypes.data_as(C.POINTER(C.c_float)),
+                                      blob.size, L.SD_F16 if act_dtype == 'f16' else L.SD_BF16, C.byref(h)), 'sd_fcn_create')
+        self._h = h
+        self._last = None
+
+    def __del__(self):
+        h, self._h = getattr(self, '_h', None), None
+        if h:
+            L.load().sd_fcn_destroy(h)
+
+    @property
+    def num_ops(self) -> int:
+        return L.load().sd_fcn_num_ops(self._h)
+
+    def _views(self, views, ndim: int) -> torch.Tensor:
+        if isinstance(views, np.ndarray) and views.dtype == np.float32:
+            views = semseg_views_to_uint8(views)
+        v = torch.from_numpy(np.ascontiguousarray(views)) if isinstance(views, np.ndarray) else views
+        shape = '(N, C, H, W)' if ndim == 4 else '(n_loc, C, nb_views, H, W)'
+        if not isinstance(v, torch.Tensor) or v.dtype != torch.uint8 or v.dim() != ndim:
+            raise ValueError(f'views must be a uint8 array / tensor {shape}')
+        if ndim == 4:
+            v = v[:, :, None]
+        if v.shape[1] != self.spec.in_channels:
+            raise ValueError(f'views have {v.shape[1]} channels, the model takes {self.spec.in_channels}')
+        if v.numel() == 0:
+            raise ValueError('views are empty')
+        self.spec.check_geometry(int(v.shape[3]), int(v.shape[4]))
+        return v.to(self.dev).contiguous()
+
+    def _forward(self, v: torch.Tensor, bs: Optional[int], want_logits: bool):
+        from .. import _dev as dv
+        bs = self.bs if bs is None else int(bs)
+        if bs < 1:
+            raise ValueError('bs must be positive')
+        n_loc, _, nb_views, H, W = (int(x) for x in v.shape)
+        n = n_loc * nb_views
+        per_plane = int(L.load().sd_fcn_workspace_bytes(self._h, 1, H, W))
+        nb = max(1, min(bs, n, self.max_workspace_bytes // max(per_plane, 1)))
+        with torch.cuda.device(self.dev):
+            ws = dv.scratch('sd_fcn_workspace_bytes', self.dev, self._h, nb, H, W)
+            labels = torch.empty((n, H, W), dtype=torch.uint8, device=self.dev)
+            logits = torch.empty((n, self.spec.n_class, H, W), dtype=torch.float32, device=self.dev) if want_logits else None
+            flags = torch.zeros((-(-n // nb), 1), dtype=torch.int32, device=self.dev)
+            for i, b in enumerate(range(0, n, nb)):
+                e = min(b + nb, n)
+                dv.call('sd_fcn_forward', self.dev, self._h, v, n, nb_views, H, W, b, e - b, labels[b:e], logits[b:e] if want_logits else None, ws,
+                        ws.numel(), flags[i])
+            fl = flags.cpu().numpy()
+        self._last = (ws, logits[b:e] if want_logits else None, e - b, H, W)
+        if fl.any():
+            raise L.ActivationOverflowError("fp16 activation storage overflowed in the semantic-segmentation network: its labels are "
+                                            "invalid; use act_dtype='bf16'")
+        return labels.view(n_loc, 1, nb_views, H, W), logits
+
+    def predict_proba(self, views, bs: Optional[int] = None, verbose: bool = False) -> np.ndarray:
+        _, logits = self._forward(self._views(views, 4), bs, True)
+        return logits.cpu().numpy()
+
+    def predict_labels(self, views, bs: Optional[int] = None):
+        labels, _ = self._forward(self._views(views, 5), bs, False)
+        return labels if isinstance(views, torch.Tensor) else labels.cpu().numpy()
+
+    def read_buffer(self, index: int) -> np.ndarray:
+        """Debug: after a forward, the stored output of op `index` of the LAST launch set as float32 (planes, h, w, c); the last op's are
+        the logits (planes, n_class, H, W) (``predict_proba`` only)."""
+        from .. import _dev as dv
+        import ctypes as C
+        if self._last is None:
+            raise RuntimeError('read_buffer: no forward yet')
+        ws, logits, n, H, W = self._last
+        lib = L.load()
+        dims = (C.c_int32 * 4)()
+        args = (self._h, int(index), ws.data_ptr(), logits.data_ptr() if logits is not None else None, n, H, W)
+        L.check(lib.sd_fcn_read_buffer(*args, None, dims, dv.stream(self.dev)), 'sd_fcn_read_buffer')
+        out = np.empty(tuple(dims), dtype=np.float32)
+        L.check(lib.sd_fcn_read_buffer(*args, out.ctypes.data_as(C.POINTER(C.c_float)), dims, dv.stream(self.dev)), 'sd_fcn_read_buffer')
+        return out
+
+
+def get_semseg_spiness_model(act_dtype: str = 'f16', n_class: int = 5):
+    """prediction.py:1003-1015: ``torch.jit.load(mpath_spiness)`` -> state dict -> the FCN (cnn/cnn_spineseg.py:28-29)."""
+    from ..cnn.fcn_spec import FCN_VGG13
+    return SemsegViewModel(FCN_VGG13(n_class), global_params.config.mpath_spiness, act_dtype=act_dtype)
+
+
+def get_semseg_axon_model(act_dtype: str = 'f16', n_class: int = 6):
+    """prediction.py:1018-1030: ``torch.jit.load(mpath_axonsem)`` -> state dict -> the FCN (cnn/cnn_axonseg.py:34-35)."""
+    from ..cnn.fcn_spec import FCN_VGG13
+    return SemsegViewModel(FCN_VGG13(n_class), global_params.config.mpath_axonsem, act_dtype=act_dtype)

@@ -580,3 +580,44 @@ def predict_celltypes_table(cells, model, views=None, nb_views_model: int = 20, 
     ids = np.arange(len(cells)) if ids is None else np.asarray(ids)
     return CellTypeTable(ids, np.array([v[0] for v in votes], np.int64), np.array([v[2] for v in votes], np.float64),
                          np.concatenate([v[1] for v in votes]), np.array(begin, np.int64))
+
+
+# -- compartment labels from multi-views (reps/super_segmentation_helper.py:1353-1392, :1820-1905) ----------------------------------
+def predict_views_semseg(views, model, batch_size=10, verbose=False):
+    """Drop-in of ``predict_views_semseg`` (:1353-1392): `views` uint8 (N_LOCS, N_CH, N_VIEWS, H, W), host array or device tensor ->
+    the pixel labels (N_LOCS, 1, N_VIEWS, H, W), ``argmax`` over the classes of ``model(views / 255)``, as the same kind.  `model`: a
+    ``handler.prediction.SemsegViewModel``; it reads the views where they are (no swap of the channel and view axes is made) and takes
+    the argmax on the device, where the first maximum wins as in ``np.argmax``.  Labels are uint8 (the reference's are int64; its
+    consumer ``semseg2mesh`` reads them as uint8 counts)."""
+    return model.predict_labels(views, bs=batch_size)
+
+
+def semseg_of_sso_nocache(sso, model, semseg_key: str, ws, nb_views: int, comp_window: float, k: int = 1, dest_path=None, verbose: bool = False,
+                          add_cellobjects=True, bs: int = 10, device=None):
+    """:1820-1905 without the view storage: raw views at ``generate_rendering_locs(verts, comp_window / 3)`` (or ``sso._sample_locations``
+    if set) -> pixel labels -> index views at the same locations -> ``semseg2mesh``.  Raw views and labels stay on the device.  The
+    vertex labels are stored as ``sso.label_dict('vertex')[semseg_key]`` (pushed if the dict has ``push``) and returned.  `sso`:
+    anything with ``.mesh``, ``.load_mesh(name)``, ``.label_dict('vertex')`` and a settable ``_sample_locations``."""
+    from ..handler.multiviews import generate_rendering_locs
+    from ..proc.rendering import render_sso_coords, render_sso_coords_index_views
+    if dest_path is not None:
+        raise NotImplementedError('semseg_of_sso_nocache: writing the coloured mesh to a k.zip is not built')
+    verts = np.asarray(sso.mesh[1]).reshape(-1, 3)
+    locs = getattr(sso, '_sample_locations', None)
+    if locs is None:
+        locs = generate_rendering_locs(verts, comp_window / 3, device=device)
+        sso._sample_locations = [locs]
+    locs = np.concatenate(locs) if isinstance(locs, (list, tuple)) else np.asarray(locs)
+    views = render_sso_coords(sso, locs, ws=ws, comp_window=comp_window, nb_views=nb_views, verbose=verbose, add_cellobjects=add_cellobjects,
+                              device=device, return_device=True)
+    if len(views) != len(locs):
+        raise ValueError('Unequal number of views and redering locations.')
+    labeled = predict_views_semseg(views, model, batch_size=bs, verbose=verbose)
+    assert labeled.shape[2] == nb_views, 'Predictions have wrong shape.'
+    index_views = render_sso_coords_index_views(sso, locs, ws=ws, comp_window=comp_window, nb_views=nb_views, verbose=verbose, device=device)
+    col = semseg2mesh(sso, semseg_key, k=k, force_recompute=True, index_views=index_views, semseg_views=labeled.cpu().numpy(), device=device)[3]
+    ld = sso.label_dict('vertex')
+    ld[semseg_key] = col
+    if hasattr(ld, 'push'):
+        ld.push()
+    return col

@@ -117,3 +117,54 @@ def certainty_celltype(sso, pred_key=None) -> float:
     if cert is not None:
         return cert
     return certainty_estimate(sso.attr_dict[pred_key + '_probas'], is_logit=True)
+
+
+# -- compartment labels (predict_semseg, :2022-2120) -------------------------------------------------------------------------------------
+def predict_semseg(sso, m, semseg_key: str, nb_views=None, verbose: bool = False, raw_view_key=None, save: bool = False, ws=None,
+                   comp_window=None, add_cellobjects=True, bs: int = 10, views=None):
+    """reps/super_segmentation_object.py:2072-2093, the non-default branch (`nb_views`, `raw_view_key` or `views` given): the pixel
+    labels of the raw views `views` (n_loc, C, nb_views, H, W), host or device -- rendered here at ``sso._sample_locations`` with `ws`
+    and `comp_window` if not passed -- through ``predict_views_semseg``; returned, and kept in ``sso.view_dict[semseg_key]`` when the
+    cell caches views.  The default branch (views stored per supervoxel) and `save` need the view storage, which is not built."""
+    from . import super_segmentation_helper as ssh
+    if nb_views is None and raw_view_key is None and views is None:
+        raise NotImplementedError('predict_semseg: the per-supervoxel view storage is not built; pass nb_views (and views, or ws and comp_window)')
+    if save:
+        raise NotImplementedError('predict_semseg: the view storage is not built (save=True)')
+    if views is None:
+        from .. import global_params
+        from ..proc.rendering import render_sso_coords
+        if nb_views is None:
+            nb_views = global_params.config['views']['view_properties']['nb_views']
+        locs = getattr(sso, '_sample_locations', None)
+        if locs is None:
+            raise ValueError('predict_semseg: no views and no rendering locations (sso._sample_locations)')
+        locs = np.concatenate(locs) if isinstance(locs, (list, tuple)) else np.asarray(locs)
+        views = render_sso_coords(sso, locs, ws=ws, comp_window=comp_window, nb_views=nb_views, verbose=verbose, add_cellobjects=add_cellobjects,
+                                  return_device=True)
+    labeled_views = ssh.predict_views_semseg(views, m, verbose=verbose, batch_size=bs)
+    if nb_views is not None:
+        assert labeled_views.shape[2] == nb_views, "Predictions have wrong shape."
+    if getattr(sso, 'view_caching', False) and hasattr(sso, 'view_dict'):
+        sso.view_dict[semseg_key] = labeled_views
+    return labeled_views
+
+
+def semseg_for_coords(sso, coords, semseg_key: str, k: int = 5, ds_vertices: int = 20, ignore_labels=None, device=None) -> np.ndarray:
+    """reps/super_segmentation_object.py:2190-2240 for one cell: the majority label of the `k` nearest mesh vertices (every
+    `ds_vertices`-th one, without `ignore_labels`) of every coordinate (voxels; scaled by ``sso.scaling``), int32.  Zeros without
+    vertices or coordinates, as there."""
+    from ..extraction.cs_processing_steps import CellTable, _check_positive_int, segmented_knn, spine_vertices
+    coords = np.asarray(coords).reshape(-1, 3)
+    verts = np.asarray(sso.mesh[1]).reshape(-1, 3)
+    if len(coords) == 0 or len(verts) == 0:
+        return np.zeros(len(coords), np.int32)
+    _check_positive_int(k=k, ds_vertices=ds_vertices)
+    if int(k) > L.SD_SYN_PROPS_MAX_K:
+        raise ValueError(f'k = {k}: at most {L.SD_SYN_PROPS_MAX_K} neighbours per query')
+    cells = CellTable([sso.id], verts, [0, len(verts)], {semseg_key: sso.label_dict('vertex')[semseg_key]}, coords, [0, len(coords)], {})
+    v, lab, begin = spine_vertices(cells, np.array([True]), semseg_key, int(ds_vertices), ignore_labels)
+    if begin[-1] == 0:
+        raise ValueError(f'every mesh vertex of cell {sso.id} carries an ignored label: no vertex to vote')
+    q_xyz = np.asarray(coords * np.asarray(sso.scaling), np.float64)
+    return segmented_knn(v, begin, lab, np.zeros(len(coords), np.int64), q_xyz, int(k), device).astype(np.int32)
