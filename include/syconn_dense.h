@@ -1028,10 +1028,24 @@ int sd_plan_clip_window(const sd_op_desc* ops, int n_ops, int axis, int lo, int 
  *                         its activation; the last one is the logits) as float32 [n_samples][out].  dims_out[4] = those extents
  *                         (the head's as [n_samples][1][1][out]).  out_host may be null to query dims_out only.
  *   sd_viewnet_num_ops    n_layers + n_fc.
+ *   sd_viewnet_embed      sd_viewnet_forward -- the same arguments, layer launches, flags, workspace layout and checks -- with the
+ *                         sample-tiled head: the form for calls of many samples with little convolution work each, as the
+ *                         morphology embedding of /root/reference/syconn/reps/super_segmentation_helper.py:1758-1817 and
+ *                         super_segmentation_object.py:3032-3079 through the RepresentationNetwork of
+ *                         /root/reference/syconn/cnn/cnn_atn.py:21-55 (one sample = view 0 of one rendering location: D = 1,
+ *                         table entry loc * nb_views).  A workgroup takes TS consecutive samples and reads every head weight once
+ *                         per tile; per sample the arithmetic is that of sd_viewnet_forward's head, operation for operation, so the
+ *                         logits and every hidden vector have the same bits.  TS = the largest of 8, 4, 2, 1 for which
+ *                         4 TS (inputs of the first Linear + 2 x the widest Linear output) bytes fit 160 KiB.
+ *   sd_viewnet_embed_timed  the same with the events of sd_viewnet_forward_timed (tools/embedding_probe.py).
+ *   sd_viewnet_embed_tile_samples  TS of the model (0 for null).
+ *   sd_viewnet_read_buffer works after either entry.
  * One grid stride of the layer kernel is SD_VIEWNET_GRID blocks (one block = 8 x 32 convolution outputs of one plane), of the head
- * kernel SD_VIEWNET_HEAD_GRID blocks (one block = one sample); neither constant rests on a measurement. */
+ * kernel SD_VIEWNET_HEAD_GRID blocks (one block = one sample), of the tiled head kernel SD_VIEWNET_HEAD_TILE_GRID blocks (one block =
+ * one tile of TS samples); none of the three constants rests on a measurement. */
 #define SD_VIEWNET_GRID 2048
 #define SD_VIEWNET_HEAD_GRID 32
+#define SD_VIEWNET_HEAD_TILE_GRID 1024
 typedef struct sd_viewnet_layer_desc { int32_t cout, k, pool; } sd_viewnet_layer_desc;
 typedef struct sd_viewnet sd_viewnet;
 int sd_viewnet_create(const sd_viewnet_layer_desc* layers, int n_layers, const int32_t* fc, int n_fc, int in_channels, int n_scalar, int act,
@@ -1044,6 +1058,13 @@ int sd_viewnet_forward(sd_viewnet* m, const uint8_t* views_dev, size_t n_planes_
 int sd_viewnet_forward_timed(sd_viewnet* m, const uint8_t* views_dev, size_t n_planes_total, int nb_views, int H, int W,
                              const int32_t* sample_table_dev, size_t n_samples, int D, const float* scalars_dev, float* logits_dev,
                              void* workspace_dev, size_t ws_bytes, int32_t* flags_dev, void* stream, float* ms_out);
+int sd_viewnet_embed(sd_viewnet* m, const uint8_t* views_dev, size_t n_planes_total, int nb_views, int H, int W, const int32_t* sample_table_dev,
+                     size_t n_samples, int D, const float* scalars_dev, float* logits_dev, void* workspace_dev, size_t ws_bytes,
+                     int32_t* flags_dev, void* stream);
+int sd_viewnet_embed_timed(sd_viewnet* m, const uint8_t* views_dev, size_t n_planes_total, int nb_views, int H, int W,
+                           const int32_t* sample_table_dev, size_t n_samples, int D, const float* scalars_dev, float* logits_dev,
+                           void* workspace_dev, size_t ws_bytes, int32_t* flags_dev, void* stream, float* ms_out);
+int sd_viewnet_embed_tile_samples(sd_viewnet* m);
 int sd_viewnet_overflow(sd_viewnet* m, const int32_t* flags_dev, void* stream, int32_t* flags_out);
 int sd_viewnet_read_buffer(sd_viewnet* m, int index, const void* workspace_dev, const float* logits_dev, size_t n_samples, int D, int H, int W,
                            float* out_host, int32_t* dims_out, void* stream);

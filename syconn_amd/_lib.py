@@ -22,7 +22,7 @@ SD_MESH_GRID = 256
 SD_GLIA_GRID = 1024
 SD_VIEWS_GRID, SD_VIEWS_RASTER_GRID, SD_VIEWS_MAX_VIEWS, SD_VIEWS_TILE_PX = 1024, 4096, 16, 32768
 SD_LOCATIONS_GRID, SD_LOCATIONS_WAVE_GRID, SD_LOCATIONS_MAX_CELLS = 1024, 4096, 1 << 21
-SD_VIEWNET_GRID, SD_VIEWNET_HEAD_GRID = 2048, 32
+SD_VIEWNET_GRID, SD_VIEWNET_HEAD_GRID, SD_VIEWNET_HEAD_TILE_GRID = 2048, 32, 1024
 
 LIB_NAME = 'libsyconn_dense_hip.so'
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), os.environ.get('SD_LIB_NAME', LIB_NAME))
@@ -53,7 +53,8 @@ EXPORTS = ['sd_init', 'sd_device_count', 'sd_model_create', 'sd_model_destroy', 
            'sd_views_candidates_temp_bytes', 'sd_views_candidates', 'sd_views_render_temp_bytes', 'sd_views_render', 'sd_views_render_index',
            'sd_views_vote_temp_bytes', 'sd_views_vote', 'sd_locations_voxel_temp_bytes', 'sd_locations_voxel', 'sd_locations_surface_temp_bytes',
            'sd_locations_surface', 'sd_viewnet_create', 'sd_viewnet_destroy', 'sd_viewnet_workspace_bytes', 'sd_viewnet_forward', 'sd_viewnet_forward_timed',
-           'sd_viewnet_overflow', 'sd_viewnet_read_buffer', 'sd_viewnet_num_ops', 'sd_fcn_create', 'sd_fcn_destroy', 'sd_fcn_workspace_bytes',
+           'sd_viewnet_overflow', 'sd_viewnet_read_buffer', 'sd_viewnet_num_ops', 'sd_viewnet_embed', 'sd_viewnet_embed_timed',
+           'sd_viewnet_embed_tile_samples', 'sd_fcn_create', 'sd_fcn_destroy', 'sd_fcn_workspace_bytes',
            'sd_fcn_forward', 'sd_fcn_forward_timed', 'sd_fcn_overflow', 'sd_fcn_read_buffer', 'sd_fcn_num_ops']
 
 
@@ -277,6 +278,10 @@ def load():
     lib.sd_viewnet_workspace_bytes.argtypes = [vp, sz, i32, i32, i32]; lib.sd_viewnet_workspace_bytes.restype = sz
     lib.sd_viewnet_forward.argtypes = [vp, vp, sz, i32, i32, i32, vp, sz, i32, vp, vp, vp, sz, vp, vp]; lib.sd_viewnet_forward.restype = i32
     lib.sd_viewnet_forward_timed.argtypes = lib.sd_viewnet_forward.argtypes + [f32p]; lib.sd_viewnet_forward_timed.restype = i32
+    # reps/super_segmentation_helper.py:1758-1817 (view_embedding_of_sso_nocache) for cnn/cnn_atn.py:21-55 (RepresentationNetwork)
+    lib.sd_viewnet_embed.argtypes = lib.sd_viewnet_forward.argtypes; lib.sd_viewnet_embed.restype = i32
+    lib.sd_viewnet_embed_timed.argtypes = lib.sd_viewnet_forward_timed.argtypes; lib.sd_viewnet_embed_timed.restype = i32
+    lib.sd_viewnet_embed_tile_samples.argtypes = [vp]; lib.sd_viewnet_embed_tile_samples.restype = i32
     lib.sd_viewnet_overflow.argtypes = [vp, vp, vp, i32p]; lib.sd_viewnet_overflow.restype = i32
     lib.sd_viewnet_read_buffer.argtypes = [vp, i32, vp, vp, sz, i32, i32, i32, f32p, i32p, vp]; lib.sd_viewnet_read_buffer.restype = i32
     lib.sd_viewnet_num_ops.argtypes = [vp]; lib.sd_viewnet_num_ops.restype = i32

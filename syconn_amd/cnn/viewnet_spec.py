@@ -29,12 +29,15 @@ class ViewNetSpec:
     n_scalar: int = 0
     act: str = 'relu'
     name: str = field(default='viewnet', compare=False)
+    conv_ndim: int = 3                            # 3: Conv3d weights (cout, cin, 1, k, k); 2: Conv2d weights (cout, cin, k, k)
 
     def __post_init__(self):
         object.__setattr__(self, 'layers', tuple(tuple(int(v) for v in l) for l in self.layers))
         object.__setattr__(self, 'fc', tuple(int(v) for v in self.fc))
         if self.act not in ACTS:
             raise ValueError(f'act must be one of {ACTS}, got {self.act!r}')
+        if self.conv_ndim not in (2, 3):
+            raise ValueError('conv_ndim must be 2 (Conv2d weights) or 3 (Conv3d weights)')
         if not 1 <= self.in_channels <= 4:
             raise ValueError('in_channels must be 1 to 4 (the renderer writes at most four channels)')
         if not self.layers:
@@ -76,10 +79,11 @@ class ViewNetSpec:
         return (self.fc_in + self.n_scalar,) + self.fc + (self.n_classes,)
 
     def param_shapes(self) -> 'OrderedDict[str, tuple]':
-        """Registration order of the reference's module: 5-D convolution weights and biases, then the Linear ones."""
+        """Registration order of the reference's module: convolution weights (5-D, or 4-D with ``conv_ndim = 2``) and biases, then the
+        Linear ones."""
         out, cin = OrderedDict(), self.in_channels
         for i, (cout, k, _) in enumerate(self.layers):
-            out[f'seq.{i}.conv.weight'] = (cout, cin, 1, k, k)
+            out[f'seq.{i}.conv.weight'] = (cout, cin, 1, k, k) if self.conv_ndim == 3 else (cout, cin, k, k)
             out[f'seq.{i}.conv.bias'] = (cout,)
             cin = cout
         sizes = self.linear_sizes
@@ -104,8 +108,8 @@ class ViewNetSpec:
     # -- weights --------------------------------------------------------------------------------------------------------------
     def weights_from_state_dict(self, state_dict) -> List[np.ndarray]:
         """The float32 arrays [w, b, w, b, ...] of the spec from a state dict in registration order, whatever its keys are called
-        (so a ``torch.jit.load``-ed module works): the 5-D tensors are the convolution weights, the 2-D ones the Linear weights, each
-        followed by its 1-D bias.  Every shape is checked against the spec; other entries (none in the reference's module) raise."""
+        (so a ``torch.jit.load``-ed module works, and a module wrapped in another one): the 5-D tensors (4-D for a ``conv_ndim = 2``
+        spec) are the convolution weights, the 2-D ones the Linear weights, each followed by its 1-D bias.  Every shape is checked against the spec; other entries (none in the reference's module) raise."""
         arrs = [(k, np.ascontiguousarray(v.detach().cpu().numpy() if hasattr(v, 'detach') else np.asarray(v), dtype=np.float32))
                 for k, v in state_dict.items()]
         want = list(self.param_shapes().items())
@@ -130,3 +134,15 @@ def VIEWNET_SMALL(n_classes: int = 2, n_scalar: int = 0, act: str = 'relu', in_c
     convolution stack of the glia view model."""
     return ViewNetSpec(in_channels, ((13, 5, 2), (19, 5, 2), (25, 4, 2), (25, 4, 2), (30, 2, 2), (30, 1, 2), (31, 1, 1)), 1860,
                        (50, 30), n_classes, n_scalar, act, name='viewnet_small')
+
+
+def TNET_REP(z_dim: int = 25, fc_in: int = 372, in_channels: int = 4) -> ViewNetSpec:
+    """``RepresentationNetwork`` of cnn_atn.py:21-55 as ``get_model`` builds it (:111-116, ReLU; Dropout2d is the identity in
+    inference): Conv2d 13 (5, pool) / 19 (5, pool) / 25 (4) / 25 (4, pool) / 30 (2, pool) / 30 (2, pool) / 31 (1), then
+    Linear(fc_in, 50) -> ReLU -> Linear(50, z_dim) on single views (D = 1).  ``fc_in = 372`` is what the 128 x 256 window of the config
+    flattens to (31 x 2 x 6) and what the tree's commented ``Linear(372, 50)`` takes; the module as written has ``Linear(6076, 50)``,
+    and 6076 = 31 x 14 x 14 is what a 512 x 512 view flattens to: 512 -> 508 -> 254 -> 250 -> 125 -> 122 -> 119 -> 59 -> 58 -> 29 -> 28 ->
+    14.  The smallest view the stack takes is 92 x 92 (31 features).  Weights are ``Conv2d`` ones (``conv_ndim = 2``): the state dict
+    of the bare module (``conv.N.*``, ``fc.N.*``) and of the whole ``TripletNet`` (``rep_net.*``) load alike, by registration order."""
+    return ViewNetSpec(in_channels, ((13, 5, 2), (19, 5, 2), (25, 4, 1), (25, 4, 2), (30, 2, 2), (30, 2, 2), (31, 1, 1)), fc_in, (50,), z_dim,
+                       0, 'relu', name='tnet_rep', conv_ndim=2)

@@ -57,6 +57,22 @@ struct Workspace { std::vector<size_t> layer_off, hidden_off; size_t total = 0; 
 int workspace(const Plan& p, size_t n_samples, int D, int H, int W, Workspace& ws, std::string& err);
 // multiply-adds of one sample, convolutions (real channels, computed pixels only) + head
 double macs_per_sample(const Plan& p, int D, int H, int W);
+// The sample-tiled head (k_vn_head_tile): TS samples of a workgroup share one pass over the weights.  LDS: the input tile [TS][nin of
+// the first Linear] and two hidden tiles [TS][hmax], float; TS = the largest of 8, 4, 2, 1 that fits the 160 KiB a gfx950 workgroup can
+// have (TS = 1 always fits: three vectors of at most 8192 values).
+constexpr size_t HEAD_TILE_LDS = 160 * 1024;
+constexpr int HEAD_TILE_THREADS = 512;      // 8 waves, one output row of a Linear each
+inline int head_tile_hmax(const Plan& p) {
+    int h = 0;
+    for (const Fc& f : p.fc) h = f.nout > h ? f.nout : h;
+    return h;
+}
+inline size_t head_tile_lds(const Plan& p, int TS) { return sizeof(float) * (size_t)TS * ((size_t)p.fc[0].nin + 2 * (size_t)head_tile_hmax(p)); }
+inline int head_tile_samples(const Plan& p) {
+    for (int ts = 8; ts > 1; ts >>= 1)
+        if (head_tile_lds(p, ts) <= HEAD_TILE_LDS) return ts;
+    return 1;
+}
 // storage type <-> float (the plan's rounding: nearest even)
 uint16_t to_storage(float f, int dtype);
 float from_storage(uint16_t bits, int dtype);

@@ -222,6 +222,101 @@ __global__ __launch_bounds__(256) void k_vn_head(const HeadArgs a) {
     }
 }
 
+// TS consecutive samples per block (the embedding call: one sample per rendering location, thousands of them, each a single plane of
+// convolution work).  x = [TS][nin of the first Linear] in LDS, filled once per tile in k_vn_head's order; every output row j of a
+// Linear belongs to one wave, whose lanes load w[j][i] once for i = lane, lane + 64, ... and feed TS accumulators from it -- per sample
+// the FMA chain, the butterfly, the bias add and the activation of k_vn_head, in its order, so every sample has k_vn_head's bits; only
+// the weight traffic differs (once per tile, not once per sample).  Lanes of a wave read consecutive floats of one LDS row: no bank
+// conflict.  After the butterfly every lane holds every sum, so lane t stores sample t.  A partial last tile stages, accumulates and
+// stores its real samples only.  The hidden tiles are [TS][hmax], hmax = the widest Linear output.
+template <typename T, int TS>
+__global__ __launch_bounds__(HEAD_TILE_THREADS) void k_vn_head_tile(const HeadArgs a, const int hmax) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char vn_smem[];
+    float* x = reinterpret_cast<float*>(vn_smem);
+    float* y0 = x + (size_t)TS * a.nin[0];
+    float* y1 = y0 + (size_t)TS * hmax;
+    constexpr int NW = HEAD_TILE_THREADS / 64;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int flat = a.C * a.S, nin0 = a.nin[0];
+    const long long n_tiles = (a.n_samples + TS - 1) / TS;
+    for (long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const long long s0 = tile * TS;
+        const int nt = (int)(a.n_samples - s0 < TS ? a.n_samples - s0 : TS);      // real samples of this tile
+        __syncthreads();
+        for (int t = 0; t < nt; ++t) {
+            const T* f = reinterpret_cast<const T*>(a.feat) + (size_t)(s0 + t) * a.S * a.cp;
+            float* xt = x + (size_t)t * nin0;
+            for (int i = tid; i < flat; i += HEAD_TILE_THREADS) {
+                const int c = i / a.S, sp = i - c * a.S;
+                xt[i] = (float)f[(size_t)sp * a.cp + c];
+            }
+            for (int i = tid; i < a.n_scalar; i += HEAD_TILE_THREADS) xt[flat + i] = a.scal[(size_t)(s0 + t) * a.n_scalar + i];
+        }
+        __syncthreads();
+        const float* xin = x;
+        int xs = nin0;
+        float* xout = y0;
+        for (int l = 0; l < a.n_fc; ++l) {
+            const int nin = a.nin[l], nout = a.nout[l];
+            for (int j = wave; j < nout; j += NW) {
+                const float* w = a.w[l] + (size_t)j * nin;
+                float sum[TS];
+#pragma unroll
+                for (int t = 0; t < TS; ++t) sum[t] = 0.f;
+                if (nt == TS) {
+                    for (int i = lane; i < nin; i += 64) {
+                        const float wv = w[i];
+#pragma unroll
+                        for (int t = 0; t < TS; ++t) sum[t] = fmaf(wv, xin[t * xs + i], sum[t]);
+                    }
+                } else {
+                    for (int i = lane; i < nin; i += 64) {
+                        const float wv = w[i];
+#pragma unroll
+                        for (int t = 0; t < TS; ++t)
+                            if (t < nt) sum[t] = fmaf(wv, xin[t * xs + i], sum[t]);      // rows t >= nt were never staged
+                    }
+                }
+#pragma unroll
+                for (int t = 0; t < TS; ++t)
+#pragma unroll
+                    for (int d = 32; d >= 1; d >>= 1) sum[t] += __shfl_xor(sum[t], d);
+                float mine = sum[0];
+#pragma unroll
+                for (int t = 1; t < TS; ++t) mine = lane == t ? sum[t] : mine;
+                if (lane < nt) {
+                    float v = mine + a.b[l][j];
+                    if (l + 1 < a.n_fc) v = v < 0.f ? fmaf(v, a.slope, 0.f) : v;
+                    xout[lane * hmax + j] = v;
+                    a.h[l][(size_t)(s0 + lane) * nout + j] = v;
+                }
+            }
+            __syncthreads();
+            xin = xout, xs = hmax;
+            xout = xout == y0 ? y1 : y0;
+        }
+    }
+}
+
+template <typename T, int TS>
+hipError_t launch_head_tile(int grid, size_t lds, hipStream_t s, const HeadArgs& a, int hmax) {
+    if (lds > 65536) {      // beyond the default limit of dynamic LDS: ask for it
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_vn_head_tile<T, TS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL((k_vn_head_tile<T, TS>), dim3(grid), dim3(HEAD_TILE_THREADS), lds, s, a, hmax);
+    return hipSuccess;
+}
+template <typename T>
+hipError_t launch_head_tile_ts(int TS, int grid, size_t lds, hipStream_t s, const HeadArgs& a, int hmax) {
+    switch (TS) {
+    case 8: return launch_head_tile<T, 8>(grid, lds, s, a, hmax);
+    case 4: return launch_head_tile<T, 4>(grid, lds, s, a, hmax);
+    case 2: return launch_head_tile<T, 2>(grid, lds, s, a, hmax);
+    default: return launch_head_tile<T, 1>(grid, lds, s, a, hmax);
+    }
+}
+
 int fail(const std::string& msg, int code = SD_ERR_INVALID) { return sd_fail_msg(code, msg.c_str()); }
 
 template <typename T, bool FIRST>
@@ -294,20 +389,21 @@ int sd_viewnet_num_ops(sd_viewnet* m) { return m ? (int)(m->plan.layers.size() +
 // ev (or null): n_layers + 2 events, recorded in front of the first launch and behind every launch
 static int vn_forward(sd_viewnet* m, const uint8_t* views_dev, size_t n_planes_total, int nb_views, int H, int W, const int32_t* sample_table_dev,
                       size_t n_samples, int D, const float* scalars_dev, float* logits_dev, void* workspace_dev, size_t ws_bytes,
-                      int32_t* flags_dev, void* stream, hipEvent_t* ev) {
-    if (!m || !views_dev || !sample_table_dev || !logits_dev || !workspace_dev || !flags_dev) return fail("sd_viewnet_forward: null argument");
+                      int32_t* flags_dev, void* stream, hipEvent_t* ev, bool tiled_head = false) {
+    const std::string who = tiled_head ? "sd_viewnet_embed" : "sd_viewnet_forward";
+    if (!m || !views_dev || !sample_table_dev || !logits_dev || !workspace_dev || !flags_dev) return fail(who + ": null argument");
     const Plan& p = m->plan;
-    if (p.n_scalar > 0 && !scalars_dev) return fail("sd_viewnet_forward: the model takes scalars, scalars_dev is null");
+    if (p.n_scalar > 0 && !scalars_dev) return fail(who + ": the model takes scalars, scalars_dev is null");
     if (nb_views < 1 || n_planes_total < 1 || n_planes_total % (size_t)nb_views != 0 || n_planes_total > ((size_t)1 << 31) - 1)
-        return fail("sd_viewnet_forward: n_planes_total must be a multiple of nb_views below 2^31");
+        return fail(who + ": n_planes_total must be a multiple of nb_views below 2^31");
     Workspace ws;
     std::vector<Dims> dims;
     std::string err;
     if (workspace(p, n_samples, D, H, W, ws, err) != SD_OK || infer_shapes(p, D, H, W, dims, err) != SD_OK) return fail(err);
-    if (ws_bytes < ws.total) return fail("sd_viewnet_forward: workspace smaller than sd_viewnet_workspace_bytes(m, n_samples, D, H, W)");
-    if ((reinterpret_cast<uintptr_t>(workspace_dev) & 15) != 0) return fail("sd_viewnet_forward: workspace must be 16-byte aligned");
+    if (ws_bytes < ws.total) return fail(who + ": workspace smaller than sd_viewnet_workspace_bytes(m, n_samples, D, H, W)");
+    if ((reinterpret_cast<uintptr_t>(workspace_dev) & 15) != 0) return fail(who + ": workspace must be 16-byte aligned");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (hipMemsetAsync(flags_dev, 0, 2 * sizeof(int32_t), s) != hipSuccess) return fail("sd_viewnet_forward: memset failed", SD_ERR_HIP);
+    if (hipMemsetAsync(flags_dev, 0, 2 * sizeof(int32_t), s) != hipSuccess) return fail(who + ": memset failed", SD_ERR_HIP);
     if (ev) (void)hipEventRecord(ev[0], s);
     char* wsb = reinterpret_cast<char*>(workspace_dev);
     const long long planes = (long long)n_samples * D;
@@ -346,12 +442,21 @@ static int vn_forward(sd_viewnet* m, const uint8_t* views_dev, size_t n_planes_t
         ha.h[j] = j + 1 < ha.n_fc ? reinterpret_cast<float*>(wsb + ws.hidden_off[j]) : logits_dev;
         ha.maxlen = std::max(ha.maxlen, std::max(ha.nin[j], ha.nout[j]));
     }
-    const int hgrid = (int)std::min<long long>(ha.n_samples, SD_VIEWNET_HEAD_GRID);
-    const size_t hlds = 2 * sizeof(float) * (size_t)ha.maxlen;
-    if (p.act_dtype == SD_F16) hipLaunchKernelGGL(k_vn_head<f16_t>, dim3(hgrid), dim3(256), hlds, s, ha);
-    else hipLaunchKernelGGL(k_vn_head<bf16_t>, dim3(hgrid), dim3(256), hlds, s, ha);
+    if (tiled_head) {
+        const int TS = head_tile_samples(p), hmax = head_tile_hmax(p);
+        const long long tiles = (ha.n_samples + TS - 1) / TS;
+        const int hgrid = (int)std::min<long long>(tiles, SD_VIEWNET_HEAD_TILE_GRID);
+        const size_t hlds = head_tile_lds(p, TS);
+        const hipError_t e = p.act_dtype == SD_F16 ? launch_head_tile_ts<f16_t>(TS, hgrid, hlds, s, ha, hmax) : launch_head_tile_ts<bf16_t>(TS, hgrid, hlds, s, ha, hmax);
+        if (e != hipSuccess) return fail(who + ": the head's LDS request was refused", SD_ERR_HIP);
+    } else {
+        const int hgrid = (int)std::min<long long>(ha.n_samples, SD_VIEWNET_HEAD_GRID);
+        const size_t hlds = 2 * sizeof(float) * (size_t)ha.maxlen;
+        if (p.act_dtype == SD_F16) hipLaunchKernelGGL(k_vn_head<f16_t>, dim3(hgrid), dim3(256), hlds, s, ha);
+        else hipLaunchKernelGGL(k_vn_head<bf16_t>, dim3(hgrid), dim3(256), hlds, s, ha);
+    }
     if (ev) (void)hipEventRecord(ev[p.layers.size() + 1], s);
-    return hipGetLastError() == hipSuccess ? SD_OK : fail("sd_viewnet_forward: launch failed", SD_ERR_HIP);
+    return hipGetLastError() == hipSuccess ? SD_OK : fail(who + ": launch failed", SD_ERR_HIP);
 }
 
 int sd_viewnet_forward(sd_viewnet* m, const uint8_t* views_dev, size_t n_planes_total, int nb_views, int H, int W, const int32_t* sample_table_dev,
@@ -361,25 +466,49 @@ int sd_viewnet_forward(sd_viewnet* m, const uint8_t* views_dev, size_t n_planes_
                       flags_dev, stream, nullptr);
 }
 
-int sd_viewnet_forward_timed(sd_viewnet* m, const uint8_t* views_dev, size_t n_planes_total, int nb_views, int H, int W,
-                             const int32_t* sample_table_dev, size_t n_samples, int D, const float* scalars_dev, float* logits_dev,
-                             void* workspace_dev, size_t ws_bytes, int32_t* flags_dev, void* stream, float* ms_out) {
-    if (!m || !ms_out) return fail("sd_viewnet_forward_timed: null argument");
+static int vn_forward_timed(sd_viewnet* m, const uint8_t* views_dev, size_t n_planes_total, int nb_views, int H, int W,
+                            const int32_t* sample_table_dev, size_t n_samples, int D, const float* scalars_dev, float* logits_dev,
+                            void* workspace_dev, size_t ws_bytes, int32_t* flags_dev, void* stream, float* ms_out, bool tiled_head) {
+    const std::string who = tiled_head ? "sd_viewnet_embed_timed" : "sd_viewnet_forward_timed";
+    if (!m || !ms_out) return fail(who + ": null argument");
     const size_t n = m->plan.layers.size() + 2;
     std::vector<hipEvent_t> ev(n, nullptr);
     int rc = SD_OK;
     for (size_t i = 0; i < n && rc == SD_OK; ++i)
-        if (hipEventCreate(&ev[i]) != hipSuccess) rc = fail("sd_viewnet_forward_timed: event creation failed", SD_ERR_HIP);
+        if (hipEventCreate(&ev[i]) != hipSuccess) rc = fail(who + ": event creation failed", SD_ERR_HIP);
     if (rc == SD_OK)
         rc = vn_forward(m, views_dev, n_planes_total, nb_views, H, W, sample_table_dev, n_samples, D, scalars_dev, logits_dev, workspace_dev, ws_bytes,
-                        flags_dev, stream, ev.data());
-    if (rc == SD_OK && hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)) != hipSuccess) rc = fail("sd_viewnet_forward_timed: synchronise failed", SD_ERR_HIP);
+                        flags_dev, stream, ev.data(), tiled_head);
+    if (rc == SD_OK && hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)) != hipSuccess) rc = fail(who + ": synchronise failed", SD_ERR_HIP);
     for (size_t i = 0; i + 1 < n && rc == SD_OK; ++i)
-        if (hipEventElapsedTime(&ms_out[i], ev[i], ev[i + 1]) != hipSuccess) rc = fail("sd_viewnet_forward_timed: elapsed time failed", SD_ERR_HIP);
+        if (hipEventElapsedTime(&ms_out[i], ev[i], ev[i + 1]) != hipSuccess) rc = fail(who + ": elapsed time failed", SD_ERR_HIP);
     for (hipEvent_t e : ev)
         if (e) (void)hipEventDestroy(e);
     return rc;
 }
+
+int sd_viewnet_forward_timed(sd_viewnet* m, const uint8_t* views_dev, size_t n_planes_total, int nb_views, int H, int W,
+                             const int32_t* sample_table_dev, size_t n_samples, int D, const float* scalars_dev, float* logits_dev,
+                             void* workspace_dev, size_t ws_bytes, int32_t* flags_dev, void* stream, float* ms_out) {
+    return vn_forward_timed(m, views_dev, n_planes_total, nb_views, H, W, sample_table_dev, n_samples, D, scalars_dev, logits_dev, workspace_dev,
+                            ws_bytes, flags_dev, stream, ms_out, false);
+}
+
+int sd_viewnet_embed(sd_viewnet* m, const uint8_t* views_dev, size_t n_planes_total, int nb_views, int H, int W, const int32_t* sample_table_dev,
+                     size_t n_samples, int D, const float* scalars_dev, float* logits_dev, void* workspace_dev, size_t ws_bytes,
+                     int32_t* flags_dev, void* stream) {
+    return vn_forward(m, views_dev, n_planes_total, nb_views, H, W, sample_table_dev, n_samples, D, scalars_dev, logits_dev, workspace_dev, ws_bytes,
+                      flags_dev, stream, nullptr, true);
+}
+
+int sd_viewnet_embed_timed(sd_viewnet* m, const uint8_t* views_dev, size_t n_planes_total, int nb_views, int H, int W,
+                           const int32_t* sample_table_dev, size_t n_samples, int D, const float* scalars_dev, float* logits_dev,
+                           void* workspace_dev, size_t ws_bytes, int32_t* flags_dev, void* stream, float* ms_out) {
+    return vn_forward_timed(m, views_dev, n_planes_total, nb_views, H, W, sample_table_dev, n_samples, D, scalars_dev, logits_dev, workspace_dev,
+                            ws_bytes, flags_dev, stream, ms_out, true);
+}
+
+int sd_viewnet_embed_tile_samples(sd_viewnet* m) { return m ? head_tile_samples(m->plan) : 0; }
 
 int sd_viewnet_overflow(sd_viewnet* m, const int32_t* flags_dev, void* stream, int32_t* flags_out) {
     if (!m || !flags_dev || !flags_out) return fail("sd_viewnet_overflow: null argument");

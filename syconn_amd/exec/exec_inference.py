@@ -88,6 +88,20 @@ def run_celltype_prediction(cells, model=None, views=None, ids=None, nb_views_mo
     return predict_celltypes_table(cells, model, views=views, nb_views_model=nb, use_syntype=syn, bs=bs, ids=ids, **vote_kw)
 
 
+def run_morphology_embedding(cells, model=None, views=None, locations=None, ids=None, bs=None):
+    """exec/exec_inference.py:29-66 as a table form: the local morphology embeddings of `cells` (objects with ``skeleton``,
+    ``scaling``, and rendered views in ``view_dict['tmp_views']`` with their rendering locations, or `views` and `locations` per cell)
+    with one pass over the representation network and one nearest-location call -> ``MorphologyTable``.  The reference spreads the
+    cells over batch jobs that each call ``predict_views_embedding``; the dataset and job layers and the point-model branch
+    (``infere_cell_morphology_ssd``) are not built.  `model` defaults to ``get_tripletnet_model_e3()``."""
+    from ..handler.prediction import get_tripletnet_model_e3
+    from ..reps.super_segmentation_helper import embed_cells_table
+    if global_params.config['use_point_models']:
+        raise NotImplementedError('run_morphology_embedding: the point models are not built')
+    model = get_tripletnet_model_e3() if model is None else model
+    return embed_cells_table(cells, model, views=views, locations=locations, bs=bs, ids=ids)
+
+
 def run_semsegaxoness_prediction(cells, model=None, view_props=None, map_properties=None, pred_key=None, max_dist=None, bs: int = 5, device=None):
     """exec/exec_inference.py:147-186 over cells in memory, each handled as ``semsegaxoness_predictor`` does
     (reps/super_segmentation_object.py:3468-3494): ``semseg_of_sso_nocache`` with ``config['compartments']['view_properties_semsegax']``

@@ -236,6 +236,11 @@ class DynConfig:
         return self.model_dir + '/celltype_e3/model.pts'
 
     @property
+    def mpath_tnet(self) -> str:
+        """config.py:485-492: the encoder of local cell morphology trained with a triplet loss (tCMN)."""
+        return self.model_dir + '/tCMN/model.pts'
+
+    @property
     def mpath_spiness(self) -> str:
         """config.py:537-544: the 2D semantic-segmentation model of spine head, neck, shaft and other."""
         return self.model_dir + '/spiness/model.pts'

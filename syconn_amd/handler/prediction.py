@@ -792,6 +792,8 @@ class ViewModel:
     function, so "proba" are logits there too.  `weights`: a state dict, a module, or the path of a ``torch.jit`` file.  The views are
     uint8 (n_samples, C, D, H, W), a ``ViewSamples``, or float32 that ``views_to_uint8`` takes.  Deviations: DESIGN.md."""
 
+    _entry = 'sd_viewnet_forward'      # the C entry of a launch set (EmbeddingModel: the one with the sample-tiled head)
+
     def __init__(self, spec, weights, act_dtype: str = 'f16', bs: int = 40, device=None):
         from .. import _dev as dv
         if act_dtype not in ('f16', 'bf16'):
@@ -851,6 +853,10 @@ class ViewModel:
         return ViewSamples(v.to(self.dev).contiguous(), t.to(self.dev).contiguous())
 
     def predict_proba(self, inp, bs: Optional[int] = None) -> np.ndarray:
+        return self._forward(inp, bs).cpu().numpy()
+
+    def _forward(self, inp, bs: Optional[int] = None) -> torch.Tensor:
+        """``predict_proba`` with the logits left on the device."""
         from .. import _dev as dv
         views, scal = inp if isinstance(inp, (tuple, list)) else (inp, None)
         spec = self.spec
@@ -877,7 +883,7 @@ class ViewModel:
             flags = torch.zeros((-(-n // nb), 2), dtype=torch.int32, device=self.dev)
             for i, b in enumerate(range(0, n, nb)):
                 e = min(b + nb, n)
-                dv.call('sd_viewnet_forward', self.dev, self._h, sm.views, n_loc * nb_views, nb_views, H, W, sm.table[b:e], e - b, D,
+                dv.call(self._entry, self.dev, self._h, sm.views, n_loc * nb_views, nb_views, H, W, sm.table[b:e], e - b, D,
                         scal[b:e] if spec.n_scalar else None, logits[b:e], ws, ws.numel(), flags[i])
             fl = flags.cpu().numpy()
         self._last = (ws, logits[b:e], e - b, D, H, W)
@@ -886,7 +892,7 @@ class ViewModel:
         if fl[:, 0].any():
             raise L.ActivationOverflowError("fp16 activation storage overflowed in the view network: its logits are invalid; use "
                                             "act_dtype='bf16'")
-        return logits.cpu().numpy()
+        return logits
 
     def read_buffer(self, index: int) -> np.ndarray:
         """Debug: after ``predict_proba``, the stored output of layer `index` of the LAST launch set as float32 (planes, Ho, Wo, cout), or
@@ -909,6 +915,76 @@ def get_celltype_model_e3(act_dtype: str = 'f16', n_classes: int = 7, n_scalar: 
     """prediction.py:985-1000: ``torch.jit.load(mpath_celltype_e3)`` -> state dict -> the view network (bs=40 as there)."""
     from ..cnn.viewnet_spec import CELLTYPE_CMN
     return ViewModel(CELLTYPE_CMN(n_classes, n_scalar), global_params.config.mpath_celltype_e3, act_dtype=act_dtype, bs=40)
+
+
+# -- morphology embeddings from multi-views (the triplet network) ------------------------------------------------------------------------
+def views2tripletinput(views):
+    """prediction.py:1189-1194: (n, C, nb_views, H, W) -> float32 (n, C, 3, H, W), view 0 followed by two planes of ones."""
+    first = np.asarray(views)[:, :, :1]
+    ones = np.ones_like(first)
+    return np.concatenate((first, ones, ones), axis=2).astype(np.float32)
+
+
+class EmbeddingModel(ViewModel):
+    """``InferenceModel`` around the ``TripletNet`` of cnn/cnn_atn.py:90-116 as reps/super_segmentation_helper.py:1803-1809 and
+    reps/super_segmentation_object.py:3063-3069 call it, for the representation network given as a spec (``TNET_REP``): only ``z_0 =
+    rep_net(x)`` is computed.  ``predict_proba(inp, bs=None)`` takes
+
+    * uint8 views (n, C, H, W) -- what the module takes --, or float32 ones that ``views_to_uint8`` accepts,
+    * the renderer's (n_loc, C, nb_views, H, W) tensor, host or device: view 0 of every location is read in place,
+    * a ``ViewSamples`` whose table is (n, 1),
+    * the reference's triple ``(x, y, z)``, of which `x` is used,
+
+    and returns the float32 latents (n, z_dim); for the triple ``(None, None, latent, None, None)``, so that the reference's
+    ``_, _, latent, _, _ = model.predict_proba(inp)`` works: the two distances and the latents of `y` and `z`, which the callers throw
+    away, are not computed.  A launch set is `bs` planes; the default of 800 is the 40 x 20 planes of a cell type launch set and
+    rests on no measurement.  The head runs sample-tiled (``sd_viewnet_embed``), with the bits of ``ViewModel``'s head."""
+    _entry = 'sd_viewnet_embed'
+
+    def __init__(self, spec, weights, act_dtype: str = 'f16', bs: int = 800, device=None):
+        super().__init__(spec, weights, act_dtype=act_dtype, bs=bs, device=device)
+
+    @property
+    def tile_samples(self) -> int:
+        """Samples per workgroup of the head kernel."""
+        return L.load().sd_viewnet_embed_tile_samples(self._h)
+
+    def _view0(self, views) -> 'ViewSamples':
+        if isinstance(views, ViewSamples):
+            t = views.table
+            if getattr(t, 'ndim', 0) != 2 or t.shape[1] != 1:
+                raise ValueError('the sample table of an embedding call must be (n, 1): one view per sample')
+            return views
+        if isinstance(views, np.ndarray) and views.dtype == np.float32:
+            views = views_to_uint8(views)
+        nd = getattr(views, 'ndim', 0)
+        if nd == 4:
+            return ViewSamples(views[:, :, None], np.arange(views.shape[0], dtype=np.int32).reshape(-1, 1))
+        if nd == 5:
+            return ViewSamples(views, (np.arange(views.shape[0], dtype=np.int32) * np.int32(views.shape[2])).reshape(-1, 1))
+        raise ValueError('views must be (n, C, H, W) or (n_loc, C, nb_views, H, W)')
+
+    def predict_proba(self, inp, bs: Optional[int] = None):
+        triple = isinstance(inp, (tuple, list))
+        if triple and len(inp) != 3:
+            raise ValueError('a tuple input must be the triple (x, y, z) of the TripletNet')
+        latent = self.predict_device(inp[0] if triple else inp, bs).cpu().numpy()
+        return (None, None, latent, None, None) if triple else latent
+
+    def predict_device(self, views, bs: Optional[int] = None) -> torch.Tensor:
+        """The latents of `views` (any of the forms above but the triple) as a float32 device tensor (n, z_dim)."""
+        return self._forward(self._view0(views), bs)
+
+    def forward_samples(self, inp, bs: Optional[int] = None) -> np.ndarray:
+        """``ViewModel.predict_proba`` -- any sample table, scalars -- through the tiled head."""
+        return self._forward(inp, bs).cpu().numpy()
+
+
+def get_tripletnet_model_e3(act_dtype: str = 'f16'):
+    """prediction.py:1033-1044: ``torch.jit.load(mpath_tnet)`` -> state dict -> the representation network of cnn/cnn_atn.py (25 values)
+    for the 128 x 256 window of the config.  A file whose first Linear takes another size is refused with both shapes in the message."""
+    from ..cnn.viewnet_spec import TNET_REP
+    return EmbeddingModel(TNET_REP(), global_params.config.mpath_tnet, act_dtype=act_dtype)
 
 
 # -- 2D semantic segmentation of multi-views (compartments) -------------------------------------------------------------------------

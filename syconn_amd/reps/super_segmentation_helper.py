@@ -582,6 +582,165 @@ def predict_celltypes_table(cells, model, views=None, nb_views_model: int = 20, 
                          np.concatenate([v[1] for v in votes]), np.array(begin, np.int64))
 
 
+# -- morphology embeddings from multi-views (reps/super_segmentation_helper.py:1758-1817) --------------------------------------------
+def _cell_locations(sso) -> np.ndarray:
+    """``np.concatenate(sso.sample_locations())`` (:1814), or the ``_sample_locations`` a rendering call left on a cell without the
+    method: (n_loc, 3), in the order of the views."""
+    if hasattr(sso, 'sample_locations'):
+        locs = sso.sample_locations()
+    else:
+        locs = getattr(sso, '_sample_locations', None)
+        if locs is None:
+            raise ValueError('no rendering locations: the cell has neither sample_locations() nor _sample_locations')
+    locs = np.concatenate(locs) if isinstance(locs, (list, tuple)) or np.asarray(locs).ndim == 3 else np.asarray(locs)
+    return locs.reshape(-1, 3)
+
+
+def _node_queries(sso) -> np.ndarray:
+    """``sso.skeleton['nodes'] * sso.scaling`` (:1815) as the float64 the tree makes of it."""
+    if hasattr(sso, 'load_skeleton'):
+        sso.load_skeleton()
+    return np.asarray(np.asarray(sso.skeleton['nodes']).reshape(-1, 3) * np.asarray(sso.scaling), dtype=np.float64)
+
+
+def nearest_locations(locations, loc_begin, q_cell, q_xyz, ids=None, device=None) -> np.ndarray:
+    """The ``cKDTree(locations).query(nodes * scaling, k=1)`` of :1814-1815 for many cells in one ``sd_syn_props_knn`` call: for every
+    query the row, inside its cell's ``locations[loc_begin[c]:loc_begin[c + 1]]``, of the nearest location; the smaller row on equal
+    float64 distances (the entry's rule, as in ``attr_for_coords``).  int64.  ValueError for a cell with queries and no location."""
+    from ..extraction.cs_processing_steps import segmented_knn
+    loc_begin = np.asarray(loc_begin, np.int64).reshape(-1)
+    q_cell = np.asarray(q_cell, np.int64).reshape(-1)
+    if len(q_cell) == 0:
+        return np.zeros(0, np.int64)
+    empty = np.diff(loc_begin)[q_cell] == 0
+    if empty.any():
+        c = int(q_cell[np.flatnonzero(empty)[0]])
+        raise ValueError(f'cell {c if ids is None else ids[c]} has skeleton nodes but no rendering location')
+    rows = segmented_knn(locations, loc_begin, None, q_cell, q_xyz, 1, device)
+    return rows.astype(np.int64) - loc_begin[q_cell]
+
+
+def view_embedding_of_sso_nocache(sso, model, ws, nb_views, comp_window, pred_key_appendix: str = '', verbose: bool = False,
+                                  overwrite: bool = True, add_cellobjects=True, device=None):
+    """:1758-1817: render the views at ``generate_rendering_locs(verts, comp_window / 3)`` -- they stay on the device, and in
+    ``sso.view_dict['tmp_views' + pred_key_appendix]``, which is reused unless `overwrite` --, embed view 0 of every location with
+    `model` (a ``handler.prediction.EmbeddingModel``; the uint8 views go in, the normalisation is the first layer's), give every
+    skeleton node the latent of its nearest rendering location and store that as ``sso.skeleton['latent_morph' + pred_key_appendix]``,
+    float32 (n_nodes, z_dim); also returned.  `sso`: anything with ``.mesh``, ``.load_mesh(name)``, ``.view_caching``,
+    ``.view_dict``, ``.skeleton`` (``'nodes'`` in voxels) and ``.scaling``; ``load_skeleton`` / ``save_skeleton`` are called if there."""
+    from ..handler.multiviews import generate_rendering_locs
+    from ..proc.rendering import render_sso_coords
+    pred_key = 'latent_morph' + pred_key_appendix
+    assert sso.view_caching, "'view_caching' of {} has to be True in order to run 'view_embedding_of_sso_nocache'.".format(sso)
+    tmp_view_key = 'tmp_views' + pred_key_appendix
+    if tmp_view_key not in sso.view_dict or overwrite:
+        verts = np.asarray(sso.mesh[1]).reshape(-1, 3)
+        rendering_locs = generate_rendering_locs(verts, comp_window / 3, device=device)
+        sso._sample_locations = rendering_locs[None, ]
+        views = render_sso_coords(sso, rendering_locs, ws=ws, comp_window=comp_window, nb_views=nb_views, verbose=verbose,
+                                  add_cellobjects=add_cellobjects, return_rot_mat=False, device=device, return_device=True)
+        sso.view_dict[tmp_view_key] = views
+        locs = rendering_locs
+    else:
+        views = sso.view_dict[tmp_view_key]
+        locs = _cell_locations(sso)
+    return _embed_to_skeleton(sso, model, views, locs, pred_key, None)
+
+
+def _embed_to_skeleton(sso, model, views, locs, pred_key, view_ixs_key):
+    queries = _node_queries(sso)
+    if len(locs) != len(views):
+        raise ValueError(f'{len(views)} view locations, {len(locs)} rendering locations')
+    if len(queries) and not len(views):
+        raise ValueError('the cell has skeleton nodes but no rendering location')
+    if view_ixs_key is not None and view_ixs_key in sso.skeleton:
+        ixs = np.asarray(sso.skeleton[view_ixs_key], np.int64).reshape(-1)
+        if len(ixs) != len(queries):
+            raise IndexError(f'skeleton[{view_ixs_key!r}] holds {len(ixs)} entries for {len(queries)} nodes')
+        if len(ixs) and (ixs.min() < 0 or ixs.max() >= len(views)):      # stale indices: the reference's latent[ixs] raises too
+            raise IndexError(f'skeleton[{view_ixs_key!r}] names a location outside [0, {len(views)})')
+    else:
+        ixs = nearest_locations(locs, [0, len(locs)], np.zeros(len(queries), np.int64), queries, device=model.dev)
+        if view_ixs_key is not None:
+            sso.skeleton[view_ixs_key] = ixs
+    if len(views):
+        latent = model.predict_device(views)
+        node_latent = latent[D.up(ixs, model.dev)].cpu().numpy()
+    else:
+        node_latent = np.zeros((0, model.spec.n_classes), np.float32)
+    sso.skeleton[pred_key] = node_latent
+    if hasattr(sso, 'save_skeleton'):
+        sso.save_skeleton()
+    return node_latent
+
+
+class MorphologyTable:
+    """Morphology embeddings of many cells: ``ids``; ``latent`` float32 (n_loc_total, z), the locations of cell k at
+    ``loc_begin[k]:loc_begin[k + 1]``; ``node_latent`` float32 (n_nodes_total, z) with ``node_begin`` likewise -- what goes into
+    ``CellTable(node_attrs={'latent_morph': ...})`` --; ``view_ixs`` int64 (n_nodes_total): the nearest location of every node as a row
+    inside its own cell, so that ``node_latent = latent[loc_begin[cell] + view_ixs]``."""
+
+    def __init__(self, ids, latent, loc_begin, node_latent, node_begin, view_ixs):
+        self.ids, self.latent, self.loc_begin = np.asarray(ids), latent, np.asarray(loc_begin, np.int64)
+        self.node_latent, self.node_begin, self.view_ixs = node_latent, np.asarray(node_begin, np.int64), np.asarray(view_ixs, np.int64)
+        n = len(self.ids)
+        if len(self.loc_begin) != n + 1 or len(self.node_begin) != n + 1:
+            raise ValueError('MorphologyTable: loc_begin and node_begin hold one offset per cell and one more')
+        mono = self.loc_begin[0] == 0 and self.node_begin[0] == 0 and (np.diff(self.loc_begin) >= 0).all() and (np.diff(self.node_begin) >= 0).all()
+        if not mono or self.loc_begin[-1] != len(latent) or self.node_begin[-1] != len(node_latent) or len(self.view_ixs) != len(node_latent):
+            raise ValueError('MorphologyTable: offsets do not match the arrays')
+
+    def __len__(self):
+        return len(self.ids)
+
+    def latent_of(self, k: int) -> np.ndarray:
+        return self.latent[self.loc_begin[k]:self.loc_begin[k + 1]]
+
+    def node_latent_of(self, k: int) -> np.ndarray:
+        return self.node_latent[self.node_begin[k]:self.node_begin[k + 1]]
+
+    def view_ixs_of(self, k: int) -> np.ndarray:
+        return self.view_ixs[self.node_begin[k]:self.node_begin[k + 1]]
+
+
+def embed_cells_table(cells, model, views=None, locations=None, bs=None, ids=None) -> MorphologyTable:
+    """``view_embedding_of_sso_nocache``'s embedding and node mapping for many cells at once: the locations of all cells go through the
+    network in launch sets of `bs` planes, whatever cell they belong to, and one segmented nearest-neighbour call covers all nodes.
+    `views[k]` (default ``cells[k].view_dict['tmp_views']``): the views of cell k, host or device, (n_loc_k, C, nb_views, H, W);
+    `locations[k]` (default: the cell's rendering locations) (n_loc_k, 3) in their order.  Equals one single call per cell bit for
+    bit: a sample's latent does not depend on its launch set or tile, and the node mapping is the same entry's."""
+    cells = list(cells)
+    if not cells:
+        raise ValueError('embed_cells_table: no cells')
+    views = [c.view_dict['tmp_views'] for c in cells] if views is None else list(views)
+    locations = [_cell_locations(c) for c in cells] if locations is None else [np.asarray(l).reshape(-1, 3) for l in locations]
+    if len(views) != len(cells) or len(locations) != len(cells):
+        raise ValueError('embed_cells_table: one view array and one location array per cell')
+    if len({tuple(v.shape[1:]) for v in views}) != 1:
+        raise ValueError('embed_cells_table: the view arrays differ in channels, views per location or window')
+    for k, (v, l) in enumerate(zip(views, locations)):
+        if len(v) != len(l):
+            raise ValueError(f'embed_cells_table: cell {k} has {len(v)} view locations and {len(l)} rendering locations')
+    ids = np.arange(len(cells)) if ids is None else np.asarray(ids)
+    dev = model.dev
+    queries = [_node_queries(c) for c in cells]
+    loc_begin = np.concatenate(([0], np.cumsum([len(l) for l in locations]))).astype(np.int64)
+    node_begin = np.concatenate(([0], np.cumsum([len(q) for q in queries]))).astype(np.int64)
+    z = model.spec.n_classes
+    if loc_begin[-1] == 0:
+        if node_begin[-1]:
+            raise ValueError('embed_cells_table: a cell has skeleton nodes but no rendering location')
+        return MorphologyTable(ids, np.zeros((0, z), np.float32), loc_begin, np.zeros((0, z), np.float32), node_begin, np.zeros(0, np.int64))
+    loc_dtype = np.float32 if all(l.dtype == np.float32 for l in locations) else np.float64
+    view_ixs = nearest_locations(np.concatenate(locations).astype(loc_dtype), loc_begin, np.repeat(np.arange(len(cells)), np.diff(node_begin)),
+                                 np.concatenate(queries), ids=ids, device=dev)
+    tens = [v.to(dev) if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v)).to(dev) for v in views if len(v)]
+    latent = model.predict_device(tens[0] if len(tens) == 1 else torch.cat(tens, 0), bs)
+    rows = view_ixs + np.repeat(loc_begin[:-1], np.diff(node_begin))
+    node_latent = latent[D.up(rows, dev)].cpu().numpy()
+    return MorphologyTable(ids, latent.cpu().numpy(), loc_begin, node_latent, node_begin, view_ixs)
+
+
 # -- compartment labels from multi-views (reps/super_segmentation_helper.py:1353-1392, :1820-1905) ----------------------------------
 def predict_views_semseg(views, model, batch_size=10, verbose=False):
     """Drop-in of ``predict_views_semseg`` (:1353-1392): `views` uint8 (N_LOCS, N_CH, N_VIEWS, H, W), host array or device tensor ->

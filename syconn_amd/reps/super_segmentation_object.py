@@ -93,20 +93,43 @@ def predict_celltype_multiview(sso, model, pred_key_appendix: str = '', model_tn
                                overwrite: bool = True, model_props=None, verbose: bool = False, save_to_attr_dict: bool = True, **kw):
     """reps/super_segmentation_object.py:3125-3165: ``celltype_cnn_e3``, ``_probas`` and ``_certainty`` of `sso` from `model` (a
     ``handler.prediction.ViewModel``), from the stored views (``sso.load_views()``, or ``views=`` in `kw`) or, with `onthefly_views`,
-    from views rendered with the view properties of the config (updated by `view_props`).  The morphology embedding (`model_tnet`, the
-    triplet net) is not built."""
+    from views rendered with the view properties of the config (updated by `view_props`).  With `model_tnet` (a
+    ``handler.prediction.EmbeddingModel``) the morphology embedding follows, as there (:3160-3165): ``view_embedding_of_sso_nocache``
+    on the view properties without ``use_syntype``, with ``overwrite=True``.  Any other `model_tnet` object -- an arbitrary torch
+    module is not built -- is a NotImplementedError before anything runs."""
     from .. import global_params
+    from ..handler.prediction import EmbeddingModel
     from . import super_segmentation_helper as ssh
-    if model_tnet is not None:
-        raise NotImplementedError('predict_celltype_multiview: the morphology embedding (view_embedding_of_sso_nocache) is not built')
+    if model_tnet is not None and not isinstance(model_tnet, EmbeddingModel):
+        raise NotImplementedError('predict_celltype_multiview: the morphology embedding (view_embedding_of_sso_nocache) is built for '
+                                  'handler.prediction.EmbeddingModel only, not for an arbitrary module')
     model_props = dict(model_props or {})
     props = dict(global_params.config['views']['view_properties'])
     props.update(view_props or {})
     if not onthefly_views:
-        return ssh.predict_sso_celltype(sso, model, pred_key_appendix=pred_key_appendix, save_to_attr_dict=save_to_attr_dict,
-                                        overwrite=overwrite, **model_props, **kw)
-    return ssh.celltype_of_sso_nocache(sso, model, pred_key_appendix=pred_key_appendix, save_to_attr_dict=save_to_attr_dict,
-                                       overwrite=overwrite, verbose=verbose, **props, **model_props, **kw)
+        out = ssh.predict_sso_celltype(sso, model, pred_key_appendix=pred_key_appendix, save_to_attr_dict=save_to_attr_dict,
+                                       overwrite=overwrite, **model_props, **kw)
+    else:
+        out = ssh.celltype_of_sso_nocache(sso, model, pred_key_appendix=pred_key_appendix, save_to_attr_dict=save_to_attr_dict,
+                                          overwrite=overwrite, verbose=verbose, **props, **model_props, **kw)
+    if model_tnet is not None:
+        emb_props = {k: v for k, v in props.items() if k != 'use_syntype'}
+        ssh.view_embedding_of_sso_nocache(sso, model_tnet, pred_key_appendix=pred_key_appendix, overwrite=True, device=kw.get('device'), **emb_props)
+    return out
+
+
+def predict_views_embedding(sso, model, pred_key_appendix: str = '', view_key=None):
+    """reps/super_segmentation_object.py:3032-3079, the cached-views form of ``view_embedding_of_sso_nocache``: the views of
+    ``sso.load_views(view_key=view_key)`` (n_loc, C, nb_views, H, W), uint8, host or device, through `model` (a
+    ``handler.prediction.EmbeddingModel``), and every skeleton node gets the latent of the rendering location
+    ``sso.skeleton['view_ixs']``, which is computed from ``sso.sample_locations()`` and written when absent, as there.  Stores and
+    returns ``sso.skeleton['latent_morph' + pred_key_appendix]``, float32 (n_nodes, z_dim)."""
+    from . import super_segmentation_helper as ssh
+    views = sso.load_views(view_key=view_key)
+    if hasattr(sso, 'load_skeleton'):
+        sso.load_skeleton()
+    locs = ssh._cell_locations(sso) if 'view_ixs' not in sso.skeleton else np.zeros((len(views), 3), np.float32)
+    return ssh._embed_to_skeleton(sso, model, views, locs, 'latent_morph' + pred_key_appendix, 'view_ixs')
 
 
 def certainty_celltype(sso, pred_key=None) -> float:
