@@ -1114,6 +1114,29 @@ int sd_fcn_read_buffer(sd_fcn* m, int index, const void* workspace_dev, const fl
                        int32_t* dims_out, void* stream);
 int sd_fcn_num_ops(sd_fcn* m);
 
+/* ---- glia probabilities from supervoxel views: the steps around the view network (csrc/sd_glia_views.hip) -------------------------
+ *   sd_glia_view_probas        the probabilities behind /root/reference/syconn/handler/prediction.py:978-982 (get_glia_model_e3 ->
+ *                              InferenceModel.predict_proba over cnn/cnn_gliaviews_e3.py:27 get_model), which reps/segmentation.py:799-814
+ *                              thresholds: logits_dev float32[n][2] -> probas_dev float32[n][2] = softmax of every row, taken in float64
+ *                              from the float32 logits with the row maximum subtracted and rounded once to float32.  Both 8-byte aligned;
+ *                              n = 0 is legal.  flag_dev int32[1], zeroed by the call: != 0 a logit was NaN or infinite (that row's
+ *                              result is meaningless).
+ *   sd_views_center_component  /root/reference/syconn/proc/image.py:125-144 single_conn_comp_img, as proc/sd_proc.py:1404-1411
+ *                              (predict_views, single_cc_only) applies it plane by plane, for a batch: in_dev / out_dev
+ *                              uint8[n_planes][H][W], equal or disjoint.  Per plane: foreground = pixel != background; the pixels of the
+ *                              4-connected foreground component (scipy.ndimage.label's default structure) that holds the centre pixel
+ *                              (H / 2, W / 2) keep their value, every other pixel becomes background; a background centre empties the
+ *                              plane (the reference's labeled == 0 branch).  One workgroup per plane holds two bit masks of the plane in
+ *                              LDS: 8 H ceil(W / 32) + 16 bytes, which is what the launch requests; a plane for which that exceeds
+ *                              SD_GLIA_VIEWS_LDS_BYTES (the LDS of a compute unit; 512 x 1024 fits) is SD_ERR_INVALID before anything
+ *                              is launched.  n_planes = 0 is legal.
+ * Asynchronous on the stream.  One grid stride of either kernel is SD_GLIA_VIEWS_GRID blocks (256 samples, or one plane, per block);
+ * the constant rests on no measurement. */
+#define SD_GLIA_VIEWS_GRID 1024
+#define SD_GLIA_VIEWS_LDS_BYTES 163840
+int sd_glia_view_probas(const float* logits_dev, size_t n, float* probas_dev, int32_t* flag_dev, void* stream);
+int sd_views_center_component(const uint8_t* in_dev, size_t n_planes, int H, int W, int background, uint8_t* out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

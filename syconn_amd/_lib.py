@@ -23,6 +23,7 @@ SD_GLIA_GRID = 1024
 SD_VIEWS_GRID, SD_VIEWS_RASTER_GRID, SD_VIEWS_MAX_VIEWS, SD_VIEWS_TILE_PX = 1024, 4096, 16, 32768
 SD_LOCATIONS_GRID, SD_LOCATIONS_WAVE_GRID, SD_LOCATIONS_MAX_CELLS = 1024, 4096, 1 << 21
 SD_VIEWNET_GRID, SD_VIEWNET_HEAD_GRID, SD_VIEWNET_HEAD_TILE_GRID = 2048, 32, 1024
+SD_GLIA_VIEWS_GRID, SD_GLIA_VIEWS_LDS_BYTES = 1024, 163840
 
 LIB_NAME = 'libsyconn_dense_hip.so'
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), os.environ.get('SD_LIB_NAME', LIB_NAME))
@@ -55,7 +56,8 @@ EXPORTS = ['sd_init', 'sd_device_count', 'sd_model_create', 'sd_model_destroy', 
            'sd_locations_surface', 'sd_viewnet_create', 'sd_viewnet_destroy', 'sd_viewnet_workspace_bytes', 'sd_viewnet_forward', 'sd_viewnet_forward_timed',
            'sd_viewnet_overflow', 'sd_viewnet_read_buffer', 'sd_viewnet_num_ops', 'sd_viewnet_embed', 'sd_viewnet_embed_timed',
            'sd_viewnet_embed_tile_samples', 'sd_fcn_create', 'sd_fcn_destroy', 'sd_fcn_workspace_bytes',
-           'sd_fcn_forward', 'sd_fcn_forward_timed', 'sd_fcn_overflow', 'sd_fcn_read_buffer', 'sd_fcn_num_ops']
+           'sd_fcn_forward', 'sd_fcn_forward_timed', 'sd_fcn_overflow', 'sd_fcn_read_buffer', 'sd_fcn_num_ops',
+           'sd_glia_view_probas', 'sd_views_center_component']
 
 
 class OpDesc(C.Structure):
@@ -295,6 +297,9 @@ def load():
     lib.sd_fcn_overflow.argtypes = [vp, vp, vp, i32p]; lib.sd_fcn_overflow.restype = i32
     lib.sd_fcn_read_buffer.argtypes = [vp, i32, vp, vp, sz, i32, i32, f32p, i32p, vp]; lib.sd_fcn_read_buffer.restype = i32
     lib.sd_fcn_num_ops.argtypes = [vp]; lib.sd_fcn_num_ops.restype = i32
+    # handler/prediction.py:978-982 (get_glia_model_e3: the probabilities), proc/image.py:125-144 (single_conn_comp_img)
+    lib.sd_glia_view_probas.argtypes = [vp, sz, vp, vp, vp]; lib.sd_glia_view_probas.restype = i32
+    lib.sd_views_center_component.argtypes = [vp, sz, i32, i32, i32, vp, vp]; lib.sd_views_center_component.restype = i32
     _lib = lib
     return lib
 

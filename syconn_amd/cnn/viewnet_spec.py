@@ -136,6 +136,18 @@ def VIEWNET_SMALL(n_classes: int = 2, n_scalar: int = 0, act: str = 'relu', in_c
                        (50, 30), n_classes, n_scalar, act, name='viewnet_small')
 
 
+def GLIA_CMN(n_classes: int = 2, act: str = 'relu') -> ViewNetSpec:
+    """The glia view model, ``StackedConv2Scalar(1, 2)`` of cnn_gliaviews_e3.py:27 (``get_model``) behind ``get_glia_model_e3``
+    (handler/prediction.py:978-982).  ``elektronn3.models.simple`` is not part of the reference tree.  Pinned by the tree: one input
+    channel (the raw views only: ``raw_only=True`` in ``predict_views_gliaSV``) and two classes (``StackedConv2Scalar(1, 2)``), 2 views
+    per sample (``nb_views: 2`` in cnn_gliaviews_e3.py), no scalars, ``naive_view_normalization_new`` as the normalisation.  Stated, not
+    pinned: the layer widths, which are the ``VIEWNET_SMALL`` stack, the commented family of cnn_celltype_cmn.py:60-95 -- 2 views of
+    128 x 256 flatten to 31 x 2 x 1 x 3 = 186 features, then 186 -> 50 -> 30 -> 2 --, and the softmax behind the logits
+    (``GliaViewModel``)."""
+    s = VIEWNET_SMALL(n_classes, 0, act, in_channels=1)
+    return ViewNetSpec(1, s.layers, 186, s.fc, n_classes, 0, act, name='glia_cmn')
+
+
 def TNET_REP(z_dim: int = 25, fc_in: int = 372, in_channels: int = 4) -> ViewNetSpec:
     """``RepresentationNetwork`` of cnn_atn.py:21-55 as ``get_model`` builds it (:111-116, ReLU; Dropout2d is the identity in
     inference): Conv2d 13 (5, pool) / 19 (5, pool) / 25 (4) / 25 (4, pool) / 30 (2, pool) / 30 (2, pool) / 31 (1), then

@@ -1,8 +1,11 @@
 """Astrocyte splitting between ``run_create_rag`` and ``run_create_neuron_ssd``: ``run_astrocyte_splitting`` of /root/reference/syconn/
 exec/exec_inference.py (:341-380) over the tables of ``exec_init``.  The reference reads the pruned graph from an edge-list file, splits
 cell by cell in batch jobs and writes the neuron graph to a file; here the pruned graph is the ``SvGraphComponents`` of
-``run_create_rag`` and the result's ``neuron_edges`` go straight into ``run_create_neuron_ssd(edges=...)``.  Not built: views, rendering
-and the glia model itself (``run_astrocyte_rendering`` / ``run_astrocyte_prediction``: the glia probabilities are an input), files."""
+``run_create_rag`` and the result's ``neuron_edges`` go straight into ``run_create_neuron_ssd(edges=...)``.  The glia probabilities come
+from ``run_astrocyte_prediction`` (the reference's ``run_astrocyte_rendering`` and ``run_astrocyte_prediction``, :290-338, in one: the
+views of every supervoxel are rendered, predicted and classified on the device and never stored), so that ``run_create_rag ->
+run_astrocyte_prediction -> run_astrocyte_splitting -> run_create_neuron_ssd`` runs without an outside input.  Not built: view
+storages, batch jobs, files, the point models."""
 import numpy as np
 
 from .. import global_params
@@ -70,6 +73,21 @@ def run_astrocyte_splitting(components, sv_props, mesh_bb=None, glia_probas=None
                                               sv_props.sizes, device)
     return AstrocyteSplitting(split, glia_splitting.collect_glia_sv(split, ids), glia_splitting.write_astrocyte_svgraph(split, scaling),
                               np.asarray(glia), proba)
+
+
+def run_astrocyte_prediction(cells, model=None, thresh=None, **kw):
+    """``run_astrocyte_rendering`` (exec/exec_render.py:206) and ``run_astrocyte_prediction`` (exec/exec_inference.py:290-338) in one:
+    views are never stored, so rendering is no step of its own.  `cells`: the connected components of the pruned supervoxel graph as
+    objects with ``.mesh`` and ``.svs``; -> the ``GliaTable`` of ``predict_glia_table`` (whose keyword arguments `kw` are), with the
+    views on the device from the rasteriser to the class.  ``table.glia_probas[:, 1]`` and ``table.view_begin`` go into
+    ``run_astrocyte_splitting``.  `model` defaults to ``get_glia_model_e3()``, `thresh` to ``config['glia']['glia_thresh']``.  The
+    reference spreads the cells over batch jobs and storages; neither layer is built, nor is the point-model path."""
+    from ..handler.prediction import get_glia_model_e3
+    from ..reps.super_segmentation_helper import predict_glia_table
+    if global_params.config['use_point_models']:
+        raise NotImplementedError('run_astrocyte_prediction: the point models are not built')
+    model = get_glia_model_e3() if model is None else model
+    return predict_glia_table(cells, model, thresh=thresh, **kw)
 
 
 def run_celltype_prediction(cells, model=None, views=None, ids=None, nb_views_model=None, use_syntype=None, bs: int = 40, **vote_kw):

@@ -231,6 +231,12 @@ class DynConfig:
         return self.model_dir + '/mivcsj/model.pt'
 
     @property
+    def mpath_glia_e3(self) -> str:
+        """config.py:594-600: the view network that tells glia from neuron supervoxels.  The reference names the model's folder; the
+        file in it is ``model.pts`` as for the other view networks."""
+        return self.model_dir + '/glia_e3/model.pts'
+
+    @property
     def mpath_celltype_e3(self) -> str:
         """config.py:565-570: the view network of the cell type step."""
         return self.model_dir + '/celltype_e3/model.pts'

@@ -987,6 +987,59 @@ def get_tripletnet_model_e3(act_dtype: str = 'f16'):
     return EmbeddingModel(TNET_REP(), global_params.config.mpath_tnet, act_dtype=act_dtype)
 
 
+# -- glia probabilities from supervoxel views ---------------------------------------------------------------------------------------------
+def glia_view_probas(logits: torch.Tensor) -> torch.Tensor:
+    """float32 device logits (n, 2) -> float32 device probabilities (n, 2): the softmax of every row in float64, rounded once
+    (``sd_glia_view_probas``).  A NaN or infinite logit is a ``ValueError``."""
+    from .. import _dev as dv
+    if not isinstance(logits, torch.Tensor) or not logits.is_cuda or logits.dtype != torch.float32 or logits.dim() != 2 or logits.shape[1] != 2:
+        raise ValueError('glia_view_probas: logits must be a float32 device tensor (n, 2)')
+    logits = logits.contiguous()
+    n, dev = int(logits.shape[0]), logits.device
+    probas = torch.empty((n, 2), dtype=torch.float32, device=dev)
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        dv.call('sd_glia_view_probas', dev, logits if n else None, n, probas if n else None, flag)
+        if int(flag.cpu()[0]):
+            raise ValueError('glia_view_probas: a logit is NaN or infinite')
+    return probas
+
+
+class GliaViewModel(ViewModel):
+    """``InferenceModel(mpath_glia_e3, normalize_func=naive_view_normalization_new)`` (prediction.py:978-982) for the glia view network
+    given as a spec (``GLIA_CMN``).  ``predict_proba(views, bs=None, apply_softmax=True)`` takes uint8 views (n, 1, 2, H, W), host or
+    device, float32 ones that ``views_to_uint8`` accepts, or a ``ViewSamples``, and returns float32 (n, 2): the probabilities of neuron
+    and glia.  The softmax is stated, not pinned (elektronn3 is not in the reference tree): the reference thresholds column 1 at
+    ``glia_thresh``, which only makes sense for a probability.  ``apply_softmax=False`` gives the logits, the bits of a plain
+    ``ViewModel`` run through the same head entry.  Every sample is two planes, so thousands of samples make one call: the head runs
+    sample-tiled (``sd_viewnet_embed``); a launch set is `bs` samples, and the default of 400 (the 800 planes of an embedding launch
+    set) rests on no measurement."""
+    _entry = 'sd_viewnet_embed'
+
+    def __init__(self, spec, weights, act_dtype: str = 'f16', bs: int = 400, device=None):
+        if spec.n_classes != 2 or spec.n_scalar != 0:
+            raise ValueError('GliaViewModel: the spec must have two classes and no scalars')
+        super().__init__(spec, weights, act_dtype=act_dtype, bs=bs, device=device)
+
+    def predict_device(self, views, bs: Optional[int] = None, apply_softmax: bool = True) -> torch.Tensor:
+        """``predict_proba`` with the result left on the device."""
+        if not isinstance(views, ViewSamples) and getattr(views, 'ndim', 0) == 5 and views.shape[0] == 0:
+            if views.shape[1] != self.spec.in_channels:
+                raise ValueError(f'views have {views.shape[1]} channels, the model takes {self.spec.in_channels}')
+            return torch.zeros((0, 2), dtype=torch.float32, device=self.dev)
+        logits = self._forward(views, bs)
+        return glia_view_probas(logits) if apply_softmax else logits
+
+    def predict_proba(self, views, bs: Optional[int] = None, apply_softmax: bool = True, verbose: bool = False) -> np.ndarray:
+        return self.predict_device(views, bs, apply_softmax).cpu().numpy()
+
+
+def get_glia_model_e3(act_dtype: str = 'f16'):
+    """prediction.py:978-982: the glia view network with the weights of ``config.mpath_glia_e3``."""
+    from ..cnn.viewnet_spec import GLIA_CMN
+    return GliaViewModel(GLIA_CMN(), global_params.config.mpath_glia_e3, act_dtype=act_dtype)
+
+
 # -- 2D semantic segmentation of multi-views (compartments) -------------------------------------------------------------------------
 def semseg_views_to_uint8(x: np.ndarray) -> np.ndarray:
     """float32 views that are exactly ``u.astype(np.float32) / 255.`` of uint8 renderings `u` (what ``predict_views_semseg`` hands to

@@ -399,3 +399,77 @@ def invert_mdc(mapping_dict):
         for cell_id, value in cells.items():
             out.setdefault(cell_id, {})[sub_id] = value
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# view predictions per supervoxel (proc/sd_proc.py:1345-1432)
+def _views_device(who, views, dev):
+    """The per-object view arrays (host uint8 or device tensors, (n_i, C, nb_views, H, W)) as ONE device tensor and the partition."""
+    import torch
+    tens = []
+    for k, v in enumerate(views):
+        t = torch.from_numpy(np.ascontiguousarray(v)) if isinstance(v, np.ndarray) else v
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 5:
+            raise ValueError(f'{who}: views[{k}] must be a uint8 array or tensor (n, C, nb_views, H, W)')
+        tens.append(t)
+    if not tens:
+        raise ValueError(f'{who}: no views')
+    if len({tuple(t.shape[1:]) for t in tens}) != 1:
+        raise ValueError(f'{who}: the view arrays differ in channels, views per location or window')
+    part_views = np.cumsum([0] + [len(t) for t in tens])
+    return torch.cat([t.to(dev) for t in tens], 0), part_views
+
+
+def predict_views(model, views, ch=None, pred_key=None, single_cc_only=False, verbose=False, return_proba=False, nb_cpus=1, background=1):
+    """``predict_views`` (proc/sd_proc.py:1386-1427).  `views`: one uint8 array or device tensor (n_i, C, nb_views, H, W) per object.
+    With `single_cc_only` every plane of channel 0 goes through ``single_conn_comp_img`` -- one ``sd_views_center_component`` call for
+    the whole batch; for the two views of the glia model these are the reference's two calls per location --, with `background` as
+    its background value: 1 as in the reference, whose call leaves ``single_conn_comp_img``'s default in place although the renderer
+    paints 255.  Then ONE ``model.predict_proba`` call over all locations; -> with `return_proba` the list of per-object slices
+    (n_i, classes); otherwise the slices are stored as ``so.attr_dict[pred_key]`` of the objects in `ch` (there is no storage layer, so
+    `nb_cpus` has nothing to parallelise).  The caller's arrays are not modified (the reference filters them in place)."""
+    from .. import _dev as D
+    from .image import center_component_planes
+    who = 'predict_views'
+    views = list(views)
+    if not return_proba:
+        if ch is None or pred_key is None:
+            raise ValueError(f'{who}: storing the probabilities needs the objects (ch) and pred_key')
+        ch = list(ch)
+        if len(ch) != len(views):
+            raise ValueError(f'{who}: {len(views)} view arrays for {len(ch)} objects')
+    dev = getattr(model, 'dev', None)
+    dev = D.device(None) if dev is None else dev
+    flat, part_views = _views_device(who, views, dev)
+    assert len(part_views) == len(views) + 1
+    if single_cc_only and len(flat):
+        if flat.shape[1] == 1:
+            center_component_planes(flat, background, out=flat)
+        else:
+            flat[:, 0] = center_component_planes(flat[:, 0].contiguous(), background)
+    probas = model.predict_proba(flat, verbose=verbose)
+    so_probas = [probas[part_views[ii]:part_views[ii + 1]] for ii in range(len(views))]
+    if return_proba:
+        return so_probas
+    for so, prob in zip(ch, so_probas):
+        so.attr_dict[pred_key] = prob
+
+
+def predict_sos_views(model, sos, pred_key, nb_cpus=1, woglia=True, verbose=False, raw_only=False, single_cc_only=False, return_proba=False,
+                      background=1):
+    """``predict_sos_views`` (proc/sd_proc.py:1345-1383) over objects that have ``load_views(woglia=, raw_only=)`` and ``attr_dict``:
+    ``predict_views`` in chunks of about 200 objects, cut round-robin as the reference cuts them (``chunkify``), so with `return_proba`
+    the rows follow the chunks.  `raw_only` keeps channel 0 of a view array that has more."""
+    from ..handler.basics import chunkify
+    sos = list(sos)
+    all_probas = []
+    for ch in chunkify(sos, max(1, len(sos) // 200)):
+        views = [sv.load_views(woglia=woglia, raw_only=raw_only) for sv in ch]
+        if raw_only:
+            views = [v[:, :1] if v.shape[1] > 1 else v for v in views]
+        proba = predict_views(model, views, ch, pred_key, verbose=False, single_cc_only=single_cc_only, return_proba=return_proba,
+                              nb_cpus=nb_cpus, background=background)
+        if return_proba:
+            all_probas.append(np.concatenate(proba))
+    if return_proba:
+        return np.concatenate(all_probas)

@@ -395,6 +395,133 @@ def sample_locations_sso(sso, ds_factor=None, device=None):
     return [table.locations[lb[k]:lb[k + 1]] for k in range(len(svs))]
 
 
+# -- glia probabilities from supervoxel views (reps/super_segmentation_helper.py:956-958, :1495-1523) ---------------------------------
+def glia_pred_exists(so) -> bool:
+    """:956-958."""
+    if hasattr(so, 'load_attr_dict'):
+        so.load_attr_dict()
+    return "glia_probas" in so.attr_dict
+
+
+def gliapred_sso_nocache(sso, model, verbose: bool = True, device=None):
+    """:1495-1523: the rendering locations of every supervoxel (``sample_locations_sso``), raw views of the whole cell at all of them
+    (``render_sso_coords(add_cellobjects=False)``; they stay on the device), one ``predict_views`` call, and
+    ``sso.svs[i].attr_dict['glia_probas']`` = float32 (n_i, 2) per supervoxel.  `sso`: anything with ``.mesh`` and ``.svs`` (each with
+    ``.id``, ``.mesh``, ``.rep_coord``, ``.scaling``, ``.attr_dict``), as for ``render_sampled_views``; the reference's assertion on
+    ``sso.version == 'tmp'`` belongs to its storage layer and is not made.  As there, a supervoxel without vertices is looked at from
+    its representative coordinate."""
+    from ..proc.rendering import render_sso_coords
+    from ..proc.sd_proc import predict_views
+    pred_key = "glia_probas"
+    svs = list(sso.svs)
+    coords = sample_locations_sso(sso, device=device)
+    # len(part_views) == N + 1
+    part_views = np.cumsum([0] + [len(c) for c in coords])
+    flat_coords = np.concatenate(coords) if coords else np.zeros((0, 3), np.float32)
+    # views are flat
+    views = render_sso_coords(sso, flat_coords, verbose=verbose, add_cellobjects=False, return_rot_mat=False, device=device, return_device=True)
+    sv_views = [views[part_views[ii]:part_views[ii + 1]] for ii in range(len(svs))]
+    if not sv_views:
+        return
+    probas = predict_views(model, sv_views, None, return_proba=True, pred_key=pred_key, verbose=verbose)
+    for ii, prob in enumerate(probas):
+        svs[ii].attr_dict[pred_key] = prob
+
+
+class GliaTable:
+    """Glia probabilities of many supervoxels, one row per supervoxel, ascending by id: ``sv_ids`` uint64 (n_sv,), ``view_begin`` int64
+    (n_sv + 1,) into ``glia_probas`` float32 (n_loc, 2) (neuron, glia; one row per rendering location), ``glia_proba`` float64 (n_sv,)
+    the mean of column 1 (NaN without locations) and ``glia`` uint8 (n_sv,) the class of ``graphs.glia_pred``.
+    ``glia_probas[:, 1]`` and ``view_begin`` are the arguments of ``run_astrocyte_splitting``."""
+
+    def __init__(self, sv_ids, view_begin, glia_probas, glia_proba, glia):
+        self.sv_ids, self.view_begin = np.asarray(sv_ids, np.uint64), np.asarray(view_begin, np.int64)
+        self.glia_probas, self.glia_proba, self.glia = glia_probas, glia_proba, glia
+        n = len(self.sv_ids)
+        if len(self.view_begin) != n + 1 or self.view_begin[0] != 0 or self.view_begin[-1] != len(glia_probas) or (np.diff(self.view_begin) < 0).any() \
+                or len(glia_proba) != n or len(glia) != n:
+            raise ValueError('GliaTable: offsets do not match the arrays')
+
+    def __len__(self):
+        return len(self.sv_ids)
+
+    def _rows(self, ids):
+        ids = np.asarray(ids, np.uint64).reshape(-1)
+        rows = np.searchsorted(self.sv_ids, ids)
+        if len(ids) and ((rows >= len(self.sv_ids)) | (self.sv_ids[np.minimum(rows, max(len(self.sv_ids) - 1, 0))] != ids)).any():
+            raise KeyError('GliaTable: an id is not in the table')
+        return rows
+
+    def probas_of(self, ids):
+        """The (n_i, 2) probabilities of one id, or the list of them for several."""
+        rows = self._rows(ids)
+        out = [self.glia_probas[self.view_begin[r]:self.view_begin[r + 1]] for r in rows]
+        return out[0] if np.ndim(ids) == 0 else out
+
+    def as_dict(self) -> dict:
+        """id -> (n_i, 2): what the reference stores as ``glia_probas`` per supervoxel."""
+        return {int(i): self.glia_probas[self.view_begin[k]:self.view_begin[k + 1]] for k, i in enumerate(self.sv_ids)}
+
+
+class _Svs:
+    def __init__(self, svs):
+        self.svs = svs
+
+
+def predict_glia_table(cells, model, thresh=None, max_locs_per_batch=None, single_cc_only=False, ds_factor=None, device=None,
+                       background=1) -> GliaTable:
+    """``run_astrocyte_rendering`` and ``run_astrocyte_prediction`` (exec/exec_render.py:206, exec/exec_inference.py:290) for cells in
+    memory -> ``GliaTable``.  `cells`: the connected components of the pruned supervoxel graph as objects with ``.mesh`` and ``.svs``
+    (see ``gliapred_sso_nocache``): as in the reference every supervoxel is looked at in the context of its whole component.  Per cell
+    the locations of its supervoxels are rendered (``render_sso_coords(add_cellobjects=False)``), optionally filtered
+    (`single_cc_only`: ``sd_views_center_component`` with `background`, as ``predict_views`` does), predicted and turned into
+    probabilities in batches of at most `max_locs_per_batch` locations -- default: what keeps the uint8 view tensor at or below 256 MiB,
+    4096 locations of 2 x 128 x 256 --; the views never reach the host, a supervoxel may straddle two batches, and because every
+    sample's arithmetic is its own the result does not depend on the batch size, bit for bit.  A supervoxel without vertices has no
+    locations here (``gliapred_sso_nocache`` looks at it from its representative coordinate): a neuron with a NaN mean, as
+    ``glia_pred`` states.  A cell whose mesh is empty raises.  `thresh` as in ``glia_pred``.  `model`: a
+    ``handler.prediction.GliaViewModel``."""
+    from ..proc import graphs
+    from ..proc.image import center_component_planes
+    from ..proc.rendering import _window_defaults, render_sso_coords
+    what = 'predict_glia_table'
+    cells = list(cells)
+    dev = model.dev if device is None else D.device(device)
+    if max_locs_per_batch is None:
+        ws, nb_views, _ = _window_defaults(None, None, None)
+        max_locs_per_batch = max(1, (256 << 20) // (nb_views * ws[0] * ws[1]))
+    if isinstance(max_locs_per_batch, bool) or int(max_locs_per_batch) != max_locs_per_batch or max_locs_per_batch < 1:
+        raise ValueError(f'{what}: max_locs_per_batch must be a positive integer, got {max_locs_per_batch!r}')
+    B = int(max_locs_per_batch)
+    ids, counts, parts = [], [], []                      # per supervoxel in cell order; per batch the device probabilities
+    for k, cell in enumerate(cells):
+        svs = list(cell.svs)
+        if len(np.asarray(cell.mesh[1]).reshape(-1)) == 0:
+            raise ValueError(f'{what}: cell {k} has an empty mesh')
+        has = [len(np.asarray(sv.mesh[1]).reshape(-1)) > 0 for sv in svs]
+        coords = iter(sample_locations_sso(_Svs([sv for sv, h in zip(svs, has) if h]), ds_factor, device=dev))
+        coords = [next(coords) if h else np.zeros((0, 3), np.float32) for h in has]
+        ids += [int(sv.id) for sv in svs]
+        counts += [len(c) for c in coords]
+        flat = np.concatenate(coords) if coords else np.zeros((0, 3), np.float32)
+        for b0 in range(0, len(flat), B):
+            views = render_sso_coords(cell, flat[b0:b0 + B], add_cellobjects=False, device=dev, return_device=True)
+            if single_cc_only:
+                center_component_planes(views, background, out=views)
+            parts.append(model.predict_device(views))
+    ids = np.array(ids, np.uint64)
+    if len(np.unique(ids)) != len(ids):
+        raise ValueError(f'{what}: a supervoxel id occurs twice')
+    probas = (torch.cat(parts, 0) if parts else torch.zeros((0, 2), dtype=torch.float32, device=dev)).cpu().numpy()
+    order = np.argsort(ids, kind='stable')
+    begin = np.concatenate(([0], np.cumsum(counts))).astype(np.int64)
+    rows = np.concatenate([np.arange(begin[r], begin[r + 1]) for r in order]) if len(order) else np.zeros(0, np.int64)
+    probas = np.ascontiguousarray(probas[rows.astype(np.int64)])
+    view_begin = np.concatenate(([0], np.cumsum(np.asarray(counts, np.int64)[order]))).astype(np.int64)
+    glia, mean = graphs.glia_pred(probas[:, 1], view_begin, thresh, False, dev)
+    return GliaTable(ids[order], view_begin, probas, mean, glia)
+
+
 # -- cell types from multi-views (reps/super_segmentation_helper.py:180-213, :1670-1755, :1981-2065) -------------------------------
 def view_sample_table(n_loc: int, views_per_loc: int, nb_views: int) -> np.ndarray:
     """The draws of ``sso_views_to_modelinput`` (:199-212) as a table over the UNSHUFFLED views (n_loc, C, views_per_loc, H, W): int32

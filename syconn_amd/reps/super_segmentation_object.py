@@ -132,6 +132,17 @@ def predict_views_embedding(sso, model, pred_key_appendix: str = '', view_key=No
     return ssh._embed_to_skeleton(sso, model, views, locs, 'latent_morph' + pred_key_appendix, 'view_ixs')
 
 
+def predict_views_gliaSV(sso, model, pred_key_appendix: str = '', verbose: bool = False, single_cc_only: bool = False):
+    """reps/super_segmentation_object.py:2842-2859: the glia probabilities of the supervoxels ``sso.svs`` from their stored views
+    (``sv.load_views(woglia=False, raw_only=True)``) through ``predict_sos_views``, into ``sv.attr_dict['glia_probas' +
+    pred_key_appendix]``.  A cell of version ``'tmp'`` is not written to (as there); its probabilities are returned, one row per
+    location in the order of ``predict_sos_views`` -- the reference drops them."""
+    from ..proc.sd_proc import predict_sos_views
+    pred_key = "glia_probas" + pred_key_appendix
+    return predict_sos_views(model, sso.svs, pred_key, nb_cpus=getattr(sso, 'nb_cpus', 1), verbose=verbose, woglia=False, raw_only=True,
+                             single_cc_only=single_cc_only, return_proba=getattr(sso, 'version', None) == 'tmp')
+
+
 def certainty_celltype(sso, pred_key=None) -> float:
     """reps/super_segmentation_object.py:3193-3220: the stored certainty, else the entropy certainty of the stored logits."""
     from ..handler.prediction import certainty_estimate
