@@ -1,4 +1,5 @@
-// Device-side helpers shared by the kernel translation units (sd_kernels.hip, sd_dec0.hip): storage types, the MFMA
+// Device-side helpers shared by the kernel translation units (sd_kernels.hip, sd_dec0.hip, and through sd_planar_mma.h the view
+// networks sd_viewnet.hip, sd_fcn.hip, which take the storage and vector types from here): storage types, the MFMA
 // wrappers, packed 16-bit max, explicit LDS reads, cross-lane swaps, LDS-DMA.  gfx950 only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -203,8 +204,8 @@ __device__ __forceinline__ void glds16(const void* g, void* lds_wave_base) {
 // does NOT reliably reach the logits: the next convolution turns it into NaNs, and the packed integer ReLU maps a NaN with the
 // sign bit set to 0 -- a whole tensor can come out as finite zeros (observed: tests/test_gpu_f32.py::test_fp16_range_guard).  So
 // the guard sits where overflow is BORN: every epilogue that rounds fp32 accumulators to the storage type keeps a per-lane running
-// maximum of |value| (one v_max3_f32 per two values) and raises a device flag when it reaches 65520 (the smallest magnitude
-// that rounds to inf); the final-layer epilogues additionally test the softmax denominator / the logits.  The host reads
+// maximum of |value| (one v_max3_f32 per two values) and raises a device flag when it reaches the smallest magnitude
+// that rounds to inf (stores_inf, sd_planar_mma.h); the final-layer epilogues additionally test the softmax denominator / the logits.  The host reads
 // the flag after the forward pass (sd_model_overflow).  Everything here compiles to nothing for bf16: the headline path pays nothing.
 template <typename T> struct StoreGuard {
     unsigned m = 0u;       // running packed unsigned 16-bit maximum of the magnitudes stored so far

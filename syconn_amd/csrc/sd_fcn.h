@@ -17,15 +17,12 @@
 //                                    mean scale, computed in double and rounded to fp32 once; zero for pad channels
 //   cls    float[n_class][dec_last] then float[n_class]: the classifier in fp32
 #pragma once
-#include <stddef.h>
-#include <stdint.h>
-#include <string>
-#include <vector>
-#include "../../include/syconn_dense.h"
+#include "sd_netplan.h"      // the tile (TILE_H x TILE_W positions of one workgroup), rup, to_storage / from_storage
 
 namespace sdfcn {
 
-constexpr int TILE_H = 8, TILE_W = 32;      // positions of one workgroup (4 waves x 4 MFMA row tiles)
+using namespace sdnet;
+
 constexpr int CK = 32;                      // input channels per LDS chunk = one K step
 constexpr int CKP = 40;                     // element stride of a pixel inside the LDS tile (80 bytes: 16-byte aligned, spreads the banks)
 constexpr int HALO_H = TILE_H + 2, HALO_W = TILE_W + 2;
@@ -34,9 +31,6 @@ constexpr int MAX_NT = 4;                   // N tiles of one workgroup (64 outp
 constexpr int MAX_C = 512, MAX_CLASS = 16, N_BLOCKS = 5, MAX_BLOCK_CONVS = 3;
 constexpr double BN_EPS = 1e-5;
 enum { OP_CONV = 0, OP_DECONV = 1, OP_CLASSIFY = 2 };
-
-inline int rup(int v, int m) { return (v + m - 1) / m * m; }
-inline size_t rup_sz(size_t v, size_t m) { return (v + m - 1) / m * m; }
 
 struct Op {
     int kind = OP_CONV;
@@ -70,6 +64,5 @@ double macs_per_view(const Plan& p, int H, int W);
 // taps of an op: (dy, dx) inside the LDS tile relative to the position, and (ky, kx) of the weight.  parity only for OP_DECONV.
 struct Tap { int dy, dx, ky, kx; };
 int taps_of(int kind, int parity, Tap taps[9]);
-// storage type <-> float: sdvn::to_storage / from_storage (sd_viewnet.h)
 
 }  // namespace sdfcn

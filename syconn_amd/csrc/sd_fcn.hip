@@ -18,28 +18,15 @@
 //
 // Small deep layers (x4 is 8 x 16 and x5 4 x 8 at 128 x 256) fill a fraction of an 8 x 32 tile; an M tile is NOT run over several planes
 // there: their time is set by the serial K loop of few workgroups, not by the empty tile slots (tools/semseg_probe.py).
-#include "sd_device.h"
+#include "sd_planar_mma.h"
+#include "sd_netrt.h"
 #include "sd_fcn.h"
-#include "sd_viewnet.h"
 
 #include <algorithm>
-#include <string>
-#include <type_traits>
-#include <vector>
-
-int sd_fail_msg(int code, const char* msg);      // sd_api.hip: sets sd_last_error()
 
 using namespace sdfcn;
 
 namespace {
-
-template <typename T> struct Mma16;
-template <> struct Mma16<f16_t> {
-    static __device__ __forceinline__ f32x4 mfma(f16x8 a, f16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-};
-template <> struct Mma16<bf16_t> {
-    static __device__ __forceinline__ f32x4 mfma(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-};
 
 struct MmaArgs {
     const void* in;          // first layer: uint8 views; else T[planes][H][W][cin_p]
@@ -74,19 +61,13 @@ __device__ __forceinline__ void fcn_mma(const MmaArgs& a, T* tile, long long pla
     for (int ch = 0; ch < a.n_chunks; ++ch) {
         __syncthreads();      // the previous chunk's reads are done
         if constexpr (FIRST) {
-            const long long src = a.plane0 + plane, loc = src / a.nb_views, v = src - loc * a.nb_views;
-            const size_t hw = (size_t)a.H * a.W, cs = hw * a.nb_views;
-            const uint8_t* base = reinterpret_cast<const uint8_t*>(a.in) + ((size_t)loc * a.cin * a.nb_views + v) * hw;
+            const U8Plane<T> u8(a.in, a.plane0 + plane, a.nb_views, a.cin, a.H, a.W);
             for (int p = tid; p < HALO_H * HALO_W; p += 256) {
                 const int ly = p / HALO_W, lx = p - ly * HALO_W, gy = y0 + a.org + ly, gx = x0 + a.org + lx;
                 const bool in = gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
                 V8 val;
 #pragma unroll
-                for (int c = 0; c < 8; ++c) {
-                    float u = 0.f;
-                    if (c < 4 && c < a.cin && in) u = (float)base[c * cs + (size_t)gy * a.W + gx];
-                    val[c] = (T)u;
-                }
+                for (int c = 0; c < 8; ++c) val[c] = c < 4 ? u8.at(c, gy, gx, in) : (T)0.f;
                 *reinterpret_cast<V8*>(tile + p * CKP) = val;
 #pragma unroll
                 for (int vv = 1; vv < 4; ++vv) *reinterpret_cast<uint4*>(tile + p * CKP + vv * 8) = uint4{0u, 0u, 0u, 0u};
@@ -113,7 +94,7 @@ __device__ __forceinline__ void fcn_mma(const MmaArgs& a, T* tile, long long pla
             for (int i = 0; i < 4; ++i) {
                 const V8 af = *reinterpret_cast<const V8*>(tile + pix[i] + off);
 #pragma unroll
-                for (int nt = 0; nt < NT; ++nt) acc[i][nt] = Mma16<T>::mfma(af, b[nt], acc[i][nt]);
+                for (int nt = 0; nt < NT; ++nt) acc[i][nt] = mma16(af, b[nt], acc[i][nt]);
             }
         }
     }
@@ -128,32 +109,20 @@ __device__ __forceinline__ void block_coords(const MmaArgs& a, long long& plane,
     y0 = (tt / a.tiles_x) * TILE_H, x0 = (tt % a.tiles_x) * TILE_W;
 }
 
-template <typename T> __device__ __forceinline__ bool out_of_range(float v) {
-    if constexpr (std::is_same<T, f16_t>::value) return !(fabsf(v) < 65520.f);      // 65520 is the first value that rounds to inf
-    return false;
-}
-
 // 3 x 3 same-padded convolution + bias + ReLU (+ 2 x 2 max-pool)
 template <typename T, int NT, bool FIRST, bool POOL>
 __global__ __launch_bounds__(256) void k_fcn_conv(const MmaArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char fcn_smem[];
     T* tile = reinterpret_cast<T*>(fcn_smem);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, m = lane & 15, g = lane >> 4;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     long long plane;
     int y0, x0, grp;
     block_coords(a, plane, y0, x0, grp);
     int pix[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const int mt = wave * 4 + i;
         int cy, cx;
-        if (POOL) {
-            cy = 2 * (mt >> 2) + ((m & 3) >> 1);
-            cx = 8 * (mt & 3) + 2 * (m >> 2) + (m & 1);
-        } else {
-            cy = mt >> 1;
-            cx = 16 * (mt & 1) + m;
-        }
+        lane_pos(wave, i, lane & 15, POOL, cy, cx);
         pix[i] = (cy * HALO_W + cx) * CKP;
     }
     f32x4 acc[4][NT];
@@ -163,9 +132,10 @@ __global__ __launch_bounds__(256) void k_fcn_conv(const MmaArgs a) {
     auto finish = [&](float v, int n, int py, int px) {
         v = FIRST ? fmaf(v, a.in_scale, a.bias[n]) : v + a.bias[n];
         v = fmaxf(v, 0.f);
-        ovf |= out_of_range<T>(v);
+        ovf |= stores_inf<T>(v);
         out[((size_t)py * a.Wo + px) * a.cout_p + n] = (T)v;
     };
+    const int m = lane & 15, g = lane >> 4;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int mt = wave * 4 + i;
@@ -187,7 +157,7 @@ __global__ __launch_bounds__(256) void k_fcn_conv(const MmaArgs a) {
             }
         }
     }
-    if (ovf) a.flags[0] = 1;      // (every writer stores the same value: the race between blocks is harmless)
+    if (ovf) a.flags[0] = 1;     // (every writer stores the same value: the race between blocks is harmless)
 }
 
 // One output parity of ConvTranspose2d(k = 3, stride = 2, padding = 1, output_padding = 1) + bias + ReLU + BatchNorm (+ skip)
@@ -202,8 +172,9 @@ __global__ __launch_bounds__(256) void k_fcn_deconv(const MmaArgs a) {
     int pix[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const int mt = wave * 4 + i;
-        pix[i] = ((mt >> 1) * HALO_W + 16 * (mt & 1) + m) * CKP;
+        int cy, cx;
+        lane_pos(wave, i, m, false, cy, cx);
+        pix[i] = (cy * HALO_W + cx) * CKP;
     }
     f32x4 acc[4][NT];
     fcn_mma<T, NT, false>(a, tile, plane, y0, x0, grp, pix, acc);
@@ -226,7 +197,7 @@ __global__ __launch_bounds__(256) void k_fcn_deconv(const MmaArgs a) {
                 const size_t o = ((size_t)(2 * iy + a.py) * a.Wo + (2 * ix + a.px)) * a.cout_p + n;
                 float v = fmaf(sc, fmaxf(acc[i][nt][r] + b, 0.f), sh);
                 if (skip) v += (float)skip[o];
-                ovf |= out_of_range<T>(v);
+                ovf |= stores_inf<T>(v);
                 out[o] = (T)v;
             }
         }
@@ -279,8 +250,6 @@ __global__ __launch_bounds__(256) void k_fcn_classify(const ClsArgs a) {
     }
 }
 
-int fail(const std::string& msg, int code = SD_ERR_INVALID) { return sd_fail_msg(code, msg.c_str()); }
-
 template <typename T, int NT>
 void launch_conv_nt(bool first, bool pool, unsigned grid, hipStream_t s, const MmaArgs& a) {
     if (first && pool) hipLaunchKernelGGL((k_fcn_conv<T, NT, true, true>), dim3(grid), dim3(256), LDS_BYTES, s, a);
@@ -309,41 +278,18 @@ void launch_mma(const Op& op, unsigned grid, hipStream_t s, const MmaArgs& a) {
 
 }  // namespace
 
-struct sd_fcn {
-    Plan plan;
-    char* dev_blob = nullptr;
-};
+struct sd_fcn : Net<Plan> {};
 
 extern "C" {
 
 int sd_fcn_create(int in_channels, const int32_t* blocks, const int32_t* block_len, int dec_last, int n_class, const float* weights, size_t n_floats,
                   int act_dtype, sd_fcn** out) {
-    if (!out) return fail("sd_fcn_create: null output");
-    *out = nullptr;
-    sd_fcn* m = new sd_fcn;
-    std::string err;
-    const int rc = build_plan(in_channels, blocks, block_len, dec_last, n_class, weights, n_floats, act_dtype, m->plan, err);
-    if (rc != SD_OK) {
-        delete m;
-        return fail(err, rc);
-    }
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&m->dev_blob), m->plan.blob.size());
-    if (e == hipSuccess) e = hipMemcpy(m->dev_blob, m->plan.blob.data(), m->plan.blob.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (m->dev_blob) (void)hipFree(m->dev_blob);
-        delete m;
-        return fail(std::string("sd_fcn_create: ") + hipGetErrorString(e), e == hipErrorOutOfMemory ? SD_ERR_NOMEM : SD_ERR_HIP);
-    }
-    std::vector<char>().swap(m->plan.blob);
-    *out = m;
-    return SD_OK;
+    return create_net(out, "sd_fcn_create", [&](Plan& plan, std::string& err) {
+        return build_plan(in_channels, blocks, block_len, dec_last, n_class, weights, n_floats, act_dtype, plan, err);
+    });
 }
 
-void sd_fcn_destroy(sd_fcn* m) {
-    if (!m) return;
-    if (m->dev_blob) (void)hipFree(m->dev_blob);
-    delete m;
-}
+void sd_fcn_destroy(sd_fcn* m) { delete m; }
 
 size_t sd_fcn_workspace_bytes(sd_fcn* m, size_t n_planes, int H, int W) {
     if (!m) return 0;
@@ -434,28 +380,14 @@ int sd_fcn_forward(sd_fcn* m, const uint8_t* views_dev, size_t n_planes_total, i
 int sd_fcn_forward_timed(sd_fcn* m, const uint8_t* views_dev, size_t n_planes_total, int nb_views, int H, int W, size_t plane0, size_t n_planes,
                          uint8_t* labels_dev, float* logits_dev, void* workspace_dev, size_t ws_bytes, int32_t* flags_dev, void* stream, float* ms_out) {
     if (!m || !ms_out) return fail("sd_fcn_forward_timed: null argument");
-    const size_t n = m->plan.ops.size() + 1;
-    std::vector<hipEvent_t> ev(n, nullptr);
-    int rc = SD_OK;
-    for (size_t i = 0; i < n && rc == SD_OK; ++i)
-        if (hipEventCreate(&ev[i]) != hipSuccess) rc = fail("sd_fcn_forward_timed: event creation failed", SD_ERR_HIP);
-    if (rc == SD_OK)
-        rc = fcn_forward(m, views_dev, n_planes_total, nb_views, H, W, plane0, n_planes, labels_dev, logits_dev, workspace_dev, ws_bytes, flags_dev, stream,
-                         ev.data());
-    if (rc == SD_OK && hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)) != hipSuccess) rc = fail("sd_fcn_forward_timed: synchronise failed", SD_ERR_HIP);
-    for (size_t i = 0; i + 1 < n && rc == SD_OK; ++i)
-        if (hipEventElapsedTime(&ms_out[i], ev[i], ev[i + 1]) != hipSuccess) rc = fail("sd_fcn_forward_timed: elapsed time failed", SD_ERR_HIP);
-    for (hipEvent_t e : ev)
-        if (e) (void)hipEventDestroy(e);
-    return rc;
+    return timed(m->plan.ops.size() + 1, stream, ms_out, "sd_fcn_forward_timed", [&](hipEvent_t* ev) {
+        return fcn_forward(m, views_dev, n_planes_total, nb_views, H, W, plane0, n_planes, labels_dev, logits_dev, workspace_dev, ws_bytes, flags_dev, stream,
+                           ev);
+    });
 }
 
 int sd_fcn_overflow(sd_fcn* m, const int32_t* flags_dev, void* stream, int32_t* flags_out) {
-    if (!m || !flags_dev || !flags_out) return fail("sd_fcn_overflow: null argument");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (hipMemcpyAsync(flags_out, flags_dev, sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-        return fail("sd_fcn_overflow: copy failed", SD_ERR_HIP);
-    return SD_OK;
+    return read_flags(m, flags_dev, 1, stream, flags_out, "sd_fcn_overflow");
 }
 
 int sd_fcn_read_buffer(sd_fcn* m, int index, const void* workspace_dev, const float* logits_dev, size_t n_planes, int H, int W, float* out_host,
@@ -468,27 +400,17 @@ int sd_fcn_read_buffer(sd_fcn* m, int index, const void* workspace_dev, const fl
     std::vector<Dims> dims;
     std::string err;
     if (workspace(p, n_planes, H, W, ws, err) != SD_OK || infer_shapes(p, H, W, dims, err) != SD_OK) return fail(err);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const Dims& d = dims[index];
     if (index == n_ops - 1) {
         dims_out[0] = (int32_t)n_planes, dims_out[1] = d.c, dims_out[2] = d.h, dims_out[3] = d.w;
         if (!out_host) return SD_OK;
         if (!logits_dev) return fail("sd_fcn_read_buffer: the logits were not kept (logits_dev is null)");
-        if (hipMemcpyAsync(out_host, logits_dev, n_planes * d.c * d.h * d.w * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess)
-            return fail("sd_fcn_read_buffer: copy failed", SD_ERR_HIP);
-        return SD_OK;
+        return copy_out(out_host, logits_dev, n_planes * d.c * d.h * d.w * sizeof(float), stream, "sd_fcn_read_buffer");
     }
     dims_out[0] = (int32_t)n_planes, dims_out[1] = d.h, dims_out[2] = d.w, dims_out[3] = d.c;
     if (!out_host) return SD_OK;
-    const size_t px = n_planes * d.h * d.w;
-    std::vector<uint16_t> raw(px * d.cp);
-    if (hipMemcpyAsync(raw.data(), reinterpret_cast<const char*>(workspace_dev) + ws.off[index], raw.size() * 2, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess)
-        return fail("sd_fcn_read_buffer: copy failed", SD_ERR_HIP);
-    for (size_t i = 0; i < px; ++i)
-        for (int c = 0; c < d.c; ++c) out_host[i * d.c + c] = sdvn::from_storage(raw[i * d.cp + c], p.act_dtype);
-    return SD_OK;
+    return read_stored(reinterpret_cast<const char*>(workspace_dev) + ws.off[index], n_planes * d.h * d.w, d.c, d.cp, p.act_dtype, out_host, stream,
+                       "sd_fcn_read_buffer");
 }
 
 }  // extern "C"

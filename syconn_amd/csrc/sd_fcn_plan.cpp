@@ -2,24 +2,11 @@
 // of the convolutions and of the four output parities of the transposed convolutions, the BatchNorm constants, shapes and the
 // workspace layout.
 #include "sd_fcn.h"
-#include "sd_viewnet.h"      // sdvn::to_storage / from_storage
 
 #include <cmath>
 #include <cstring>
 
 namespace sdfcn {
-
-namespace {
-int bad(std::string& err, const std::string& msg) {
-    err = msg;
-    return SD_ERR_INVALID;
-}
-size_t grow(std::vector<char>& blob, size_t bytes) {      // a zeroed, 256-byte aligned range at the end of the blob
-    const size_t off = rup_sz(blob.size(), 256);
-    blob.resize(off + bytes, 0);
-    return off;
-}
-}  // namespace
 
 int taps_of(int kind, int parity, Tap taps[9]) {
     if (kind == OP_CONV) {
@@ -43,7 +30,6 @@ static int pack_frags(Plan& plan, Op& op, const float* w, bool deconv, int parit
     const int NTtot = op.NT * op.groups;
     off_out = grow(plan.blob, (size_t)op.n_chunks * nt * NTtot * 64 * 8 * 2);
     uint16_t* f = reinterpret_cast<uint16_t*>(plan.blob.data() + off_out);
-    const uint16_t inf = plan.act_dtype == SD_BF16 ? 0x7f80u : 0x7c00u;
     for (int ch = 0; ch < op.n_chunks; ++ch)
         for (int t = 0; t < nt; ++t)
             for (int ntg = 0; ntg < NTtot; ++ntg)
@@ -54,8 +40,7 @@ static int pack_frags(Plan& plan, Op& op, const float* w, bool deconv, int parit
                         if (c < op.cin && n < op.cout) {
                             const size_t idx = deconv ? (((size_t)c * op.cout + n) * 3 + taps[t].ky) * 3 + taps[t].kx
                                                       : (((size_t)n * op.cin + c) * 3 + taps[t].ky) * 3 + taps[t].kx;
-                            v = sdvn::to_storage(w[idx], plan.act_dtype);
-                            if ((v & 0x7fffu) == inf) return bad(err, what + ": a weight overflows the storage type (use bf16, or rescale)");
+                            if (!store_weight(w[idx], plan.act_dtype, v)) return bad(err, what + ": a weight overflows the storage type (use bf16, or rescale)");
                         }
                         f[((((size_t)ch * nt + t) * NTtot + ntg) * 64 + lane) * 8 + j] = v;
                     }

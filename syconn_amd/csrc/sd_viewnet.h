@@ -13,23 +13,17 @@
 //                                    (cin_p = 4) reads two taps of 4 channels, hence two offsets; padding k point at offset 0
 //   bias   float[16 NT]              b, for the first layer b - 0.5 sum(stored w): conv(u / 255 - 0.5) = acc(u) / 255 - 0.5 sum(w) + b
 #pragma once
-#include <stddef.h>
-#include <stdint.h>
-#include <string>
-#include <vector>
-#include "../../include/syconn_dense.h"
+#include "sd_netplan.h"      // the tile (TILE_H x TILE_W convolution outputs of one workgroup), rup, to_storage / from_storage
 
 namespace sdvn {
 
-constexpr int TILE_H = 8, TILE_W = 32;      // convolution outputs of one workgroup (4 waves x 4 MFMA row tiles)
+using namespace sdnet;
+
 constexpr int MAX_NT = 5;                   // cout <= 80
 constexpr int MAX_FC = 4;
 constexpr size_t MAX_LDS = 65536;           // halo tile of a layer / the two vectors of the head
 constexpr int ACT_RELU = 0, ACT_LEAKY = 1;
 constexpr float LEAKY_SLOPE = 0.01f;        // torch.nn.LeakyReLU()
-
-inline int rup(int v, int m) { return (v + m - 1) / m * m; }
-inline size_t rup_sz(size_t v, size_t m) { return (v + m - 1) / m * m; }
 
 struct Layer {
     int cin = 0, cout = 0, k = 0, pool = 0;
@@ -73,8 +67,5 @@ inline int head_tile_samples(const Plan& p) {
         if (head_tile_lds(p, ts) <= HEAD_TILE_LDS) return ts;
     return 1;
 }
-// storage type <-> float (the plan's rounding: nearest even)
-uint16_t to_storage(float f, int dtype);
-float from_storage(uint16_t bits, int dtype);
 
 }  // namespace sdvn

@@ -11,26 +11,15 @@
 // maximum of a lane's four registers and rows / columns that the floor pool drops are never part of a stored window.  Without a pool
 // a tile is 16 pixels of one row.  The epilogue runs in fp32: max, + bias (first layer: acc / 255 + (b - 0.5 sum w), a rising map,
 // so it commutes with the maximum), activation, range guard, round to nearest even, 2-byte store (16 lanes = 32 contiguous bytes).
-#include "sd_device.h"
+#include "sd_planar_mma.h"
+#include "sd_netrt.h"
 #include "sd_viewnet.h"
 
 #include <algorithm>
-#include <string>
-#include <vector>
-
-int sd_fail_msg(int code, const char* msg);      // sd_api.hip: sets sd_last_error()
 
 using namespace sdvn;
 
 namespace {
-
-template <typename T> struct Mma16;
-template <> struct Mma16<f16_t> {
-    static __device__ __forceinline__ f32x4 mfma(f16x8 a, f16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-};
-template <> struct Mma16<bf16_t> {
-    static __device__ __forceinline__ f32x4 mfma(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-};
 
 struct ConvArgs {
     const void* in;          // first layer: uint8 views; else T[planes][H][W][cin_p]
@@ -63,15 +52,8 @@ __global__ __launch_bounds__(256) void k_vn_conv(const ConvArgs a) {
     int pix[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const int mt = wave * 4 + i;
         int cy, cx;
-        if (a.pool == 2) {
-            cy = 2 * (mt >> 2) + ((m & 3) >> 1);
-            cx = 8 * (mt & 3) + 2 * (m >> 2) + (m & 1);
-        } else {
-            cy = mt >> 1;
-            cx = 16 * (mt & 1) + m;
-        }
+        lane_pos(wave, i, m, a.pool == 2, cy, cx);
         pix[i] = (cy * twin + cx) * a.cin_p;
     }
     for (long long t = blockIdx.x; t < a.n_tiles; t += gridDim.x) {
@@ -85,18 +67,12 @@ __global__ __launch_bounds__(256) void k_vn_conv(const ConvArgs a) {
                 if (tid == 0) a.flags[1] = 1;      // (every writer stores the same value: the race between blocks is harmless)
                 continue;
             }
-            const long long loc = src / a.nb_views, v = src - loc * a.nb_views;
-            const size_t hw = (size_t)a.H * a.W, cs = hw * a.nb_views;
-            const uint8_t* base = reinterpret_cast<const uint8_t*>(a.in) + ((size_t)loc * a.cin * a.nb_views + v) * hw;
+            const U8Plane<T> u8(a.in, src, a.nb_views, a.cin, a.H, a.W);
             for (int i = tid; i < thin * twin; i += 256) {
                 const int iy = i / twin, ix = i - iy * twin, gy = y0 + iy, gx = x0 + ix;
                 V4 val;
 #pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    float u = 0.f;
-                    if (c < a.cin && gy < a.H && gx < a.W) u = (float)base[c * cs + (size_t)gy * a.W + gx];
-                    val[c] = (T)u;
-                }
+                for (int c = 0; c < 4; ++c) val[c] = u8.at(c, gy, gx, gy < a.H && gx < a.W);
                 *reinterpret_cast<V4*>(tile + i * 4) = val;
             }
         } else {
@@ -130,7 +106,7 @@ __global__ __launch_bounds__(256) void k_vn_conv(const ConvArgs a) {
                     af = *reinterpret_cast<const V8*>(tile + pix[i] + off.x);
                 }
 #pragma unroll
-                for (int nt = 0; nt < NT; ++nt) acc[i][nt] = Mma16<T>::mfma(af, b[nt], acc[i][nt]);
+                for (int nt = 0; nt < NT; ++nt) acc[i][nt] = mma16(af, b[nt], acc[i][nt]);
             }
         }
         // epilogue
@@ -139,7 +115,7 @@ __global__ __launch_bounds__(256) void k_vn_conv(const ConvArgs a) {
         auto finish = [&](float v, int n, int py, int px) {
             v = FIRST ? fmaf(v, a.scale, a.bias[n]) : v + a.bias[n];
             v = v < 0.f ? fmaf(v, a.slope, 0.f) : v;      // (a NaN stays a NaN; slope 0 gives +0)
-            if constexpr (std::is_same<T, f16_t>::value) ovf |= !(fabsf(v) < 65520.f);      // 65520 is the first value that rounds to inf
+            ovf |= stores_inf<T>(v);
             if (py < a.Ho && px < a.Wo) out[((size_t)py * a.Wo + px) * a.cout_p + n] = (T)v;
         };
 #pragma unroll
@@ -317,8 +293,6 @@ hipError_t launch_head_tile_ts(int TS, int grid, size_t lds, hipStream_t s, cons
     }
 }
 
-int fail(const std::string& msg, int code = SD_ERR_INVALID) { return sd_fail_msg(code, msg.c_str()); }
-
 template <typename T, bool FIRST>
 void launch_conv_nt(int NT, int grid, size_t lds, hipStream_t s, const ConvArgs& a) {
     switch (NT) {
@@ -337,41 +311,18 @@ void launch_conv(bool first, int NT, int grid, size_t lds, hipStream_t s, const 
 
 }  // namespace
 
-struct sd_viewnet {
-    Plan plan;
-    char* dev_blob = nullptr;
-};
+struct sd_viewnet : Net<Plan> {};
 
 extern "C" {
 
 int sd_viewnet_create(const sd_viewnet_layer_desc* layers, int n_layers, const int32_t* fc, int n_fc, int in_channels, int n_scalar, int act,
                       const float* weights, size_t n_floats, int act_dtype, sd_viewnet** out) {
-    if (!out) return fail("sd_viewnet_create: null output");
-    *out = nullptr;
-    sd_viewnet* m = new sd_viewnet;
-    std::string err;
-    const int rc = build_plan(layers, n_layers, fc, n_fc, in_channels, n_scalar, act, weights, n_floats, act_dtype, m->plan, err);
-    if (rc != SD_OK) {
-        delete m;
-        return fail(err, rc);
-    }
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&m->dev_blob), m->plan.blob.size());
-    if (e == hipSuccess) e = hipMemcpy(m->dev_blob, m->plan.blob.data(), m->plan.blob.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (m->dev_blob) (void)hipFree(m->dev_blob);
-        delete m;
-        return fail(std::string("sd_viewnet_create: ") + hipGetErrorString(e), e == hipErrorOutOfMemory ? SD_ERR_NOMEM : SD_ERR_HIP);
-    }
-    std::vector<char>().swap(m->plan.blob);
-    *out = m;
-    return SD_OK;
+    return create_net(out, "sd_viewnet_create", [&](Plan& plan, std::string& err) {
+        return build_plan(layers, n_layers, fc, n_fc, in_channels, n_scalar, act, weights, n_floats, act_dtype, plan, err);
+    });
 }
 
-void sd_viewnet_destroy(sd_viewnet* m) {
-    if (!m) return;
-    if (m->dev_blob) (void)hipFree(m->dev_blob);
-    delete m;
-}
+void sd_viewnet_destroy(sd_viewnet* m) { delete m; }
 
 size_t sd_viewnet_workspace_bytes(sd_viewnet* m, size_t n_samples, int D, int H, int W) {
     if (!m) return 0;
@@ -471,20 +422,10 @@ static int vn_forward_timed(sd_viewnet* m, const uint8_t* views_dev, size_t n_pl
                             void* workspace_dev, size_t ws_bytes, int32_t* flags_dev, void* stream, float* ms_out, bool tiled_head) {
     const std::string who = tiled_head ? "sd_viewnet_embed_timed" : "sd_viewnet_forward_timed";
     if (!m || !ms_out) return fail(who + ": null argument");
-    const size_t n = m->plan.layers.size() + 2;
-    std::vector<hipEvent_t> ev(n, nullptr);
-    int rc = SD_OK;
-    for (size_t i = 0; i < n && rc == SD_OK; ++i)
-        if (hipEventCreate(&ev[i]) != hipSuccess) rc = fail(who + ": event creation failed", SD_ERR_HIP);
-    if (rc == SD_OK)
-        rc = vn_forward(m, views_dev, n_planes_total, nb_views, H, W, sample_table_dev, n_samples, D, scalars_dev, logits_dev, workspace_dev, ws_bytes,
-                        flags_dev, stream, ev.data(), tiled_head);
-    if (rc == SD_OK && hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)) != hipSuccess) rc = fail(who + ": synchronise failed", SD_ERR_HIP);
-    for (size_t i = 0; i + 1 < n && rc == SD_OK; ++i)
-        if (hipEventElapsedTime(&ms_out[i], ev[i], ev[i + 1]) != hipSuccess) rc = fail(who + ": elapsed time failed", SD_ERR_HIP);
-    for (hipEvent_t e : ev)
-        if (e) (void)hipEventDestroy(e);
-    return rc;
+    return timed(m->plan.layers.size() + 2, stream, ms_out, who, [&](hipEvent_t* ev) {
+        return vn_forward(m, views_dev, n_planes_total, nb_views, H, W, sample_table_dev, n_samples, D, scalars_dev, logits_dev, workspace_dev, ws_bytes,
+                          flags_dev, stream, ev, tiled_head);
+    });
 }
 
 int sd_viewnet_forward_timed(sd_viewnet* m, const uint8_t* views_dev, size_t n_planes_total, int nb_views, int H, int W,
@@ -511,11 +452,7 @@ int sd_viewnet_embed_timed(sd_viewnet* m, const uint8_t* views_dev, size_t n_pla
 int sd_viewnet_embed_tile_samples(sd_viewnet* m) { return m ? head_tile_samples(m->plan) : 0; }
 
 int sd_viewnet_overflow(sd_viewnet* m, const int32_t* flags_dev, void* stream, int32_t* flags_out) {
-    if (!m || !flags_dev || !flags_out) return fail("sd_viewnet_overflow: null argument");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (hipMemcpyAsync(flags_out, flags_dev, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-        return fail("sd_viewnet_overflow: copy failed", SD_ERR_HIP);
-    return SD_OK;
+    return read_flags(m, flags_dev, 2, stream, flags_out, "sd_viewnet_overflow");
 }
 
 int sd_viewnet_read_buffer(sd_viewnet* m, int index, const void* workspace_dev, const float* logits_dev, size_t n_samples, int D, int H, int W,
@@ -528,27 +465,19 @@ int sd_viewnet_read_buffer(sd_viewnet* m, int index, const void* workspace_dev, 
     std::vector<Dims> dims;
     std::string err;
     if (workspace(p, n_samples, D, H, W, ws, err) != SD_OK || infer_shapes(p, D, H, W, dims, err) != SD_OK) return fail(err);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const char* wsb = reinterpret_cast<const char*>(workspace_dev);
     if (index >= nl) {
         const int j = index - nl, nout = p.fc[j].nout;
         dims_out[0] = (int32_t)n_samples, dims_out[1] = 1, dims_out[2] = 1, dims_out[3] = nout;
         if (!out_host) return SD_OK;
         const void* src = j + 1 < nf ? (const void*)(wsb + ws.hidden_off[j]) : (const void*)logits_dev;
-        if (hipMemcpyAsync(out_host, src, n_samples * nout * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-            return fail("sd_viewnet_read_buffer: copy failed", SD_ERR_HIP);
-        return SD_OK;
+        return copy_out(out_host, src, n_samples * nout * sizeof(float), stream, "sd_viewnet_read_buffer");
     }
     const Layer& L = p.layers[index];
     const size_t px = n_samples * D * dims[index].h * dims[index].w;
     dims_out[0] = (int32_t)(n_samples * D), dims_out[1] = dims[index].h, dims_out[2] = dims[index].w, dims_out[3] = L.cout;
     if (!out_host) return SD_OK;
-    std::vector<uint16_t> raw(px * L.cout_p);
-    if (hipMemcpyAsync(raw.data(), wsb + ws.layer_off[index], raw.size() * 2, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-        return fail("sd_viewnet_read_buffer: copy failed", SD_ERR_HIP);
-    for (size_t i = 0; i < px; ++i)
-        for (int c = 0; c < L.cout; ++c) out_host[i * L.cout + c] = from_storage(raw[i * L.cout_p + c], p.act_dtype);
-    return SD_OK;
+    return read_stored(wsb + ws.layer_off[index], px, L.cout, L.cout_p, p.act_dtype, out_host, stream, "sd_viewnet_read_buffer");
 }
 
 }  // extern "C"

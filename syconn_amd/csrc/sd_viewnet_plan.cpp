@@ -8,43 +8,6 @@
 
 namespace sdvn {
 
-uint16_t to_storage(float f, int dtype) {
-    if (dtype == SD_BF16) {
-        uint32_t u;
-        std::memcpy(&u, &f, 4);
-        if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);      // NaN
-        u += 0x7fffu + ((u >> 16) & 1u);
-        return (uint16_t)(u >> 16);
-    }
-    const _Float16 h = (_Float16)f;
-    uint16_t b;
-    std::memcpy(&b, &h, 2);
-    return b;
-}
-float from_storage(uint16_t bits, int dtype) {
-    if (dtype == SD_BF16) {
-        const uint32_t u = (uint32_t)bits << 16;
-        float f;
-        std::memcpy(&f, &u, 4);
-        return f;
-    }
-    _Float16 h;
-    std::memcpy(&h, &bits, 2);
-    return (float)h;
-}
-
-namespace {
-int bad(std::string& err, const std::string& msg) {
-    err = msg;
-    return SD_ERR_INVALID;
-}
-size_t grow(std::vector<char>& blob, size_t bytes) {      // a zeroed, 256-byte aligned range at the end of the blob
-    const size_t off = rup_sz(blob.size(), 256);
-    blob.resize(off + bytes, 0);
-    return off;
-}
-}  // namespace
-
 int build_plan(const sd_viewnet_layer_desc* layers, int n_layers, const int32_t* fc, int n_fc, int in_channels, int n_scalar, int act,
                const float* W, size_t n_floats, int act_dtype, Plan& plan, std::string& err) {
     if (!layers || !fc || !W) return bad(err, "viewnet: null argument");
@@ -110,8 +73,7 @@ int build_plan(const sd_viewnet_layer_desc* layers, int n_layers, const int32_t*
                             const int tap = kk / L.cin_p, c = kk % L.cin_p;
                             uint16_t v = 0;
                             if (tap < taps && c < cin && n < d.cout) {
-                                v = to_storage(w[((size_t)n * cin + c) * taps + tap], act_dtype);
-                                if ((v & 0x7fffu) == (act_dtype == SD_BF16 ? 0x7f80u : 0x7c00u))
+                                if (!store_weight(w[((size_t)n * cin + c) * taps + tap], act_dtype, v))
                                     return bad(err, "viewnet: layer " + std::to_string(i) + ": a weight overflows the storage type (use bf16, or rescale)");
                                 wsum[n] += (double)from_storage(v, act_dtype);
                             }

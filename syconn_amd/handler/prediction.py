@@ -786,16 +786,16 @@ class ViewSamples:
         self.views, self.table = views, table
 
 
-class ViewModel:
-    """``InferenceModel`` of elektronn3 (prediction.py:999) for a view network given as a spec: ``predict_proba(inp, bs=None)`` with
-    ``inp = views`` or ``(views, scalars)`` returns the float32 logits (n_samples, n_classes) -- the cell type path passes no normalising
-    function, so "proba" are logits there too.  `weights`: a state dict, a module, or the path of a ``torch.jit`` file.  The views are
-    uint8 (n_samples, C, D, H, W), a ``ViewSamples``, or float32 that ``views_to_uint8`` takes.  Deviations: DESIGN.md."""
+class _DeviceNet:
+    """What the view models share: the weights of a spec (`weights`: a state dict, a module, or the path of a ``torch.jit`` file) as one
+    float32 blob, the device, and the handle of the C model ``sd_<_net>_*`` that the subclass's ``_create(lib, blob, n_floats, dtype,
+    out)`` makes."""
 
-    _entry = 'sd_viewnet_forward'      # the C entry of a launch set (EmbeddingModel: the one with the sample-tiled head)
+    _net = ''      # 'viewnet' / 'fcn'
 
-    def __init__(self, spec, weights, act_dtype: str = 'f16', bs: int = 40, device=None):
+    def __init__(self, spec, weights, act_dtype: str, bs: int, device):
         from .. import _dev as dv
+        import ctypes as C
         if act_dtype not in ('f16', 'bf16'):
             raise ValueError("act_dtype must be 'f16' or 'bf16'")
         if isinstance(weights, (str, os.PathLike)):
@@ -803,32 +803,68 @@ class ViewModel:
         if hasattr(weights, 'state_dict'):
             weights = weights.state_dict()
         arrs = spec.weights_from_state_dict(weights)
-        self.spec, self.act_dtype, self.bs = spec, act_dtype, int(bs)
-        if self.bs < 1:
-            raise ValueError('bs must be positive')
+        self.spec, self.act_dtype, self.bs = spec, act_dtype, self._bs(bs)
         self.dev = dv.device(device)
-        import ctypes as C
-        lib = L.load()
         blob = np.concatenate([a.ravel() for a in arrs]).astype(np.float32)
-        descs = (L.ViewNetLayerDesc * len(spec.layers))(*[L.ViewNetLayerDesc(*l) for l in spec.layers])
-        sizes = spec.linear_sizes
-        fc = (C.c_int32 * len(sizes))(*sizes)
         h = C.c_void_p()
         with torch.cuda.device(self.dev):
-            L.check(lib.sd_viewnet_create(descs, len(spec.layers), fc, len(sizes) - 1, spec.in_channels, spec.n_scalar,
-                                          0 if spec.act == 'relu' else 1, blob.ctypes.data_as(C.POINTER(C.c_float)), blob.size,
-                                          L.SD_F16 if act_dtype == 'f16' else L.SD_BF16, C.byref(h)), 'sd_viewnet_create')
+            L.check(self._create(L.load(), blob.ctypes.data_as(C.POINTER(C.c_float)), blob.size, L.SD_F16 if act_dtype == 'f16' else L.SD_BF16,
+                                 C.byref(h)), f'sd_{self._net}_create')
         self._h = h
-        self._last = None
+        self._last = None      # the last launch set: the arguments of read_buffer behind the index, device tensors as they are
 
     def __del__(self):
         h, self._h = getattr(self, '_h', None), None
         if h:
-            L.load().sd_viewnet_destroy(h)
+            getattr(L.load(), f'sd_{self._net}_destroy')(h)
+
+    @staticmethod
+    def _bs(bs) -> int:
+        bs = int(bs)
+        if bs < 1:
+            raise ValueError('bs must be positive')
+        return bs
 
     @property
     def num_ops(self) -> int:
-        return L.load().sd_viewnet_num_ops(self._h)
+        return getattr(L.load(), f'sd_{self._net}_num_ops')(self._h)
+
+    def _read_buffer(self, index: int) -> np.ndarray:
+        """``sd_<_net>_read_buffer`` twice: for the dims, then for the data."""
+        from .. import _dev as dv
+        import ctypes as C
+        if self._last is None:
+            raise RuntimeError('read_buffer: no forward yet')
+        name = f'sd_{self._net}_read_buffer'
+        read = getattr(L.load(), name)
+        args = (self._h, int(index), *(a.data_ptr() if isinstance(a, torch.Tensor) else a for a in self._last))
+        dims = (C.c_int32 * 4)()
+        L.check(read(*args, None, dims, dv.stream(self.dev)), name)
+        out = np.empty(tuple(dims), dtype=np.float32)
+        L.check(read(*args, out.ctypes.data_as(C.POINTER(C.c_float)), dims, dv.stream(self.dev)), name)
+        return out
+
+
+class ViewModel(_DeviceNet):
+    """``InferenceModel`` of elektronn3 (prediction.py:999) for a view network given as a spec: ``predict_proba(inp, bs=None)`` with
+    ``inp = views`` or ``(views, scalars)`` returns the float32 logits (n_samples, n_classes) -- the cell type path passes no normalising
+    function, so "proba" are logits there too.  `weights`: a state dict, a module, or the path of a ``torch.jit`` file.  The views are
+    uint8 (n_samples, C, D, H, W), a ``ViewSamples``, or float32 that ``views_to_uint8`` takes.  Deviations: DESIGN.md."""
+
+    _net = 'viewnet'
+    _entry = 'sd_viewnet_forward'      # the C entry of a launch set (EmbeddingModel: the one with the sample-tiled head)
+
+    def __init__(self, spec, weights, act_dtype: str = 'f16', bs: int = 40, device=None):
+        super().__init__(spec, weights, act_dtype, bs, device)
+
+    def _create(self, lib, blob, n_floats, dtype, out):
+        import ctypes as C
+        spec = self.spec
+        descs = (L.ViewNetLayerDesc * len(spec.layers))(*[L.ViewNetLayerDesc(*l) for l in spec.layers])
+        sizes = spec.linear_sizes
+        fc = (C.c_int32 * len(sizes))(*sizes)
+        return lib.sd_viewnet_create(descs, len(spec.layers), fc, len(sizes) - 1, spec.in_channels, spec.n_scalar,
+                                     0 if spec.act == 'relu' else 1, blob, n_floats, dtype, out)
 
     def _samples(self, views) -> 'ViewSamples':
         if isinstance(views, ViewSamples):
@@ -860,9 +896,7 @@ class ViewModel:
         from .. import _dev as dv
         views, scal = inp if isinstance(inp, (tuple, list)) else (inp, None)
         spec = self.spec
-        bs = self.bs if bs is None else int(bs)
-        if bs < 1:
-            raise ValueError('bs must be positive')
+        bs = self.bs if bs is None else self._bs(bs)
         sm = self._samples(views)
         n, D = int(sm.table.shape[0]), int(sm.table.shape[1])
         n_loc, _, nb_views, H, W = (int(x) for x in sm.views.shape)
@@ -897,18 +931,8 @@ class ViewModel:
     def read_buffer(self, index: int) -> np.ndarray:
         """Debug: after ``predict_proba``, the stored output of layer `index` of the LAST launch set as float32 (planes, Ho, Wo, cout), or
         for ``index >= len(spec.layers)`` the output of Linear ``index - len(spec.layers)`` as (n_samples, out)."""
-        from .. import _dev as dv
-        import ctypes as C
-        if self._last is None:
-            raise RuntimeError('read_buffer: no forward yet')
-        ws, logits, n, D, H, W = self._last
-        lib = L.load()
-        dims = (C.c_int32 * 4)()
-        args = (self._h, int(index), ws.data_ptr(), logits.data_ptr(), n, D, H, W)
-        L.check(lib.sd_viewnet_read_buffer(*args, None, dims, dv.stream(self.dev)), 'sd_viewnet_read_buffer')
-        out = np.empty(tuple(dims), dtype=np.float32)
-        L.check(lib.sd_viewnet_read_buffer(*args, out.ctypes.data_as(C.POINTER(C.c_float)), dims, dv.stream(self.dev)), 'sd_viewnet_read_buffer')
-        return out if index < len(self.spec.layers) else out.reshape(dims[0], dims[3])
+        out = self._read_buffer(index)
+        return out if index < len(self.spec.layers) else out.reshape(out.shape[0], out.shape[3])
 
 
 def get_celltype_model_e3(act_dtype: str = 'f16', n_classes: int = 7, n_scalar: int = 2):
@@ -1060,7 +1084,7 @@ def semseg_views_to_uint8(x: np.ndarray) -> np.ndarray:
     return u8
 
 
-class SemsegViewModel:
+class SemsegViewModel(_DeviceNet):
     """``InferenceModel`` of elektronn3 (prediction.py:1003-1030) for an FCN given as a spec (syconn_amd/cnn/fcn_spec.py).
     ``predict_proba(views (N, C, H, W))`` returns the float32 logits (N, n_class, H, W) -- the reference passes no normalising
     function and takes the argmax, which a softmax would not change --; ``predict_labels(views (n_loc, C, nb_views, H, W))`` reads
@@ -1070,40 +1094,17 @@ class SemsegViewModel:
     at most ``max_workspace_bytes`` of workspace."""
 
     max_workspace_bytes = 4 << 30
+    _net = 'fcn'
 
     def __init__(self, spec, weights, act_dtype: str = 'f16', bs: int = 10, device=None):
-        from .. import _dev as dv
+        super().__init__(spec, weights, act_dtype, bs, device)
+
+    def _create(self, lib, blob, n_floats, dtype, out):
         import ctypes as C
-        if act_dtype not in ('f16', 'bf16'):
-            raise ValueError("act_dtype must be 'f16' or 'bf16'")
-        if isinstance(weights, (str, os.PathLike)):
-            weights = torch.jit.load(os.fspath(weights), map_location='cpu')
-        if hasattr(weights, 'state_dict'):
-            weights = weights.state_dict()
-        arrs = spec.weights_from_state_dict(weights)
-        self.spec, self.act_dtype, self.bs = spec, act_dtype, int(bs)
-        if self.bs < 1:
-            raise ValueError('bs must be positive')
-        self.dev = dv.device(device)
-        lib = L.load()
-        blob = np.concatenate([a.ravel() for a in arrs]).astype(np.float32)
+        spec = self.spec
         flat = [c for b in spec.blocks for c in b]
         blocks, lens = (C.c_int32 * len(flat))(*flat), (C.c_int32 * 5)(*[len(b) for b in spec.blocks])
-        h = C.c_void_p()
-        with torch.cuda.device(self.dev):
-            L.check(lib.sd_fcn_create(spec.in_channels, blocks, lens, spec.dec_last, spec.n_class, blob.ctypes.data_as(C.POINTER(C.c_float)),
-                                      blob.size, L.SD_F16 if act_dtype == 'f16' else L.SD_BF16, C.byref(h)), 'sd_fcn_create')
-        self._h = h
-        self._last = None
-
-    def __del__(self):
-        h, self._h = getattr(self, '_h', None), None
-        if h:
-            L.load().sd_fcn_destroy(h)
-
-    @property
-    def num_ops(self) -> int:
-        return L.load().sd_fcn_num_ops(self._h)
+        return lib.sd_fcn_create(spec.in_channels, blocks, lens, spec.dec_last, spec.n_class, blob, n_floats, dtype, out)
 
     def _views(self, views, ndim: int) -> torch.Tensor:
         if isinstance(views, np.ndarray) and views.dtype == np.float32:
@@ -1123,9 +1124,7 @@ class SemsegViewModel:
 
     def _forward(self, v: torch.Tensor, bs: Optional[int], want_logits: bool):
         from .. import _dev as dv
-        bs = self.bs if bs is None else int(bs)
-        if bs < 1:
-            raise ValueError('bs must be positive')
+        bs = self.bs if bs is None else self._bs(bs)
         n_loc, _, nb_views, H, W = (int(x) for x in v.shape)
         n = n_loc * nb_views
         per_plane = int(L.load().sd_fcn_workspace_bytes(self._h, 1, H, W))
@@ -1157,18 +1156,7 @@ class SemsegViewModel:
     def read_buffer(self, index: int) -> np.ndarray:
         """Debug: after a forward, the stored output of op `index` of the LAST launch set as float32 (planes, h, w, c); the last op's are
         the logits (planes, n_class, H, W) (``predict_proba`` only)."""
-        from .. import _dev as dv
-        import ctypes as C
-        if self._last is None:
-            raise RuntimeError('read_buffer: no forward yet')
-        ws, logits, n, H, W = self._last
-        lib = L.load()
-        dims = (C.c_int32 * 4)()
-        args = (self._h, int(index), ws.data_ptr(), logits.data_ptr() if logits is not None else None, n, H, W)
-        L.check(lib.sd_fcn_read_buffer(*args, None, dims, dv.stream(self.dev)), 'sd_fcn_read_buffer')
-        out = np.empty(tuple(dims), dtype=np.float32)
-        L.check(lib.sd_fcn_read_buffer(*args, out.ctypes.data_as(C.POINTER(C.c_float)), dims, dv.stream(self.dev)), 'sd_fcn_read_buffer')
-        return out
+        return self._read_buffer(index)
 
 
 def get_semseg_spiness_model(act_dtype: str = 'f16', n_class: int = 5):

@@ -1,7 +1,7 @@
-// Looks at an FCN plan without a GPU: builds it with sd_fcn_plan.cpp (+ sd_viewnet_plan.cpp for the storage conversions) alone and
-// prints every op's fields, the blob digest, and per geometry the shapes, the workspace layout and the multiply-adds per view.
+// Looks at an FCN plan without a GPU: builds it with sd_fcn_plan.cpp alone and prints every op's fields, the blob digest, and per
+// geometry the shapes, the workspace layout and the multiply-adds per view.
 //
-//   hipcc -O2 -std=c++17 syconn_amd/csrc/sd_fcn_plan.cpp syconn_amd/csrc/sd_viewnet_plan.cpp tools/fcn_plan_dump.cpp -o fcn_plan_dump
+//   hipcc -O2 -std=c++17 syconn_amd/csrc/sd_fcn_plan.cpp tools/fcn_plan_dump.cpp -o fcn_plan_dump
 //   fcn_plan_dump NET.bin [--dtypes f16,bf16] [--geom H,W[:n_planes]] ... [--unpack OUT.bin]
 //
 // NET.bin: "SDFCN01\0", int32 in_channels, dec_last, n_class, n_convs, block_len[5], int64 n_floats, n_convs x int32 output channels,
@@ -12,20 +12,12 @@
 // compared with rounding alone; "pad_nonzero" counts fragment / bias elements outside every real (c, n) that are not zero, "dup" the
 // weights found in more than one place or in none.
 #include "../syconn_amd/csrc/sd_fcn.h"
-#include "../syconn_amd/csrc/sd_viewnet.h"
 
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 
-using namespace sdfcn;
-
-static uint64_t fnv1a64(const void* p, size_t n) {
-    const unsigned char* b = static_cast<const unsigned char*>(p);
-    uint64_t h = 1469598103934665603ull;
-    for (size_t i = 0; i < n; ++i) { h ^= b[i]; h *= 1099511628211ull; }
-    return h;
-}
+using namespace sdfcn;      // (with sdnet: fnv1a64, from_storage)
 
 struct Geom { int h, w; size_t n; };
 
@@ -64,7 +56,7 @@ static void unpack(const Plan& p, std::vector<float>& out) {
                                 }
                                 const size_t idx = dec ? (((size_t)c * op.cout + n) * 3 + taps[t].ky) * 3 + taps[t].kx
                                                        : (((size_t)n * op.cin + c) * 3 + taps[t].ky) * 3 + taps[t].kx;
-                                w[idx] = sdvn::from_storage(v, dt);
+                                w[idx] = from_storage(v, dt);
                                 ++found[idx];
                             }
         }

@@ -15,14 +15,7 @@
 #include <cstdlib>
 #include <cstring>
 
-using namespace sdvn;
-
-static uint64_t fnv1a64(const void* p, size_t n) {
-    const unsigned char* b = static_cast<const unsigned char*>(p);
-    uint64_t h = 1469598103934665603ull;
-    for (size_t i = 0; i < n; ++i) { h ^= b[i]; h *= 1099511628211ull; }
-    return h;
-}
+using namespace sdvn;      // (with sdnet: fnv1a64, from_storage)
 
 struct Geom { int d, h, w; size_t n; };
 
