@@ -383,11 +383,11 @@ int sd_model_num_ops(const sd_model* m) { return m ? (int)m->n_ops() : 0; }
 int sd_debug_last_launch_count(const sd_model* m) { return m ? m->last_launches : 0; }
 int sd_debug_op_kernel(const sd_model* m, int op, char* buf, int n) {
     if (!m) return -1;
-    if (m->f32) {      // (the fp32 FMA plan keeps its own op list: one k32_* launch per op)
-        if (buf && n > 0) snprintf(buf, (size_t)n, "k32_* (fp32 FMA plan)");
+    if (op < 0 || op >= (int)m->n_ops()) return -1;
+    if (m->f32) {      // (the fp32 FMA plan keeps its own op list: every op launches its own k32_* kernel)
+        if (buf && n > 0) snprintf(buf, (size_t)n, "%s", f32_op_kernel(m->f32, op));
         return op;
     }
-    if (op < 0 || op >= (int)m->n_ops()) return -1;
     const int e = op < (int)m->op_exec.size() ? m->op_exec[op] : -1;
     if (buf && n > 0) {
         const char* name = (e >= 0 && e < (int)m->op_kernel.size() && m->op_kernel[e]) ? m->op_kernel[e] : "";

@@ -334,21 +334,26 @@ __global__ __launch_bounds__(256) void k32_final(const Final32 p) {
     }
 }
 
+// (`sym`: the instantiation that was launched, for sd_debug_op_kernel)
 template <int KZ, typename IN>
-int launch_conv32(const Conv32& q, int N, hipStream_t s) {
+int launch_conv32(const Conv32& q, int N, hipStream_t s, const char*& sym) {
     Conv32 p = q;
+    constexpr bool u8 = sizeof(IN) == 1;
     constexpr int CO = 16;
     const dim3 blk(256);
     const int ncob = (p.Cout + CO - 1) / CO;
     // block shape by the width of the layer: 64 / 32 / 16 columns (the deep levels of a tile are narrow)
     if (p.W > 40) {
         p.nbx = (p.W + 63) / 64; p.nby = (p.H + 15) / 16; p.nbz = p.D;
+        sym = KZ == 3 ? (u8 ? "k32_conv<3,1x16x16,uint8>" : "k32_conv<3,1x16x16,float>") : (u8 ? "k32_conv<1,1x16x16,uint8>" : "k32_conv<1,1x16x16,float>");
         k32_conv<KZ, 1, 16, 16, CO, IN><<<dim3(p.nbx * p.nby * p.nbz, ncob, N), blk, 0, s>>>(p);
     } else if (p.W > 20) {
         p.nbx = (p.W + 31) / 32; p.nby = (p.H + 15) / 16; p.nbz = (p.D + 1) / 2;
+        sym = KZ == 3 ? (u8 ? "k32_conv<3,2x16x8,uint8>" : "k32_conv<3,2x16x8,float>") : (u8 ? "k32_conv<1,2x16x8,uint8>" : "k32_conv<1,2x16x8,float>");
         k32_conv<KZ, 2, 16, 8, CO, IN><<<dim3(p.nbx * p.nby * p.nbz, ncob, N), blk, 0, s>>>(p);
     } else {
         p.nbx = (p.W + 15) / 16; p.nby = (p.H + 15) / 16; p.nbz = (p.D + 3) / 4;
+        sym = KZ == 3 ? (u8 ? "k32_conv<3,4x16x4,uint8>" : "k32_conv<3,4x16x4,float>") : (u8 ? "k32_conv<1,4x16x4,uint8>" : "k32_conv<1,4x16x4,float>");
         k32_conv<KZ, 4, 16, 4, CO, IN><<<dim3(p.nbx * p.nby * p.nbz, ncob, N), blk, 0, s>>>(p);
     }
     return hipGetLastError() == hipSuccess ? SD_OK : SD_ERR_HIP;
@@ -366,6 +371,7 @@ struct sd_f32_model {
     std::vector<Dims> dims;
     std::vector<size_t> buf_off;
     int final_cout = 0;
+    std::vector<const char*> op_kernel;      // per op: the kernel symbol(s) its last launch used (static strings)
 };
 
 namespace {
@@ -514,6 +520,9 @@ done:
 }
 
 int f32_final_cout(const sd_f32_model* m) { return m->final_cout; }
+const char* f32_op_kernel(const sd_f32_model* m, int op) {
+    return (op >= 0 && op < (int)m->op_kernel.size() && m->op_kernel[op]) ? m->op_kernel[op] : "";
+}
 int f32_buf_channels(const sd_f32_model* m, int b) { return (b >= 0 && b < m->nbuf) ? m->bufC[b] : 0; }
 
 size_t f32_workspace_bytes(sd_f32_model* m, int D, int H, int W) {
@@ -535,6 +544,7 @@ int f32_forward(sd_f32_model* m, const void* in_dev, int in_dtype, int N, int D,
     char* const wsb = reinterpret_cast<char*>(ws);
     auto bufp = [&](int b) { return reinterpret_cast<float*>(wsb + m->buf_off[b]); };
     auto fp = [&](size_t off) { return m->blob + off; };
+    m->op_kernel.assign(m->ops.size(), nullptr);
     for (size_t i = 0; i < m->ops.size(); ++i) {
         const FOp& op = m->ops[i];
         const sd_op_desc& d = op.d;
@@ -552,13 +562,14 @@ int f32_forward(sd_f32_model* m, const void* in_dev, int in_dtype, int N, int D,
             p.dst = bufp(d.dst); p.Cout = d.cout; p.D = o.d; p.H = o.h; p.W = o.w;
             p.w = fp(op.w_off); p.bias = fp(op.bias_off); p.alpha = fp(op.alpha_off); p.beta = fp(op.beta_off);
             p.relu = d.relu; p.tstride = tstride; p.in_tstride = in_tstride;
-            if (d.src0 == 0 && in_dtype == SD_U8) rc = d.kz == 3 ? launch_conv32<3, uint8_t>(p, N, s) : launch_conv32<1, uint8_t>(p, N, s);
-            else rc = d.kz == 3 ? launch_conv32<3, float>(p, N, s) : launch_conv32<1, float>(p, N, s);
+            if (d.src0 == 0 && in_dtype == SD_U8) rc = d.kz == 3 ? launch_conv32<3, uint8_t>(p, N, s, m->op_kernel[i]) : launch_conv32<1, uint8_t>(p, N, s, m->op_kernel[i]);
+            else rc = d.kz == 3 ? launch_conv32<3, float>(p, N, s, m->op_kernel[i]) : launch_conv32<1, float>(p, N, s, m->op_kernel[i]);
             break;
         }
         case SD_OP_POOL: {
             const Dims a = m->dims[d.src0], o = m->dims[d.dst];
             Pool32 p{bufp(d.src0), bufp(d.dst), m->bufC[d.src0], a.d, a.h, a.w, o.d, o.h, o.w, d.kz, tstride};
+            m->op_kernel[i] = "k32_pool";
             k32_pool<<<dim3(grid_for((size_t)p.C * o.d * o.h * o.w), 1, N), 256, 0, s>>>(p);
             break;
         }
@@ -569,6 +580,7 @@ int f32_forward(sd_f32_model* m, const void* in_dev, int in_dtype, int N, int D,
             p.w = fp(op.w_off); p.bias = fp(op.bias_off); p.alpha = fp(op.alpha_off); p.beta = fp(op.beta_off);
             p.relu = d.relu; p.ncob = op.ncob; p.tstride = tstride;
             const dim3 g((unsigned)(((size_t)a.d * a.h * a.w + 255) / 256), op.ncob, N);
+            m->op_kernel[i] = d.kz == 2 ? "k32_upconv<2>" : "k32_upconv<1>";
             if (d.kz == 2) k32_upconv<2><<<g, 256, 0, s>>>(p);
             else k32_upconv<1><<<g, 256, 0, s>>>(p);
             break;
@@ -585,6 +597,7 @@ int f32_forward(sd_f32_model* m, const void* in_dev, int in_dtype, int N, int D,
                 if (hipMemsetAsync(wsb + (size_t)t * tstride, 0, (size_t)2 * d.groups * sizeof(double), s) != hipSuccess)
                     return sd_fail_msg(SD_ERR_HIP, "hipMemsetAsync (GroupNorm sums)");
             const size_t per_group = (size_t)r.d * r.h * r.w * (p.C / d.groups);
+            m->op_kernel[i] = "k32_gn_stats + k32_gn_apply";
             k32_gn_stats<<<dim3((unsigned)std::min<size_t>((per_group + 4095) / 4096, 256), d.groups, N), 256, 0, s>>>(p);
             k32_gn_apply<<<dim3(grid_for((size_t)r.d * r.h * r.w * p.C), 1, N), 256, 0, s>>>(p);
             break;
@@ -596,6 +609,7 @@ int f32_forward(sd_f32_model* m, const void* in_dev, int in_dtype, int N, int D,
             p.src = bufp(d.src0); p.Cin = d.cin0; p.w = fp(op.w_off); p.bias = fp(op.bias_off); p.cout = d.cout;
             p.out = out_dev; p.out_kind = out_kind; p.nvox = (size_t)D * H * W; p.tstride = tstride; p.out_tstride = out_tstride;
             if (lab) p.lab = *lab;
+            m->op_kernel[i] = "k32_final";
             k32_final<<<dim3(grid_for(p.nvox), 1, N), 256, 0, s>>>(p);
             break;
         }

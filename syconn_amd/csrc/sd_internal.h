@@ -226,6 +226,7 @@ int f32_model_create(const sd_op_desc* ops, int n_ops, const float* W, size_t n_
 void f32_model_destroy(sd_f32_model* m);
 int f32_final_cout(const sd_f32_model* m);
 int f32_buf_channels(const sd_f32_model* m, int b);
+const char* f32_op_kernel(const sd_f32_model* m, int op);      // symbol(s) op's launch of the last forward used ("" before one)
 size_t f32_workspace_bytes(sd_f32_model* m, int D, int H, int W);
 int f32_forward(sd_f32_model* m, const void* in_dev, int in_dtype, int N, int D, int H, int W, void* out_dev, int out_kind,
                 const LabelArgs* lab, void* ws, size_t ws_bytes, hipStream_t s, hipEvent_t* ev);

@@ -1462,11 +1462,12 @@ static int launch_upconv_t(const UpconvParams& p, int NB, hipStream_t s) {
 }
 int launch_upconv(const UpconvParams& p, int act_dtype, int NB, hipStream_t s) {
     if (act_dtype == SD_F16X2) {      // split-fp16 plan: row kernel for the full-resolution shapes, else the generic kernel (3n virtual chunks)
-        SD_NOTE_KERNEL(p.nchunk == 12 || p.nchunk == 24 || p.nchunk == 18 || p.nchunk == 36 || p.nchunk == 48 ? "k_upconv_rows<split-fp16> / k_upconv_mfma<split-fp16>" : "k_upconv_mfma<split-fp16>");
+        SD_NOTE_KERNEL("k_upconv_mfma<split-fp16>");      // (every row-kernel branch below notes the form it launches)
         const long M = (long)p.D * p.H * p.W;
         if (M >= (1l << 31) || p.gn) return SD_ERR_INVALID;
         static const bool no_rows = getenv("SD_SPLIT_NO_ROWS") != nullptr;      // A/B switch
         if (!no_rows && p.nchunk == 12 && p.Cd == 32 && getenv("SD_SPLIT_ROWS32_NO_WL")) {       // 64 -> 32 channels (level 0), weights from L2
+            SD_NOTE_KERNEL("k_upconv_rows<split-fp16,NCH=4,NTAB=2>");
             dim3 grid((unsigned)((M + 127) / 128), 1, p.batch), block(256);
             hipLaunchKernelGGL((k_upconv_rows<f16_t, 4, 2, false, false, true>), grid, block, 4 * 32 * 64 * 2, s, p);
             return SD_LAUNCH_CHECK();
@@ -1486,9 +1487,12 @@ int launch_upconv(const UpconvParams& p, int act_dtype, int NB, hipStream_t s) {
         };
         // 64 -> 32 channels (level 0) with the weights in LDS as well: without them every wave fetched 24 KiB of weight fragments from L2
         // per 32 input voxels and y-tap, three times the 8 KiB it writes (SD_SPLIT_ROWS32_NO_WL: the round-4 form, A/B)
-        if (!no_rows && p.nchunk == 12 && p.Cd == 32 && !getenv("SD_SPLIT_ROWS32_NO_WL"))
+        if (!no_rows && p.nchunk == 12 && p.Cd == 32 && !getenv("SD_SPLIT_ROWS32_NO_WL")) {
+            SD_NOTE_KERNEL("k_upconv_rows<split-fp16,NCH=4,NTAB=2,LDS weights>");
             return rows_wl(k_upconv_rows<f16_t, 4, 2, true, false, true>, 2, 12);
+        }
         if (!no_rows && p.nchunk == 48 && p.Cd == 128 && M * p.batch >= 98304 && !getenv("SD_SPLIT_UPCONV128_MFMA")) {      // 256 -> 128: four channel groups of 32 (96 KiB of weights each)
+            SD_NOTE_KERNEL("k_upconv_rows<split-fp16,NCH=16,NTAB=8,LDS weights,G=4>");
             auto kern = k_upconv_rows<f16_t, 16, 8, true, false, true, 4>;
             const size_t lds = (size_t)4 * 32 * 128 + (size_t)2 * 48 * 1024;
             if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
@@ -1498,11 +1502,18 @@ int launch_upconv(const UpconvParams& p, int act_dtype, int NB, hipStream_t s) {
             hipLaunchKernelGGL(kern, grid, block, lds, s, p);
             return SD_LAUNCH_CHECK();
         }
-        if (!no_rows && p.nchunk == 24 && p.Cd == 64) return rows_wl(k_upconv_rows<f16_t, 8, 4, true, false, true>, 4, 24);     // 128 -> 64
-        if (!no_rows && p.nchunk == 18 && p.Cd == 48) return rows_wl(k_upconv_rows<f16_t, 6, 3, true, false, true>, 3, 18);     // 96 -> 48
+        if (!no_rows && p.nchunk == 24 && p.Cd == 64) {      // 128 -> 64
+            SD_NOTE_KERNEL("k_upconv_rows<split-fp16,NCH=8,NTAB=4,LDS weights>");
+            return rows_wl(k_upconv_rows<f16_t, 8, 4, true, false, true>, 4, 24);
+        }
+        if (!no_rows && p.nchunk == 18 && p.Cd == 48) {      // 96 -> 48
+            SD_NOTE_KERNEL("k_upconv_rows<split-fp16,NCH=6,NTAB=3,LDS weights>");
+            return rows_wl(k_upconv_rows<f16_t, 6, 3, true, false, true>, 3, 18);
+        }
         // 192 -> 96 channels: the 36 weight groups of all six column tiles do not fit the LDS; three workgroups per tap pair with the
         // two tiles of 32 channels each (k_upconv_rows<G = 3>: 72 KiB of weights + 16 KiB of transpose tiles)
         if (!no_rows && p.nchunk == 36 && p.Cd == 96 && !getenv("SD_SPLIT_NO_ROWS96") && !getenv("SD_SPLIT_ROWS96_L2")) {
+            SD_NOTE_KERNEL("k_upconv_rows<split-fp16,NCH=12,NTAB=6,LDS weights,G=3>");
             auto kern = k_upconv_rows<f16_t, 12, 6, true, false, true, 3>;
             const size_t lds = (size_t)4 * 32 * 128 + (size_t)2 * 36 * 1024;
             if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
@@ -1515,6 +1526,7 @@ int launch_upconv(const UpconvParams& p, int act_dtype, int NB, hipStream_t s) {
         }
         // (SD_SPLIT_ROWS96_L2: the round-4 form of that shape, weights from L2 -- A/B)
         if (!no_rows && p.nchunk == 36 && p.Cd == 96 && !getenv("SD_SPLIT_NO_ROWS96")) {
+            SD_NOTE_KERNEL("k_upconv_rows<split-fp16,NCH=12,NTAB=6>");
             auto kern = k_upconv_rows<f16_t, 12, 6, false, false, true>;
             const size_t lds = (size_t)4 * 32 * 64 * 6;
             if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
