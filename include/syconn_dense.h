@@ -15,6 +15,10 @@
  *     loop (prediction.py:783-794) keeps working.
  *   - all device buffers are CALLER-OWNED (the host framework's allocator); the library owns only the packed
  *     weights inside an sd_model.  Pointers are plain device addresses, sizes are bytes / elements as stated.
+ *   - outputs, tables, `temp_dev` and workspaces need not be initialised by the caller: whatever an entry reads of
+ *     them it has written in the same call (counts_dev / status / flag words included), so their previous bytes never
+ *     reach a result.  The exceptions are stated at their entries: the per-dataset cursors and record arrays that
+ *     the caller zeroes once before the first chunk (sd_chunkprops_append / sd_chunkpairs_append, sd_cs_syntype_records).
  *   - every launch is asynchronous on `stream` (a hipStream_t passed as void*; NULL = default stream); the caller
  *     synchronises.  A handle is bound to one device and is not thread-safe.
  *   - volumes are z,y,x (x fastest).  Network input is one channel, planar.  Network output is planar

@@ -9,6 +9,7 @@ import torch
 from syconn_amd import _lib as L
 
 GUARD = 4096
+FILL = 0xCD  # what every output and the usable scratch hold before a call (tests/test_gpu_buffer_state.py sets 0x00 / 0xFF)
 
 
 def _up(a, dev, dtype):
@@ -18,8 +19,17 @@ def _up(a, dev, dtype):
 
 def _scratch(dev, need, shrink=0):
     t = torch.empty(need + GUARD, dtype=torch.uint8, device=dev)
+    t[:need] = FILL
     t[need:] = 0xA5
     return t, max(need - shrink, 0)
+
+
+def _out(dev, shape, dtype):
+    """An output of `shape` (first extent at least 1) whose every byte is FILL."""
+    shape = shape if isinstance(shape, tuple) else (shape,)
+    t = torch.empty((max(shape[0], 1),) + shape[1:], dtype=dtype, device=dev)
+    t.view(torch.uint8).fill_(FILL)
+    return t
 
 
 def _intact(t, need):
@@ -42,9 +52,9 @@ def components(dev, edges, tab, scaling, min_cc_size, strict=True, shrink=0):
     lib = L.load()
     e = _up(np.asarray(edges, np.uint64).reshape(-1, 2), dev, np.uint64)
     n_e, m = len(e), tab['n'] + 2 * len(e)
-    i64 = lambda k: torch.zeros(max(k, 1), dtype=torch.int64, device=dev)
+    i64 = lambda k: _out(dev, k, torch.int64)
     node_ids, node_comp, ssv_ids, sv_begin, sv_ids, edges_out = i64(m), i64(m), i64(m), i64(m + 1), i64(m), i64(2 * n_e)
-    node_size = torch.zeros(max(m, 1), dtype=torch.float64, device=dev)
+    node_size = _out(dev, m, torch.float64)
     counts = torch.zeros(8, dtype=torch.int64, device=dev)
     need = lib.sd_svgraph_components_temp_bytes(tab['n'], n_e)
     tmp, told = _scratch(dev, need, shrink)
@@ -67,9 +77,9 @@ def props(dev, sv_begin, sv_ids, tab):
     lib = L.load()
     n = len(sv_begin) - 1
     sb, sv = _up(sv_begin, dev, np.int64), _up(sv_ids, dev, np.uint64)
-    size = torch.zeros(max(n, 1), dtype=torch.int64, device=dev)
-    box = torch.zeros((max(n, 1), 6), dtype=torch.int32, device=dev)
-    rep = torch.zeros((max(n, 1), 3), dtype=torch.int32, device=dev)
+    size = _out(dev, n, torch.int64)
+    box = _out(dev, (n, 6), torch.int32)
+    rep = _out(dev, (n, 3), torch.int32)
     counts = torch.zeros(8, dtype=torch.int64, device=dev)
     rc = lib.sd_cell_props(sb.data_ptr(), sv.data_ptr(), n, len(sv_ids), tab['ids'].data_ptr(), tab['sizes'].data_ptr(), tab['rep'].data_ptr(),
                            tab['box_begin'].data_ptr(), tab['boxes'].data_ptr(), tab['n'], tab['n_boxes'], size.data_ptr(), box.data_ptr(), rep.data_ptr(),
@@ -84,11 +94,11 @@ def mapping(dev, sv_begin, sv_ids, rec_sub, rec_sv, rec_count, org_ids, org_size
     r, o, n, s = len(rec_sub), len(org_ids), len(sv_begin) - 1, len(sv_ids)
     d = [_up(a, dev, t) for a, t in ((rec_sub, np.uint64), (rec_sv, np.uint64), (rec_count, np.int64), (org_ids, np.uint64), (org_sizes, np.int64),
                                      (sv_begin, np.int64), (sv_ids, np.uint64))]
-    i64 = lambda k: torch.zeros(max(k, 1), dtype=torch.int64, device=dev)
+    i64 = lambda k: _out(dev, k, torch.int64)
     cell_begin, pair_org, acc_begin, acc_org = i64(n + 1), i64(r), i64(n + 1), i64(r)
-    ratio = torch.zeros(max(r, 1), dtype=torch.float64, device=dev)
-    accepted = torch.zeros(max(r, 1), dtype=torch.uint8, device=dev)
-    org_n, org_first = (torch.zeros(max(o, 1), dtype=torch.int32, device=dev) for _ in range(2))
+    ratio = _out(dev, r, torch.float64)
+    accepted = _out(dev, r, torch.uint8)
+    org_n, org_first = (_out(dev, o, torch.int32) for _ in range(2))
     counts = torch.zeros(8, dtype=torch.int64, device=dev)
     need = lib.sd_cell_mapping_temp_bytes(r, s)
     tmp, told = _scratch(dev, need, shrink)
@@ -110,8 +120,8 @@ def synapses(dev, ssv_ids, partners, keep, syn_ids, shrink=0):
     lib = L.load()
     n, n_cells = len(syn_ids), len(ssv_ids)
     d = [_up(a, dev, t) for a, t in ((np.asarray(partners).reshape(-1, 2), np.uint64), (keep, np.uint8), (syn_ids, np.uint64), (ssv_ids, np.uint64))]
-    begin = torch.zeros(n_cells + 1, dtype=torch.int64, device=dev)
-    out = torch.zeros(max(2 * n, 1), dtype=torch.int64, device=dev)
+    begin = _out(dev, n_cells + 1, torch.int64)
+    out = _out(dev, 2 * n, torch.int64)
     counts = torch.zeros(8, dtype=torch.int64, device=dev)
     need = lib.sd_cell_synapses_temp_bytes(n)
     tmp, told = _scratch(dev, need, shrink)

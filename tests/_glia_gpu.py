@@ -7,6 +7,7 @@ import torch
 from syconn_amd import _lib as L
 
 GUARD = 4096
+FILL = 0xCD  # what the usable bytes of every output and scratch hold before a call (tests/test_gpu_buffer_state.py sets 0x00 / 0xFF)
 U = np.uint64
 
 
@@ -16,13 +17,13 @@ def _up(a, dev, dtype):
 
 
 class Guarded:
-    """`n` items of `dtype` followed by GUARD bytes of 0xA5 (all in one uint8 buffer)."""
+    """`n` items of `dtype` holding FILL bytes, followed by GUARD bytes of 0xA5 (all in one uint8 buffer)."""
 
     def __init__(self, dev, n, dtype):
         self.bytes = int(n) * np.dtype(dtype).itemsize
         self.dtype = dtype
         self.t = torch.empty(self.bytes + GUARD, dtype=torch.uint8, device=dev)
-        self.t[:self.bytes] = 0
+        self.t[:self.bytes] = FILL
         self.t[self.bytes:] = 0xA5
 
     def ptr(self):

@@ -69,6 +69,7 @@ def abi_merge(gpu, chunks, min_cs, min_syn, cap_cs=None, cap_syn=None, cap_vox=N
     n_cs, n_syn, n_vox = (int(x) for x in cur)
     need = lib.sd_cs_merge_temp_bytes(max(n_cs, n_syn, 1))
     guarded = torch.empty(need + 4096, dtype=torch.uint8, device=gpu)
+    guarded[:need] = 0xCD
     guarded[need:] = 0xA5
     tmp = guarded[:need]                                        # the merges are told `need` bytes and may touch no more
     new = lambda n, w, dt: torch.full((max(n, 1), w) if w > 1 else (max(n, 1),), -1, dtype=dt, device=gpu)

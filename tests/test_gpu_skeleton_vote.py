@@ -228,20 +228,20 @@ def test_edge_outside_its_cell_sets_the_error_slot(gpu):
     e_d, eb_d, nb_d, w_d = up(edges, np.int64), up([0, 2, 5], np.int64), up([0, 3, 6], np.int64), up(np.ones(5), np.float64)
     adj_begin, adj_nbr, adj_w = (torch.zeros(k, dtype=t, device=gpu) for k, t in ((7, torch.int64), (10, torch.int32), (10, torch.float64)))
     counts = torch.zeros(8, dtype=torch.int64, device=gpu)
-    tmp = torch.empty(lib.sd_skel_csr_temp_bytes(5), dtype=torch.uint8, device=gpu)
+    tmp = torch.empty(lib.sd_skel_csr_temp_bytes(5), dtype=torch.uint8, device=gpu).fill_(0xCD)
     L.check(lib.sd_skel_csr(e_d.data_ptr(), eb_d.data_ptr(), nb_d.data_ptr(), 2, 6, 5, w_d.data_ptr(), adj_begin.data_ptr(), adj_nbr.data_ptr(),
                             adj_w.data_ptr(), counts.data_ptr(), tmp.data_ptr(), tmp.numel(), stream), 'sd_skel_csr')
     assert int(counts.cpu()[7]) != 0
     assert adj_begin.cpu().tolist() == [0, 1, 3, 4, 5, 6, 6] and adj_nbr.cpu().tolist()[:6] == [1, 0, 2, 1, 1, 0]
     cls = up([0, 1, 1, 1, 0, 0], np.uint8)
     vote, reached = torch.zeros(6, dtype=torch.uint8, device=gpu), torch.zeros(6, dtype=torch.int32, device=gpu)
-    tmp = torch.empty(lib.sd_skel_vote_temp_bytes(6, 3), dtype=torch.uint8, device=gpu)
+    tmp = torch.empty(lib.sd_skel_vote_temp_bytes(6, 3), dtype=torch.uint8, device=gpu).fill_(0xCD)
     L.check(lib.sd_skel_vote(adj_begin.data_ptr(), adj_nbr.data_ptr(), adj_w.data_ptr(), 10, nb_d.data_ptr(), 2, 6, 3, cls.data_ptr(), 2, 5.0,
                              vote.data_ptr(), reached.data_ptr(), counts.data_ptr(), tmp.data_ptr(), tmp.numel(), stream), 'sd_skel_vote')
     assert int(counts.cpu()[7]) == 0 and reached.cpu().tolist() == [3, 3, 3, 2, 2, 1] and vote.cpu().tolist() == [1, 1, 1, 0, 0, 0]
     # the components ignore the same edges and say so
     out = torch.zeros(6, dtype=torch.uint8, device=gpu)
-    tmp = torch.empty(lib.sd_skel_components_temp_bytes(6), dtype=torch.uint8, device=gpu)
+    tmp = torch.empty(lib.sd_skel_components_temp_bytes(6), dtype=torch.uint8, device=gpu).fill_(0xCD)
     L.check(lib.sd_skel_components(e_d.data_ptr(), eb_d.data_ptr(), nb_d.data_ptr(), 2, 6, 5, cls.data_ptr(), -1, 1, 0, out.data_ptr(), counts.data_ptr(),
                                    tmp.data_ptr(), tmp.numel(), stream), 'sd_skel_components')
     assert int(counts.cpu()[7]) != 0 and out.cpu().tolist() == [1, 1, 1, 0, 0, 0]

@@ -172,6 +172,7 @@ def test_random_groups_against_restatement(gpu, seed, scale, gap, extent, coord0
     assert n_vox in (None, agg.n)
     need = agg.tmp.numel()
     guarded = torch.empty(need + 4096, dtype=torch.uint8, device=gpu)
+    guarded[:need] = 0xCD
     guarded[need:] = 0xA5
     agg.tmp = guarded[:need]
     agg.components()

@@ -86,6 +86,7 @@ def guarded_run(gpu, syn, tab, scaling, R, D, f):
 
     def guard(need):
         g = torch.empty(need + 4096, dtype=torch.uint8, device=gpu)
+        g[:need] = 0xCD
         g[need:] = 0xA5
         return g
     gp = guard(mapper.pair_tmp.numel())

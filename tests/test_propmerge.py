@@ -141,6 +141,7 @@ def test_propmerge_kernels_against_numpy(gpu, n, n_ids, seed):
     bbs, cnt = torch.empty((n, 6), dtype=torch.int32, device=gpu), torch.zeros(1, dtype=torch.int64, device=gpu)
     tb = lib.sd_propmerge_temp_bytes(n)
     tmp = torch.empty(tb + 4096, dtype=torch.uint8, device=gpu)
+    tmp[:tb] = 0xCD
     tmp[tb:] = 0xA5
     st = torch.cuda.current_stream().cuda_stream
     L.check(lib.sd_propmerge_objects(d_ids.data_ptr(), d_sz.data_ptr(), d_rc.data_ptr(), d_bb.data_ptr(), n, uniq.data_ptr(), tot.data_ptr(),
