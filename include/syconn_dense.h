@@ -1141,6 +1141,88 @@ int sd_fcn_num_ops(sd_fcn* m);
 int sd_glia_view_probas(const float* logits_dev, size_t n, float* probas_dev, int32_t* flag_dev, void* stream);
 int sd_views_center_component(const uint8_t* in_dev, size_t n_planes, int H, int W, int background, uint8_t* out_dev, void* stream);
 
+/* ---- cell skeletons from a labelled chunk: TEASAR tracing (csrc/sd_skeletonize.hip) -----------------------------------------------
+ * What proc/skeleton.py:21-86 (kimimaro_skelgen) gets from kimimaro.skeletonize, per chunk and for all cells at once.  kimimaro is not in
+ * the reference tree: the rules are this build's, and the device equals their CPU restatement bit for bit.  Volumes
+ * are (X, Y, Z) with z fastest, extents 1 .. SD_SKELETONIZE_MAX_EXTENT, fewer than 2^31 voxels; the raster index of a voxel is
+ * (x Y + y) Z + z.  anisotropy_xyz: three integers 1 .. SD_SKELETONIZE_MAX_ANISOTROPY (nm per voxel; proc/skeleton.py:21-86 passes
+ * kd.scales[0] * ds).  Tables per component are indexed by the component number c = 1 .. n_comp (entry 0 unused), so they hold n_comp + 1
+ * entries.  Everything is asynchronous on the stream; argument errors are SD_ERR_INVALID with sd_last_error.  All entries with a
+ * temp_dev take the scratch of sd_skeletonize_temp_bytes(X, Y, Z); it carries the dirty-tile state from sd_skeletonize_field_start /
+ * sd_skeletonize_round to sd_skeletonize_relax, so the chain of one chunk uses one scratch.  counts_dev uint64[8].
+ *   sd_skeletonize_components  (proc/skeleton.py:21-86, the cc3d step inside kimimaro) comp_dev int32: the 26-connected components of equal
+ *                        non-zero label of seg_dev uint64, numbered 1 .. N in raster order of their first voxel; components with fewer
+ *                        than dust_threshold voxels are 0 and take no number.  sizes_dev / labels_dev uint64[max_comps + 1], first_dev
+ *                        int32[max_comps + 1] (first voxel).  counts[0] = N; [7] != 0: N > max_comps (the rest is numbered 0).
+ *   sd_skeletonize_d2    (proc/skeleton.py:21-86, the edt step) d2_dev uint64 = min over voxels q of the array whose component number
+ *                        differs (0 included) of sum_a (w_a (v_a - q_a))^2, 0 outside the components; the array border is no boundary.
+ *                        dbf_dev float32 = float32(sqrt(double(d2))), dbf_max_dev float32[n_comp + 1] its maximum per component.
+ *                        counts[1] != 0: a component has no differing voxel in the array (its d2 is 2^64 - 1, its dbf +inf).
+ *   sd_skeletonize_field_start  (proc/skeleton.py:21-86, the dijkstra3d fields) field_dev (float32, or float64 with field_f64 = 1) = +inf,
+ *                        0 at source_dev[c] (int32[n_comp + 1], < 0: none) of every component; marks the tiles around the sources.
+ *   sd_skeletonize_relax (proc/skeleton.py:21-86) up to max_sweeps (rounded up to a multiple of 6, at most SD_SKELETONIZE_MAX_SWEEPS)
+ *                        sweeps towards the fixed point of field(v) = min over the 26 same-component neighbours u of
+ *                        fl(field(u) + cost): penalty_dev == NULL: float32 field, cost = float32(sqrt(double(sum (w_a o_a)^2))) of the
+ *                        offset; else float64 field, cost = penalty_dev[v].  A sweep is one launch over the dirty tiles of edge
+ *                        SD_SKELETONIZE_TILE, each relaxed to local convergence in LDS; a launch without dirty tiles returns at once.
+ *                        counts[3] = dirty tiles left (0: converged; otherwise call again, the field continues from its values),
+ *                        [4] += sweeps that had work, [5] += tiles relaxed, [6] != 0: a tile passed its local bound of
+ *                        SD_SKELETONIZE_TILE^3 + 1 steps.  The caller bounds the sweeps by the foreground voxels + 1.
+ *   sd_skeletonize_argmax  (proc/skeleton.py:21-86, root and target selection) index_dev int32[n_comp + 1] = the voxel with the largest
+ *                        field_dev value (float32, >= 0) per component among those with valid_dev != 0 (NULL: all), the smallest raster
+ *                        index on ties, -1 without one; value_dev float32[n_comp + 1] (may be NULL); keys_dev uint64[n_comp + 1] scratch.
+ *   sd_skeletonize_penalty  (proc/skeleton.py:21-86, the PDRF) penalty_dev float64 = pdrf_scale (1 - double(dbf) / m_dev[c])^e +
+ *                        double(daf) / double(daf_max_dev[c]) (the second term 0 where daf_max is 0), e = 1 .. SD_SKELETONIZE_MAX_EXPONENT
+ *                        by e - 1 multiplications, every operation rounded once.  m_dev float64[n_comp + 1] is the caller's dbf_max ** 1.01.
+ *   sd_skeletonize_round (proc/skeleton.py:21-86, one path with fix_branching) per component that is not void: walk from target_dev[c]
+ *                        (< 0: none) by parent steps -- the same-component neighbour with the smallest dist_dev, the smallest raster
+ *                        index on ties -- to the first voxel with dist == 0; the walked voxels get parent_dev (int32, -1 before), dist 0,
+ *                        and clear valid_dev (uint8) for the voxels u of their component with |u_a - v_a| <= floor(double(r) / w_a),
+ *                        r = fl32(fl32(inv_scale dbf(v)) + inv_const).  root_dev (int32[n_comp + 1]; NULL after the first round) joins
+ *                        the new nodes with parent = itself.  The new sources' tiles are marked: sd_skeletonize_relax on dist follows.
+ *                        counts[1] != 0: a walk passed sizes_dev[c] steps, [2] += walks whose step did not lower dist (float64
+ *                        absorption); both set void_dev[c] (int32[n_comp + 1], zeroed by the caller), which empties c's result.
+ *   sd_skeletonize_emit  (proc/skeleton.py:21-86, the skeleton of every component) nodes = voxels with parent >= 0 of components that
+ *                        are not void, by component and ascending raster index: node_begin_dev / edge_begin_dev uint64[n_comp + 2]
+ *                        (entry c .. c + 1 bounds component c), node_voxel_dev int32[max_nodes], vertices_dev float32[max_nodes][3] =
+ *                        float32(voxel w), radii_dev float32 = dbf, edges_dev int32[max_nodes][2] = (node, parent) as indices inside the
+ *                        component, one per node that is not the root, in node order.  counts[0] = nodes needed; above max_nodes
+ *                        only the two offset tables are written (and mean nothing).  Further scratch: sd_skeletonize_emit_temp_bytes.
+ * One grid stride: SD_SKELETONIZE_VOX_GRID blocks of 256 voxels, SD_SKELETONIZE_TILE_GRID tiles, SD_SKELETONIZE_COMP_GRID blocks of 256
+ * components, SD_SKELETONIZE_NODE_GRID blocks (one new node each, or 256 table rows).  None of the constants rests on a measurement. */
+#define SD_SKELETONIZE_TILE 16
+#define SD_SKELETONIZE_MAX_EXTENT 2048
+#define SD_SKELETONIZE_MAX_ANISOTROPY 32768
+#define SD_SKELETONIZE_MAX_EXPONENT 64
+#define SD_SKELETONIZE_MAX_SWEEPS 1536
+#define SD_SKELETONIZE_VOX_GRID 8192
+#define SD_SKELETONIZE_TILE_GRID 2048
+#define SD_SKELETONIZE_COMP_GRID 1024
+#define SD_SKELETONIZE_NODE_GRID 2048
+size_t sd_skeletonize_temp_bytes(int X, int Y, int Z);
+int sd_skeletonize_components(const uint64_t* seg_dev, int X, int Y, int Z, uint64_t dust_threshold, int32_t* comp_dev, uint64_t* sizes_dev,
+                              uint64_t* labels_dev, int32_t* first_dev, size_t max_comps, uint64_t* counts_dev, void* temp_dev, size_t temp_bytes,
+                              void* stream);
+int sd_skeletonize_d2(const int32_t* comp_dev, int X, int Y, int Z, const int32_t* anisotropy_xyz, size_t n_comp, uint64_t* d2_dev, float* dbf_dev,
+                      float* dbf_max_dev, uint64_t* counts_dev, void* temp_dev, size_t temp_bytes, void* stream);
+int sd_skeletonize_field_start(const int32_t* comp_dev, int X, int Y, int Z, const int32_t* source_dev, size_t n_comp, void* field_dev, int field_f64,
+                               void* temp_dev, size_t temp_bytes, void* stream);
+int sd_skeletonize_relax(const int32_t* comp_dev, int X, int Y, int Z, const int32_t* anisotropy_xyz, void* field_dev, const double* penalty_dev,
+                         int max_sweeps, uint64_t* counts_dev, void* temp_dev, size_t temp_bytes, void* stream);
+int sd_skeletonize_argmax(const int32_t* comp_dev, const float* field_dev, const uint8_t* valid_dev, size_t n_vox, size_t n_comp, int32_t* index_dev,
+                          float* value_dev, uint64_t* keys_dev, void* stream);
+int sd_skeletonize_penalty(const int32_t* comp_dev, const float* dbf_dev, const float* daf_dev, size_t n_vox, size_t n_comp, const double* m_dev,
+                           const float* daf_max_dev, double pdrf_scale, int pdrf_exponent, double* penalty_dev, void* stream);
+int sd_skeletonize_round(const int32_t* comp_dev, int X, int Y, int Z, const int32_t* anisotropy_xyz, const float* dbf_dev, double* dist_dev,
+                         uint8_t* valid_dev, int32_t* parent_dev, const int32_t* target_dev, const int32_t* root_dev, const uint64_t* sizes_dev,
+                         size_t n_comp, float inv_scale, float inv_const, int32_t* void_dev, uint64_t* counts_dev, void* temp_dev, size_t temp_bytes,
+                         void* stream);
+size_t sd_skeletonize_emit_temp_bytes(size_t max_nodes);
+int sd_skeletonize_emit(const int32_t* comp_dev, int X, int Y, int Z, const int32_t* anisotropy_xyz, const int32_t* parent_dev, const float* dbf_dev,
+                        const int32_t* root_dev, const int32_t* void_dev, size_t n_comp, size_t max_nodes, uint64_t* node_begin_dev,
+                        uint64_t* edge_begin_dev, int32_t* node_voxel_dev, float* vertices_dev, float* radii_dev, int32_t* edges_dev,
+                        uint64_t* counts_dev, void* temp_dev, size_t temp_bytes, void* emit_temp_dev, size_t emit_temp_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

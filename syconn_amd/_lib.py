@@ -24,6 +24,8 @@ SD_VIEWS_GRID, SD_VIEWS_RASTER_GRID, SD_VIEWS_MAX_VIEWS, SD_VIEWS_TILE_PX = 1024
 SD_LOCATIONS_GRID, SD_LOCATIONS_WAVE_GRID, SD_LOCATIONS_MAX_CELLS = 1024, 4096, 1 << 21
 SD_VIEWNET_GRID, SD_VIEWNET_HEAD_GRID, SD_VIEWNET_HEAD_TILE_GRID = 2048, 32, 1024
 SD_GLIA_VIEWS_GRID, SD_GLIA_VIEWS_LDS_BYTES = 1024, 163840
+SD_SKELETONIZE_TILE, SD_SKELETONIZE_MAX_EXTENT, SD_SKELETONIZE_MAX_ANISOTROPY, SD_SKELETONIZE_MAX_EXPONENT, SD_SKELETONIZE_MAX_SWEEPS = 16, 2048, 32768, 64, 1536
+SD_SKELETONIZE_VOX_GRID, SD_SKELETONIZE_TILE_GRID, SD_SKELETONIZE_COMP_GRID, SD_SKELETONIZE_NODE_GRID = 8192, 2048, 1024, 2048
 
 LIB_NAME = 'libsyconn_dense_hip.so'
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), os.environ.get('SD_LIB_NAME', LIB_NAME))
@@ -57,7 +59,9 @@ EXPORTS = ['sd_init', 'sd_device_count', 'sd_model_create', 'sd_model_destroy', 
            'sd_viewnet_overflow', 'sd_viewnet_read_buffer', 'sd_viewnet_num_ops', 'sd_viewnet_embed', 'sd_viewnet_embed_timed',
            'sd_viewnet_embed_tile_samples', 'sd_fcn_create', 'sd_fcn_destroy', 'sd_fcn_workspace_bytes',
            'sd_fcn_forward', 'sd_fcn_forward_timed', 'sd_fcn_overflow', 'sd_fcn_read_buffer', 'sd_fcn_num_ops',
-           'sd_glia_view_probas', 'sd_views_center_component']
+           'sd_glia_view_probas', 'sd_views_center_component', 'sd_skeletonize_temp_bytes', 'sd_skeletonize_components', 'sd_skeletonize_d2',
+           'sd_skeletonize_field_start', 'sd_skeletonize_relax', 'sd_skeletonize_argmax', 'sd_skeletonize_penalty', 'sd_skeletonize_round',
+           'sd_skeletonize_emit_temp_bytes', 'sd_skeletonize_emit']
 
 
 class OpDesc(C.Structure):
@@ -300,6 +304,17 @@ def load():
     # handler/prediction.py:978-982 (get_glia_model_e3: the probabilities), proc/image.py:125-144 (single_conn_comp_img)
     lib.sd_glia_view_probas.argtypes = [vp, sz, vp, vp, vp]; lib.sd_glia_view_probas.restype = i32
     lib.sd_views_center_component.argtypes = [vp, sz, i32, i32, i32, vp, vp]; lib.sd_views_center_component.restype = i32
+    # proc/skeleton.py:21-86 (kimimaro_skelgen: the TEASAR tracing of a labelled chunk, stage by stage)
+    lib.sd_skeletonize_temp_bytes.argtypes = [i32, i32, i32]; lib.sd_skeletonize_temp_bytes.restype = sz
+    lib.sd_skeletonize_components.argtypes = [vp, i32, i32, i32, C.c_uint64, vp, vp, vp, vp, sz, vp, vp, sz, vp]; lib.sd_skeletonize_components.restype = i32
+    lib.sd_skeletonize_d2.argtypes = [vp, i32, i32, i32, i32p, sz, vp, vp, vp, vp, vp, sz, vp]; lib.sd_skeletonize_d2.restype = i32
+    lib.sd_skeletonize_field_start.argtypes = [vp, i32, i32, i32, vp, sz, vp, i32, vp, sz, vp]; lib.sd_skeletonize_field_start.restype = i32
+    lib.sd_skeletonize_relax.argtypes = [vp, i32, i32, i32, i32p, vp, vp, i32, vp, vp, sz, vp]; lib.sd_skeletonize_relax.restype = i32
+    lib.sd_skeletonize_argmax.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp]; lib.sd_skeletonize_argmax.restype = i32
+    lib.sd_skeletonize_penalty.argtypes = [vp, vp, vp, sz, sz, vp, vp, f64, i32, vp, vp]; lib.sd_skeletonize_penalty.restype = i32
+    lib.sd_skeletonize_round.argtypes = [vp, i32, i32, i32, i32p, vp, vp, vp, vp, vp, vp, vp, sz, f32, f32, vp, vp, vp, sz, vp]; lib.sd_skeletonize_round.restype = i32
+    lib.sd_skeletonize_emit_temp_bytes.argtypes = [sz]; lib.sd_skeletonize_emit_temp_bytes.restype = sz
+    lib.sd_skeletonize_emit.argtypes = [vp, i32, i32, i32, i32p, vp, vp, vp, vp, sz, sz] + [vp] * 7 + [vp, sz, vp, sz, vp]; lib.sd_skeletonize_emit.restype = i32
     _lib = lib
     return lib
 

@@ -121,6 +121,8 @@ DEFAULTS = {
     },
     # cell types from multi-views (config.yml:297-299): the views per sample of the view network
     'celltypes': {'nb_views_model': 20},
+    # skeletons from the label volume (config.yml:211); False selects the mesh-based fallback, which is not built
+    'use_kimimaro': True,
 }
 
 
